@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py - PSD frames/s of the MI355X-native IQ -> spectrum path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (any N: spawns one worker per GPU itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (spawns one worker per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W        (same result)
+
+A plain run times the headline only: set-up, the pre-roll, W warm-up steps, then ONE fenced region of exactly K steps in
+the `value` submission mode (below); `ms_per_step` = that region / K, `value` = frames of the K steps / that region.
+--dump-outputs DIR then writes what the last timed step computed (dump_outputs()).  --full runs everything else
+described here as well - the three submission modes over --reps regions, the per-frame scalar leg, the kernel-alone
+pass, shader clock and copy bandwidth, parity, the CPU baselines and the short legs of the other configurations - and
+reports the headline from those regions; the options that steer those parts act with --full only.
 
 Workload (config C3 of BASELINE.json / SURVEY.md 8(d), the one the metric is quoted on):
 HackRF-shaped 20 Msps int8 IQ, N = 16384, hop = N/2, one second of IQ per step = 20e6 samples
@@ -12,7 +19,7 @@ HackRF-shaped 20 Msps int8 IQ, N = 16384, hop = N/2, one second of IQ per step =
 the hot path over that second; consecutive steps walk a ring of distinct seconds (input + output of the ring
 are several times the 256 MiB Infinity Cache) so the traffic really goes to HBM.
 
-Three ways of submitting the same K steps are timed, all in the line:
+With --full, three ways of submitting the same K steps are timed, all in the line:
   value          `--batch` queued seconds per call (tdsa_process_dev_batch: one persistent launch consumes them;
                  the per-launch costs - cold fetch of window / twiddles, hold merge, ragged last round of frames
                  over the CUs - are paid once per launch instead of once per second), calls rotating over
@@ -21,7 +28,7 @@ Three ways of submitting the same K steps are timed, all in the line:
   value_serial   one second per launch, strictly serial full-chip launches
 Results are bit-identical in all three (tests/test_gpu_parity.py::test_batched_captures_*).
 
-The default run (C3) then appends SHORT legs of the other three GPU configurations of BASELINE.json - C2, C4 as named
+The --full run (C3) then appends SHORT legs of the other three GPU configurations of BASELINE.json - C2, C4 as named
 (65 536 frames x 8192 points) and C5 - each with its own parity block, under `roofline.other_configs`; at N > 1 they are
 sharded over the same ranks (C4's frames and C5's segments split over the world - with the cross-rank Welch combine inside
 every step - plus C5 with whole captures per rank): one driver run per N carries every configuration's curve.  Also the
@@ -42,7 +49,7 @@ writes its own rows).
       `welch.combine_ms` is what a step pays for it;
   --c5-shard captures (weak scaling): every rank averages whole captures of its own; nothing to combine.
 
-Timing: after W warm-up steps the step loop of K x `inner` steps is timed `--reps` times, each time
+Timing (--full): after W warm-up steps the step loop of K x `inner` steps is timed `--reps` times, each time
 fenced (device synchronize + host barrier) on both sides; `inner` is chosen so that one timed region
 lasts >= --min-region-s (0.5 s) whatever K is; the MEDIAN repetition (max over ranks) gives ms_per_step and value.
 
@@ -134,7 +141,7 @@ def synth_iq_int8_device(n_samples: int, nfft: int, seed: int, dev, torch):
     3N/7 + 0.5} with 40 / 12 / 3 LSB, a (2 + 1j) LSB DC offset, complex Gaussian noise sigma = 4 LSB, rounded and
     clipped to interleaved int8.  Same model as utils/synthetic.synth_iq_int8, whose numpy version needs 25 s for the
     2^26 samples of C5 and minutes for the 2^29 of C4; the noise comes from torch.Generator(seed) instead of
-    np.random.default_rng(seed).  Used for the short legs of the default run and for C4; --synth picks."""
+    np.random.default_rng(seed).  Used for the short legs of the --full run and for C4; --synth picks."""
     gen = torch.Generator(device=dev)
     gen.manual_seed(1000 + seed)
     out = torch.empty(2 * n_samples, dtype=torch.int8, device=dev)
@@ -194,6 +201,27 @@ class _DryEngine:
             if c:
                 acc += np.asarray(m, dtype=np.float64) * c
         return acc / float(sum(counts))
+
+
+DUMP_ROW_BYTES = 32 << 20      # rows of one step beyond this: a fixed, seeded sample of them
+
+
+def dump_outputs(path: str, rows_dev, hold, torch) -> dict:
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float32 .npy files -
+    rows.npy (its dB rows; when they exceed DUMP_ROW_BYTES, the rows numbered in row_index.npy, drawn without
+    replacement by np.random.default_rng(0)) and hold_max.npy (the max-hold trace, where the workload keeps one)."""
+    os.makedirs(path, exist_ok=True)
+    n_rows, nfft = rows_dev.shape
+    keep = max(1, min(n_rows, DUMP_ROW_BYTES // (4 * nfft)))
+    idx = np.arange(n_rows) if keep == n_rows else np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+    arrays = {"rows": rows_dev[torch.from_numpy(idx).to(rows_dev.device)].cpu().numpy(),
+              "row_index": idx.astype(np.float64)}
+    if hold is not None:
+        arrays["hold_max"] = hold
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if name == "row_index"
+                                                                        else np.float32))
+    return {"dir": path, "files": {n + ".npy": list(a.shape) for n, a in arrays.items()}, "rows_of_step": n_rows}
 
 
 def _free_port() -> int:
@@ -299,7 +327,7 @@ def run_config(args, comm: Comm, torch) -> dict:
         eng = _DryEngine(nfft, rank)
         visible, dev_index = 0, -1
         step = lambda i: eng.step()                   # noqa: E731
-        step_batch = lambda j: eng.step(batch)        # noqa: E731
+        step_batch = lambda j, count=batch: eng.step(count)     # noqa: E731
         dev_sync = lambda: None                       # noqa: E731
         streams = 1
         base = None
@@ -371,9 +399,9 @@ def run_config(args, comm: Comm, torch) -> dict:
             if my_frames:
                 eng.process_device(nat.IN_I8, in_ring[r].data_ptr(), my_ns, hop, my_frames, out_ring[r].data_ptr())
 
-        def step_batch(j: int) -> None:                # `batch` queued steps in one call
-            r = (j * batch) % ring
-            eng.process_device_batch(nat.IN_I8, in_ring[r].data_ptr(), in_stride_b, batch, my_ns, hop, my_frames,
+        def step_batch(j: int, count: int = batch) -> None:    # `count` (<= batch) queued steps in one call
+            r = (j * batch) % ring                     # ring is whole batches: slots r .. r + count - 1 exist
+            eng.process_device_batch(nat.IN_I8, in_ring[r].data_ptr(), in_stride_b, count, my_ns, hop, my_frames,
                                      out_ring[r].data_ptr(), out_stride_f)
 
         def dev_sync() -> None:
@@ -508,7 +536,7 @@ def run_config(args, comm: Comm, torch) -> dict:
 
     # clocks: an idle MI355X needs a few hundred ms of load before shader/fabric clocks settle; this
     # untimed pre-roll keeps short --steps/--warmup runs from measuring the ramp
-    only = args.legs
+    only = args.legs if args.full else "value"
     pre_call = step_batch if (only == "value" and batch > 1) else step
     t_pre = time.perf_counter()
     i_pre = 0
@@ -517,6 +545,68 @@ def run_config(args, comm: Comm, torch) -> dict:
             pre_call(i_pre)
             i_pre += 1
         dev_sync()
+
+    metric = ("PSD frames/sec at 16384-pt FFT on synthetic 20 Msps IQ" if args.config == "c3"
+              else f"PSD frames/sec ({args.config})")
+    data = (("synthetic" + (" (SURVEY 8(d) signal model evaluated on the device, noise from torch.Generator)"
+                            if synth == "device" else ""))
+            if not args.dry_run else "dry-run (stand-in engine, no GPU work, no perf meaning)")
+    total_frames = frames if strong else world * frames          # frames (segments) one step covers, all ranks together
+
+    def release() -> None:
+        if slab is not None:
+            host_barrier()
+            if peer and rank != 0:                    # rank 0 unmaps the other ranks' buffers before their owners free them
+                host_barrier()
+            slab.close()
+            if peer and rank == 0:
+                host_barrier()
+        if not args.dry_run:
+            eng.close()
+
+    if not args.full:
+        # ---- the plain run: the `value` submission mode only, --warmup steps, then ONE timed region of exactly --steps
+        #      steps (whole calls of `batch` queued steps, the remainder in one shorter call)
+        def run_steps(n: int) -> None:
+            if batch == 1:
+                for i in range(n):
+                    (step_combined if combine else step)(i)
+                return
+            calls, rest = divmod(n, batch)
+            for j in range(calls):
+                step_batch(j)
+            if rest:
+                step_batch(calls, rest)
+
+        if not args.dry_run:
+            eng.set_overlap(streams)
+        if slab is not None:
+            fence()
+            combine_state["n"] = 0
+            slab.reset()
+            host_barrier()
+        run_steps(args.warmup)
+        t_region = timed_loop(1, lambda _: run_steps(args.steps))
+        result = None
+        if rank == 0:
+            result = {"metric": metric, "value": total_frames * args.steps / t_region, "unit": "frames/s",
+                      "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                      "ms_per_step": t_region / args.steps * 1e3, "higher_is_better": True,
+                      "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": data,
+                      "timing": {"steps_timed": args.steps, "region_ms": t_region * 1e3,
+                                 "steps_per_call": batch, "streams_per_gpu": streams,
+                                 "statistic": "one timed region of --steps steps after --warmup steps (max over ranks)",
+                                 "full_run": "bench.py --full adds the other submission modes, parity, CPU baselines, "
+                                             "roofline figures and the other configurations"}}
+            if args.dump_outputs:
+                # the last timed step wrote ring slot (steps - 1) % ring; rows of a slot only ever come from the same input
+                hold = None if welch else eng.hold()[0]
+                result["outputs"] = dump_outputs(args.dump_outputs, out_ring[(args.steps - 1) % ring], hold, torch)
+        release()
+        if not args.dry_run:
+            del in_ring, out_ring
+            torch.cuda.empty_cache()
+        return result
 
     legs = {}
     compute_only = None
@@ -570,7 +660,6 @@ def run_config(args, comm: Comm, torch) -> dict:
                   "read; the alternative - tdsa_rows_stats, a second pass over the 160 MB of rows per step - costs more than the "
                   "spectra themselves (profiles/r06_frame_stats.txt)"}
     steps_timed = head["steps"]
-    total_frames = frames if strong else world * frames          # frames (segments) one step covers, all ranks together
     per_rank_fps = [my_f * steps_timed / t for my_f, t in zip(counts, head["per_rank"])]
 
     # ---- dominant kernel alone: HIP events on the plan's stream around every frame-kernel launch,
@@ -756,8 +845,7 @@ def run_config(args, comm: Comm, torch) -> dict:
             par = (f"frames sharded over {world} GPU(s), one process + plan per GPU, no collective "
                    f"(host gloo barrier around the timed region, hold traces combined with np.fmax)")
         result = {
-            "metric": "PSD frames/sec at 16384-pt FFT on synthetic 20 Msps IQ" if args.config == "c3"
-                      else f"PSD frames/sec ({args.config})",
+            "metric": metric,
             "value": value,
             "unit": "frames/s",
             "n_gpus": world,
@@ -768,9 +856,7 @@ def run_config(args, comm: Comm, torch) -> dict:
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
             "dtype": "f32",
-            "data": ("synthetic" + (" (SURVEY 8(d) signal model evaluated on the device, noise from torch.Generator)"
-                                    if synth == "device" else ""))
-                    if not args.dry_run else "dry-run (stand-in engine, no GPU work, no perf meaning)",
+            "data": data,
             "value_streams": rate(legs["streams"]),
             "ms_per_step_streams": legs["streams"]["med"] / legs["streams"]["steps"] * 1e3,
             "value_serial": rate(legs["serial"]),
@@ -1065,15 +1151,8 @@ def run_config(args, comm: Comm, torch) -> dict:
                     result["cpu_baseline_pool"] = cpu_all_cores(wl, workers, args.cpu_pool_seconds)
                 except Exception as exc:               # a reported extra, never a reason to lose the bench line
                     result["cpu_baseline_pool"] = {"value": None, "error": str(exc)}
-    if slab is not None:
-        host_barrier()
-        if peer and rank != 0:                        # rank 0 unmaps the other ranks' buffers before their owners free them
-            host_barrier()
-        slab.close()
-        if peer and rank == 0:
-            host_barrier()
+    release()
     if not args.dry_run:
-        eng.close()
         del in_ring, out_ring
         torch.cuda.empty_cache()
     return result
@@ -1120,14 +1199,23 @@ def main() -> None:
     ap.add_argument("--synth", default="auto", choices=["auto", "numpy", "device"],
                     help="where the synthetic IQ is made: numpy (np.random.default_rng, SURVEY 8(d) to the letter; minutes for "
                          "C4), device (the same model in float64 torch ops, noise from torch.Generator); auto = numpy except "
-                         "for C4 and the short legs of the default run")
+                         "for C4 and the short legs of the --full run")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run only: skip the short C2 / C4 / C5 legs appended under roofline.other_configs")
+                    help="--full run only: skip the short C2 / C4 / C5 legs appended under roofline.other_configs")
     ap.add_argument("--dry-other-configs", action="store_true",
                     help="with --dry-run: also walk the short C2 / C4 / C5 legs (tests of the multi-rank plumbing)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: exercise spawn / barrier / aggregation with a stand-in engine (no perf meaning)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: all three submission modes timed over --reps regions, parity "
+                         "against the float64 oracle, CPU baselines, roofline and kernel figures, the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as float32 .npy files into DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.dry_run or args.full):
+        ap.error("--dump-outputs belongs to a plain run on a GPU (no --dry-run, no --full)")
     args.short_leg = False
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1162,11 +1250,11 @@ def main() -> None:
     t_run0 = time.perf_counter()
     result = run_config(args, comm, torch)
 
-    # ---- the default run: short legs of the other GPU configurations, one driver run for all four (round-4 verdict) ----
+    # ---- the --full run: short legs of the other GPU configurations, one driver run for all four (round-4 verdict) ----
     # At N > 1 the same legs run sharded over the ranks - C4 as named (its 65 536 frames split over the world), C5 both ways
     # (the segments of one capture over the ranks with the cross-rank combine inside each step = the strong-scaling curve
     # north_star names, and whole captures per rank) - so that one driver run per N yields every configuration's curve.
-    want_others = (args.config == "c3" and not args.no_other_configs and args.legs == "all"
+    want_others = (args.full and args.config == "c3" and not args.no_other_configs and args.legs == "all"
                    and (not args.dry_run or args.dry_other_configs))
     if want_others:
         others = {}

@@ -1,11 +1,13 @@
-"""bench.py launch conventions (no GPU): `python bench.py --gpus N` spawns its own workers, ranks meet over
-gloo on 127.0.0.1, rank 0 prints ONE well-formed JSON line; the same under torch.distributed.run.  The
-stand-in engine of --dry-run does no arithmetic: only the plumbing of the multi-GPU leg is exercised."""
+"""bench.py launch conventions (no GPU, except the --dump-outputs test): `python bench.py --gpus N` spawns its own
+workers, ranks meet over gloo on 127.0.0.1, rank 0 prints ONE well-formed JSON line; the same under
+torch.distributed.run.  The stand-in engine of --dry-run does no arithmetic: only the plumbing of the multi-GPU leg is
+exercised."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -47,7 +49,7 @@ def _check_line(d, n):
 @pytest.mark.parametrize("n", [1, 2])
 def test_bench_spawns_its_own_workers(n):
     d = _run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "40", "--warmup", "3", "--reps", "3", "--dry-run",
-              "--min-region-s", "0.05"])
+              "--min-region-s", "0.05", "--full"])
     _check_line(d, n)
     assert d["config"]["launcher"] == ("self-spawned workers" if n > 1 else "single process")
 
@@ -55,7 +57,7 @@ def test_bench_spawns_its_own_workers(n):
 def test_bench_under_torch_distributed_run():
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
               "127.0.0.1", "--master-port", "29517", "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "3",
-              "--reps", "3", "--dry-run", "--min-region-s", "0.05"])
+              "--reps", "3", "--dry-run", "--min-region-s", "0.05", "--full"])
     _check_line(d, 2)
     assert d["config"]["launcher"] == "torch.distributed.run"
 
@@ -67,7 +69,7 @@ def test_bench_c5_shards_the_welch_segments_over_the_ranks(n):
     utils/signal_processing.py:35-61 of the reference is the running mean being reassembled).  The stand-in engine of
     --dry-run reports the constant rank + 1 as its partial mean: the combined mean is the count-weighted average."""
     d = _run([sys.executable, "bench.py", "--gpus", str(n), "--config", "c5", "--steps", "4", "--warmup", "1", "--reps", "2",
-              "--dry-run", "--min-region-s", "0.05"])
+              "--dry-run", "--min-region-s", "0.05", "--full"])
     assert d["n_gpus"] == n and d["scaling"] == "strong" and d["metric"] == "PSD frames/sec (c5)"
     w = d["welch"]
     counts = w["segments_per_rank"]
@@ -94,7 +96,7 @@ def test_bench_c5_shards_the_welch_segments_over_the_ranks(n):
 def test_bench_c5_whole_captures_per_rank(n):
     """--c5-shard captures: every rank averages whole captures of 64 segments - weak scaling, nothing to combine."""
     d = _run([sys.executable, "bench.py", "--gpus", str(n), "--config", "c5", "--c5-shard", "captures", "--steps", "4",
-              "--warmup", "1", "--reps", "2", "--dry-run", "--min-region-s", "0.05"])
+              "--warmup", "1", "--reps", "2", "--dry-run", "--min-region-s", "0.05", "--full"])
     assert d["n_gpus"] == n and d["scaling"] == "weak"
     assert d["welch"]["shard"] == "captures" and d["welch"]["combine_ms"] == 0.0
     assert d["welch"]["segments_per_rank"] == [64] * n and d["config"]["frames_per_step_all_gpus"] == 64 * n
@@ -106,7 +108,7 @@ def test_bench_c4_is_the_named_waterfall_sharded_over_the_ranks(n):
     """--config c4: BASELINE config 4 as named - ONE waterfall of 65 536 frames x 8192 points (displays/waterfall.py:163-180
     is the layout its rows have), its frames sharded over the ranks in contiguous ranges: strong scaling, no combine."""
     d = _run([sys.executable, "bench.py", "--gpus", str(n), "--config", "c4", "--steps", "4", "--warmup", "1", "--reps", "2",
-              "--dry-run", "--min-region-s", "0.05"])
+              "--dry-run", "--min-region-s", "0.05", "--full"])
     assert d["scaling"] == "strong" and d["config"]["frames_per_step_all_gpus"] == 65536
     assert d["config"]["frames_per_step_per_rank"] == [65536 // n] * n and d["config"]["steps_per_call"] == 1
     assert "sharded over" in d["config"]["parallelism"] and "no collective" in d["config"]["parallelism"]
@@ -119,7 +121,7 @@ def test_default_run_carries_the_other_configurations_at_every_world_size(n):
     with the segments of one capture split (strong; cross-rank combine inside the step) and with whole captures per rank
     (weak) - so that one driver run per N yields every configuration's curve."""
     d = _run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "40", "--warmup", "3", "--reps", "3", "--dry-run",
-              "--dry-other-configs", "--min-region-s", "0.05"])
+              "--dry-other-configs", "--min-region-s", "0.05", "--full"])
     _check_line(d, n)
     oc = d["roofline"]["other_configs"]
     assert set(oc) == ({"c2", "c4", "c5"} | ({"c5_captures"} if n > 1 else set())), oc.keys()
@@ -135,6 +137,40 @@ def test_default_run_carries_the_other_configurations_at_every_world_size(n):
         assert oc["c5"]["welch"]["combine_ms"] >= 0.0 and "value_compute_only" in oc["c5"]
         assert oc["c5_captures"]["scaling"] == "weak" and oc["c5_captures"]["frames_per_step"] == 64 * n
         assert oc["c5_captures"]["welch"]["shard"] == "captures"
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_run_times_exactly_the_steps_and_nothing_else(n):
+    """Without --full the line carries the headline only, timed over exactly --steps steps (13: one call of 8 queued steps
+    and one of 5); the other submission modes, parity, CPU legs, roofline and other configurations belong to --full."""
+    d = _run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "13", "--warmup", "3", "--dry-run"])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 13 and d["timing"]["steps_timed"] == 13 and d["warmup"] == 3 and d["n_gpus"] == n
+    assert abs(d["ms_per_step"] * 13 - d["timing"]["region_ms"]) < 1e-9 and d["value"] > 0
+    assert d["metric"].startswith("PSD frames/sec at 16384-pt FFT") and d["unit"] == "frames/s" and d["higher_is_better"]
+    for key in ("roofline", "parity", "cpu_baseline", "value_serial", "value_streams", "hold_trace"):
+        assert key not in d, key
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_last_step_and_repeat_exactly(tmp_path):
+    """--dump-outputs DIR: the last timed step's dB rows (a seeded sample of 512 of its 2440 rows) and the max-hold trace,
+    float32, well under 64 MB, identical in two runs with the same arguments; the hold trace bounds every dumped row."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "4", "--dump-outputs", str(out)])
+        assert d["steps"] == 12 and d["ms_per_step"] > 0 and d["outputs"]["rows_of_step"] == 2440
+        files = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert set(files) == {"rows.npy", "row_index.npy", "hold_max.npy"}
+        assert sum((out / f).stat().st_size for f in files) <= 64 << 20
+        assert files["rows.npy"].shape == (512, 16384) and files["rows.npy"].dtype == np.float32
+        assert files["hold_max.npy"].shape == (16384,) and files["hold_max.npy"].dtype == np.float32
+        assert np.all(np.isfinite(files["rows.npy"])) and np.all(files["rows.npy"] <= files["hold_max.npy"])
+        runs.append(files)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
 
 
 def test_bench_workers_are_all_reaped_when_one_fails(tmp_path):

@@ -955,7 +955,7 @@ def test_trace_averager_golden(pkg, golden_dir):
 def test_trace_averager_as_the_reference_smoke_checks_it(pkg):
     """The three TraceAverager checks of the reference's test_smoke.py:137-175 (passthrough when inactive, first
     frame == input and the second blends towards it, reset clears a NaN buffer), on the device-backed class.
-    (tests/test_reference_own_tests.py runs the reference's file itself for everything that needs no GPU.)"""
+    (tests/test_reference_differential.py compares the host pieces that need no GPU with the reference's results.)"""
     ta = pkg.TraceAverager()
     ones = np.ones(128, dtype=np.float64)
     assert ta.is_active is False
@@ -1571,7 +1571,8 @@ def test_welch_partials_read_in_place_from_another_process(pkg):
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29547", "bench.py", "--gpus", "2", "--config", "c5",
-                          "--c5-combine", "peer", "--steps", "10", "--warmup", "2", "--reps", "2", "--min-region-s", "0.1"],
+                          "--c5-combine", "peer", "--steps", "10", "--warmup", "2", "--reps", "2", "--min-region-s", "0.1",
+                          "--full"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

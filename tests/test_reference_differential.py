@@ -1,8 +1,15 @@
-"""Live differential tests against the IMPORTED reference, for the host-side pieces of DataProcessor that carry no GPU
-work (peak search, NaN clean-up, zero-span view with its trigger, peak-list read-out).  They run where
-/root/reference exists (the build container) and are skipped elsewhere (the GPU box has no reference); the committed
-fixtures of tests/golden/ pin the same functions there.  Nothing is copied: both implementations are driven with
-the same seeded random inputs through plain stub objects and must agree exactly."""
+"""Differential tests against the reference, for the host-side pieces of DataProcessor that carry no GPU work (peak
+search, NaN clean-up, zero-span view with its trigger, peak-list read-out), the CPU oracle and the display
+accumulators.  Both implementations are driven with the same seeded random inputs through plain stub objects and
+must agree exactly.
+
+The reference's results are replayed from tests/golden/differential.json: for every trial of every test, a digest of
+the values the reference returned, in the order the test compares them (plus the few plain numbers the test reads
+from the reference's objects).  tests/golden/make_golden_differential.py records that file by running this module
+against the imported reference (TDSA_REFERENCE=<reference tree>, TDSA_RECORD_REFERENCE=1); while recording, every
+comparison is also asserted live.  Nothing of the reference is copied."""
+import hashlib
+import json
 import os
 import sys
 import types
@@ -11,8 +18,123 @@ from unittest.mock import MagicMock
 import numpy as np
 import pytest
 
-REF = os.environ.get("TDSA_REFERENCE", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "core")), reason="reference tree not present")
+RECORD = os.environ.get("TDSA_RECORD_REFERENCE") == "1"
+REF = os.environ.get("TDSA_REFERENCE", "")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "differential.json")
+if RECORD and not os.path.isdir(os.path.join(REF, "core")):
+    raise RuntimeError("TDSA_RECORD_REFERENCE=1 needs TDSA_REFERENCE=<reference tree>")
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# recorded reference results
+# ----------------------------------------------------------------------------------------------------------------
+def _canon(x):
+    """x as the tests compare it: numeric arrays by shape and values (any numeric dtype; NaN equals NaN, -0.0 equals
+    0.0), numbers by value, containers element by element (a list is not a tuple)."""
+    if isinstance(x, np.ndarray) and x.dtype.kind in "biufc":
+        a = np.asarray(x, dtype=np.complex128)
+        parts = []
+        for p in (a.real + 0.0, a.imag + 0.0):
+            p = np.array(p, dtype=np.float64)
+            p[np.isnan(p)] = np.nan
+            parts.append(p.tobytes())
+        return ["nd", list(a.shape), hashlib.sha256(b"".join(parts)).hexdigest()[:16]]
+    if x is None or isinstance(x, str):
+        return x
+    if isinstance(x, (bool, np.bool_, int, np.integer, float, np.floating)):
+        return ["n", repr(float(x) + 0.0)]                  # 2048 == 2048.0 == np.float32(2048), as == has it
+    if isinstance(x, (complex, np.complexfloating)):
+        return _canon(x.real) if x.imag == 0 else ["n", repr(float(x.real) + 0.0), repr(float(x.imag) + 0.0)]
+    if isinstance(x, (tuple, list)):
+        return [type(x).__name__, [_canon(e) for e in x]]
+    if isinstance(x, dict):
+        return ["dict", [[_canon(k), _canon(v)] for k, v in sorted(x.items())]]
+    raise TypeError(f"no canonical form for {type(x).__name__}")
+
+
+class Tape:
+    """The reference's side of one test.  Recording: want(fn) calls the reference, check(got, want) asserts
+    canon(got) == canon(want) and feeds canon(want) into the running digest of the trial, value(fn) keeps a plain
+    number.  Replaying: want() computes nothing, check() feeds canon(got), value() hands the recorded number back, and
+    the digest of every trial must equal the recorded one."""
+
+    def __init__(self, name, book):
+        self.name, self.book, self.i, self.k = name, book, 0, 0
+        self.h = hashlib.sha256()
+        if RECORD:
+            book[name] = {"trials": [], "values": []}
+        else:
+            assert name in book, f"{name}: no recorded reference results in {os.path.basename(FIXTURE)}"
+        self.rec = book[name]
+
+    def want(self, fn):
+        return fn() if RECORD else None
+
+    def check(self, got, want, what=None):
+        if RECORD:
+            assert _canon(got) == _canon(want), (self.name, self.i, what)
+        self.h.update(json.dumps(_canon(want if RECORD else got)).encode())
+
+    def value(self, fn):
+        if RECORD:
+            v = fn()
+            self.rec["values"].append(v)
+            return v
+        v = self.rec["values"][self.k]
+        self.k += 1
+        return v
+
+    def trial(self):
+        d = self.h.hexdigest()[:16]
+        if RECORD:
+            self.rec["trials"].append(d)
+        else:
+            assert self.i < len(self.rec["trials"]), (self.name, "more trials than recorded")
+            assert d == self.rec["trials"][self.i], (self.name, f"trial {self.i} differs from the reference's results")
+        self.i += 1
+        self.h = hashlib.sha256()
+
+    def finish(self):
+        if not RECORD:
+            assert self.i == len(self.rec["trials"]) and self.k == len(self.rec["values"]), self.name
+
+
+@pytest.fixture(scope="module")
+def book():
+    if not RECORD:
+        with open(FIXTURE) as f:
+            yield json.load(f)
+        return
+    rec = {}
+    yield rec
+    with open(FIXTURE + ".new", "w") as f:              # make_golden_differential.py keeps it when every test passed
+        json.dump(rec, f, indent=0, sort_keys=True)
+
+
+@pytest.fixture
+def tape(book, request):
+    t = Tape(request.node.name, book)
+    yield t
+    t.finish()
+
+
+class _Absent:
+    """The reference's objects while its results are replayed: any attribute, call or assignment, and nothing
+    computed (every value of the reference goes through Tape.want / Tape.value)."""
+
+    def __init__(self, *a, **k):
+        pass
+
+    def __getattr__(self, name):
+        if name.startswith("__"):
+            raise AttributeError(name)
+        return _Absent()
+
+    def __setattr__(self, name, value):
+        pass
+
+    def __call__(self, *a, **k):
+        return _Absent()
 
 
 def _forget_reference_modules(before, stubs=()):
@@ -32,9 +154,10 @@ def _forget_reference_modules(before, stubs=()):
         sys.modules.pop(name, None)
 
 
-
 @pytest.fixture(scope="module")
 def ref_dp():
+    if not RECORD:
+        return _Absent()
     sys.dont_write_bytecode = True                       # never leave __pycache__ in the reference tree
     before = set(sys.modules)
     mocked = [m for m in ("hackrf", "rtlsdr", "sounddevice") if m not in sys.modules]
@@ -70,7 +193,7 @@ def _bare(cls, mw, dm):
     return dp
 
 
-def test_find_top_peaks_random(ref_dp, our_dp):
+def test_find_top_peaks_random(ref_dp, our_dp, tape):
     rng = np.random.default_rng(11)
     for case in range(400):
         n = int(rng.integers(3, 3000))
@@ -81,24 +204,27 @@ def test_find_top_peaks_random(ref_dp, our_dp):
         tr = (10 * np.log10(p + 1e-15)).astype(np.float32 if rng.integers(0, 2) else np.float64)
         bins = np.linspace(88e6, 108e6, n)
         kw = dict(n=int(rng.integers(1, 9)), min_sep_bins=int(rng.integers(1, 60)), min_excursion_db=float(rng.choice([3.0, 6.0, 10.0])))
-        want = ref_dp._find_top_peaks(bins, tr, **kw)
+        want = tape.want(lambda: ref_dp._find_top_peaks(bins, tr, **kw))
         got = our_dp._find_top_peaks(bins, tr, **kw)
-        assert got == want, (case, kw)
+        tape.check(got, want, (case, kw))
+        tape.trial()
 
 
-def test_nan_safe_random(ref_dp, our_dp):
+def test_nan_safe_random(ref_dp, our_dp, tape):
     rng = np.random.default_rng(12)
     for case in range(200):
         a = rng.normal(-70, 10, int(rng.integers(1, 500))).astype(np.float32 if rng.integers(0, 2) else np.float64)
         if rng.integers(0, 2):
             a[rng.integers(0, a.size, int(rng.integers(1, 4)))] = np.nan
         fill = float(rng.choice([-500.0, 500.0]))
-        want, got = ref_dp._nan_safe(a, fill), our_dp._nan_safe(a, fill)
-        assert np.array_equal(got, want) and got.dtype == want.dtype
-        assert (got is a) == (want is a)                 # a clean array comes back as the same object in both
+        want, got = tape.want(lambda: ref_dp._nan_safe(a, fill)), our_dp._nan_safe(a, fill)
+        tape.check(got, want)
+        tape.check(got.dtype.str, tape.want(lambda: want.dtype.str))
+        tape.check(got is a, tape.want(lambda: want is a))   # a clean array comes back as the same object in both
+        tape.trial()
 
 
-def test_zero_span_random_histories(ref_dp, our_dp):
+def test_zero_span_random_histories(ref_dp, our_dp, tape):
     class W:
         t = y = None
 
@@ -109,7 +235,7 @@ def test_zero_span_random_histories(ref_dp, our_dp):
     for trial in range(30):
         rate = float(rng.choice([8000.0, 44100.0, 2_000_000.0]))
         pair = []
-        for cls in (ref_dp, our_dp):
+        for cls in ((ref_dp, our_dp) if RECORD else (our_dp,)):
             src = types.SimpleNamespace(sample_rate=rate, block=None)
             src.read_samples_only = (lambda s=src: s.block)
             mw = types.SimpleNamespace(current_source=src, zero_span_widget=W())
@@ -141,15 +267,15 @@ def test_zero_span_random_histories(ref_dp, our_dp):
             for dp, src, _, _ in pair:
                 src.block = None if block is None else block.copy()
                 dp._process_zero_span_data()
-            (rw, ow) = (pair[0][2].zero_span_widget, pair[1][2].zero_span_widget)
-            assert (rw.y is None) == (ow.y is None), (trial, step)
-            if rw.y is not None:
-                assert np.array_equal(ow.y, rw.y) and np.array_equal(ow.t, rw.t), (trial, step)
-            rb, ob = pair[0][3].zero_span_buffer, pair[1][3].zero_span_buffer
-            assert (rb is None) == (ob is None) and (rb is None or np.array_equal(ob, rb)), (trial, step)
+            ow, ob = pair[-1][2].zero_span_widget, pair[-1][3].zero_span_buffer
+            rw = tape.want(lambda: pair[0][2].zero_span_widget)
+            rb = tape.want(lambda: pair[0][3].zero_span_buffer)
+            tape.check((ow.t, ow.y), tape.want(lambda: (rw.t, rw.y)), (trial, step))
+            tape.check(ob, rb, (trial, step))
+        tape.trial()
 
 
-def test_peak_list_readout_random(ref_dp, our_dp):
+def test_peak_list_readout_random(ref_dp, our_dp, tape):
     class TwoD:
         peaks = None
 
@@ -162,23 +288,25 @@ def test_peak_list_readout_random(ref_dp, our_dp):
         tr = (rng.normal(-90, 4, n) + 40 * (rng.random(n) < 0.01)).astype(np.float32)
         bins = np.linspace(2.4e9, 2.5e9, n)
         exc = float(rng.choice([3.0, 6.0, 8.0, 10.0]))
-        out = []
-        for cls in (ref_dp, our_dp):
+
+        def readout(cls):
             mw = types.SimpleNamespace(two_d_widget=TwoD(), marker_readout_label=_Label(), peak_excursion=exc)
             dp = _bare(cls, mw, types.SimpleNamespace(peak_list_enabled=True))
             dp._update_peak_list(bins, tr)
-            out.append((mw.marker_readout_label.text, mw.two_d_widget.peaks))
-        assert out[0][0] == out[1][0], case
-        assert out[0][1] == out[1][1], case
+            return mw.marker_readout_label.text, mw.two_d_widget.peaks
+        tape.check(readout(our_dp), tape.want(lambda: readout(ref_dp)), case)
+        tape.trial()
 
 
 # ----------------------------------------------------------------------------------------------------------------
-# the ORACLE against the imported reference on random inputs: oracle/spectrum_oracle.py (precision="ref") has to be
+# the ORACLE against the reference on random inputs: oracle/spectrum_oracle.py (precision="ref") has to be
 # np.array_equal to what the reference's own source classes return, frame by frame, through random knob histories -
-# the committed fixtures pin the same thing at fixed inputs, this pins it at thousands more
+# the other fixtures of tests/golden pin the same thing at fixed inputs, this pins it at thousands more
 # ----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def ref_sources():
+    if not RECORD:
+        return _Absent()
     sys.dont_write_bytecode = True
     before = set(sys.modules)
     mocked = [m for m in ("hackrf", "rtlsdr", "sounddevice") if m not in sys.modules]
@@ -197,7 +325,7 @@ def ref_sources():
                                  audio=MicrophoneSamplesDataSource, averager=TraceAverager)
 
 
-def test_oracle_hackrf_branch_random_histories(ref_sources):
+def test_oracle_hackrf_branch_random_histories(ref_sources, tape):
     from oracle import spectrum_oracle as so
     rng = np.random.default_rng(21)
     for trial in range(12):
@@ -228,14 +356,15 @@ def test_oracle_hackrf_branch_random_histories(ref_sources):
                 br.dc_alpha = a
             fr = x[k * n:(k + 1) * n]
             src._reservoir = np.array(fr, dtype=np.complex64, copy=True)
-            want, _ = src.get_power_levels()
+            want = tape.want(lambda: src.get_power_levels()[0])
             got = br.power_levels(np.array(fr, copy=True))
-            assert np.asarray(got).dtype == np.asarray(want).dtype, (trial, k)
-            assert np.array_equal(got, want), (trial, k, n, br.averager.mode, br.use_psd, br.dc_alpha)
-        assert complex(br.dc_estimate) == complex(src._dc_estimate)
+            tape.check(np.asarray(got).dtype.str, tape.want(lambda: np.asarray(want).dtype.str), (trial, k))
+            tape.check(got, want, (trial, k, n, br.averager.mode, br.use_psd, br.dc_alpha))
+        tape.check(complex(br.dc_estimate), tape.want(lambda: complex(src._dc_estimate)))
+        tape.trial()
 
 
-def test_oracle_rtl_branch_random_histories(ref_sources):
+def test_oracle_rtl_branch_random_histories(ref_sources, tape):
     from oracle import spectrum_oracle as so
 
     class Sdr:
@@ -274,12 +403,13 @@ def test_oracle_rtl_branch_random_histories(ref_sources):
                 psd = bool(rng.integers(0, 2))
                 src.set_psd_mode(psd)
                 br.use_psd = psd
-            want, _ = src.get_power_levels()
+            want = tape.want(lambda: src.get_power_levels()[0])
             got = br.power_levels(x[k * n:(k + 1) * n])
-            assert np.array_equal(got, want), (trial, k, n, br.averager.mode, br.use_psd)
+            tape.check(got, want, (trial, k, n, br.averager.mode, br.use_psd))
+        tape.trial()
 
 
-def test_oracle_trace_averager_random_histories(ref_sources):
+def test_oracle_trace_averager_random_histories(ref_sources, tape):
     from oracle import spectrum_oracle as so
     rng = np.random.default_rng(23)
     for trial in range(40):
@@ -297,68 +427,12 @@ def test_oracle_trace_averager_random_histories(ref_sources):
             elif ev < 0.24:
                 shape = [(64,), (100,), (2, 32)][int(rng.integers(0, 3))]
             xin = (10.0 ** rng.uniform(-12, 3, size=shape)).astype(np.float32 if rng.integers(0, 2) else np.float64)
-            want = np.array(ref.process(xin.copy()), copy=True)
+            want = tape.want(lambda: np.array(ref.process(xin.copy()), copy=True))
             got = np.array(ora.process(xin.copy()), copy=True)
-            assert got.dtype == want.dtype and np.array_equal(got, want), (trial, step)
-            assert ora.is_active == ref.is_active
-
-
-def test_processor_model_against_reference(ref_dp):
-    """The float64 model the GPU suite checks DataProcessor against (tests/test_gpu_parity.py::ProcessorModel) is
-    itself checked here against the reference's DataProcessor._process_sample_data, through the same seeded random
-    GUI histories (holds switched, tare runs, offset and trace-length changes, NaN bins)."""
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import test_gpu_parity as T
-    sys.path.insert(0, REF)
-    try:
-        from core.tare_state import TareState
-    finally:
-        sys.path.remove(REF)
-        for m in [k for k in sys.modules if k == "core" or k.startswith("core.")]:
-            del sys.modules[m]
-    for seed in range(40):
-        rng = np.random.default_rng(8000 + seed)
-        cal = {"v": 0.0}
-        src = types.SimpleNamespace(trace=None, axis=None, last_data_time=0.0)
-        src.get_power_levels = lambda s=src: (s.trace, s.axis)
-        mw = types.SimpleNamespace(current_source=src, status_label=_Label(), tare_active=False, baseline_power_levels=None,
-                                   live_power_levels=None, max_power_levels=None, min_power_levels=None,
-                                   frequency_bins=None, min_hold_enabled=bool(rng.integers(0, 2)))
-        mw.calibration_manager = types.SimpleNamespace(get_offset=lambda source_type: cal["v"])
-        mw.source_manager = types.SimpleNamespace(last_source_type="hackrf_samples")
-        dm = types.SimpleNamespace(tare_state=TareState(), max_peak_search_enabled=bool(rng.integers(0, 2)),
-                                   duty_cycle_enabled=False, peak_list_enabled=False,
-                                   _update_tare_button_label=lambda s: None)
-
-        def _clear():
-            mw.tare_active, mw.baseline_power_levels = False, None
-            dm.tare_state = TareState()
-        dm._clear_tare = _clear
-        dp = ref_dp(mw, dm)
-        model = T.ProcessorModel(alias_quirk=True)           # the reference's own behaviour incl. quirk ii
-        for tick, (event, x) in enumerate(T.processor_history(rng)):
-            if event == ("max",):
-                dm.max_peak_search_enabled = not dm.max_peak_search_enabled
-            elif event == ("min",):
-                mw.min_hold_enabled = not mw.min_hold_enabled
-            elif event == ("tare",):
-                dm.tare_state = TareState(collecting=True)
-                model.start_tare()
-            elif event == ("clear",):
-                dm._clear_tare()
-                model.clear_tare()
-            elif event is not None:
-                cal["v"] = event[1]
-            src.trace, src.axis = x.copy(), np.arange(len(x), dtype=np.float64)
-            dp._process_sample_data()
-            lv = model.frame(x, cal["v"], dm.max_peak_search_enabled, mw.min_hold_enabled)
-            what = (seed, tick)
-            assert mw.tare_active == model.active, what
-            assert np.allclose(mw.live_power_levels, lv, rtol=0, atol=2e-4, equal_nan=True), what
-            for got, want in ((mw.max_power_levels, model.max), (mw.min_power_levels, model.min)):
-                assert (got is None) == (want is None), what
-                if want is not None:
-                    assert np.allclose(got, want, rtol=0, atol=2e-4, equal_nan=True), what
+            tape.check(got.dtype.str, tape.want(lambda: want.dtype.str), (trial, step))
+            tape.check(got, want, (trial, step))
+            tape.check(ora.is_active, tape.want(lambda: ref.is_active), (trial, step))
+        tape.trial()
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -381,6 +455,8 @@ class _Stub:
 
 @pytest.fixture(scope="module")
 def ref_displays():
+    if not RECORD:
+        return _Absent()
     sys.dont_write_bytecode = True
     before = set(sys.modules)
 
@@ -416,7 +492,7 @@ def ref_displays():
 
 
 @pytest.mark.filterwarnings("ignore:invalid value encountered in cast")
-def test_density_oracle_random_streams(ref_displays):
+def test_density_oracle_random_streams(ref_displays, tape):
     from oracle import analytics_oracle as ao
     rng = np.random.default_rng(31)
     for trial in range(30):
@@ -424,7 +500,7 @@ def test_density_oracle_random_streams(ref_displays):
         mode = str(rng.choice(["medium", "fast", "off"]))
         d = ref_displays.density()
         d.set_decay(mode)
-        ora = ao.DensityOracle(float(d._decay))
+        ora = ao.DensityOracle(tape.value(lambda: float(d._decay)))
         fb = np.linspace(99e6, 101e6, n)
         for r in range(int(rng.integers(1, 80))):
             row = rng.normal(rng.uniform(-150, 50), float(rng.choice([0.3, 5.0, 40.0, 150.0])), n).astype(np.float32)
@@ -433,10 +509,11 @@ def test_density_oracle_random_streams(ref_displays):
             with np.errstate(invalid="ignore"):
                 d._update_hist(row, fb)
             ora.update(row)
-            assert np.array_equal(ora.hist, d._hist), (trial, r, mode)
+            tape.check(ora.hist, tape.want(lambda: d._hist), (trial, r, mode))
+        tape.trial()
 
 
-def test_waterfall_oracle_random_streams(ref_displays):
+def test_waterfall_oracle_random_streams(ref_displays, tape):
     from oracle import analytics_oracle as ao
     rng = np.random.default_rng(32)
     for trial in range(30):
@@ -446,20 +523,26 @@ def test_waterfall_oracle_random_streams(ref_displays):
         fb = np.linspace(2.40e9, 2.48e9, nb)
         pool = rng.normal(-90, 5, size=(10, nb)).astype(np.float32)
         ora = None
+        last = None                                     # the row pushed before: what the reference keeps as _last_row
         for step in range(int(rng.integers(5, 80))):
             row = pool[int(rng.integers(0, len(pool)))] if rng.integers(0, 3) else pool[0]
-            before = None if w._last_row is None else w._last_row.copy()
+            tape.check(last, tape.want(lambda: None if w._last_row is None else w._last_row.copy()), (trial, step))
             w.update_widget_data(row, None, fb)
             if ora is None:
-                ora = ao.WaterfallOracle(int(w.history_lines), nb, float(w.wf_min_db))
+                ora = ao.WaterfallOracle(tape.value(lambda: int(w.history_lines)), nb,
+                                         tape.value(lambda: float(w.wf_min_db)))
             new = ora.update(row)
-            assert new == (before is None or not np.array_equal(before, row)), (trial, step)
-            assert ora.ptr == w._ptr, (trial, step)
-            assert np.array_equal(ora.view(), w._display_view()), (trial, step)
+            assert new == (last is None or not np.array_equal(last, row)), (trial, step)
+            last = row.copy()
+            tape.check(ora.ptr, tape.want(lambda: w._ptr), (trial, step))
+            tape.check(ora.view(), tape.want(lambda: w._display_view()), (trial, step))
+        tape.trial()
 
 
 @pytest.fixture(scope="module")
 def ref_analytics():
+    if not RECORD:
+        return _Absent()
     sys.dont_write_bytecode = True
     before = set(sys.modules)
     mocked = [m for m in ("hackrf", "rtlsdr", "sounddevice") if m not in sys.modules]
@@ -476,7 +559,7 @@ def ref_analytics():
     return types.SimpleNamespace(duty=DutyCycleAnalyser, markers=MarkerManager, audio=MicrophoneSamplesDataSource)
 
 
-def test_band_power_oracle_random(ref_analytics):
+def test_band_power_oracle_random(ref_analytics, tape):
     from oracle import analytics_oracle as ao
     rng = np.random.default_rng(41)
     for case in range(300):
@@ -486,15 +569,14 @@ def test_band_power_oracle_random(ref_analytics):
         if rng.integers(0, 4) == 0:
             tr[rng.integers(0, n)] = np.nan
         a, b = rng.uniform(98e6, 102e6, 2)
-        want = ref_analytics.markers._band_power(types.SimpleNamespace(_data=lambda: (fb, tr)), a, b)
+        want = tape.want(lambda: ref_analytics.markers._band_power(types.SimpleNamespace(_data=lambda: (fb, tr)), a, b))
         got = ao.band_power_db(fb, tr, a, b)
-        assert (want is None) == (got is None), case
-        if want is not None:
-            assert (np.isnan(want) and np.isnan(got)) or want == got, (case, want, got)
+        tape.check(got, want, (case, want, got))            # None for None, NaN for NaN, else the same value
+        tape.trial()
 
 
-def test_marker_peak_search_oracle_random(ref_analytics):
-    """oracle.marker_find_peaks / snap_to_peak_bin / snap_to_next_peak_bin against the imported MarkerManager (which
+def test_marker_peak_search_oracle_random(ref_analytics, tape):
+    """oracle.marker_find_peaks / snap_to_peak_bin / snap_to_next_peak_bin against the reference's MarkerManager (which
     runs the real scipy.signal.find_peaks) through random traces, thresholds, excursions and marker positions.
     Pairs of EQUAL maxima closer than 3 bins are broken up first: between those the reference follows numpy's
     unstable argsort (see oracle/analytics_oracle.py::_select_by_distance)."""
@@ -532,25 +614,30 @@ def test_marker_peak_search_oracle_random(ref_analytics):
         mm._sync_display = lambda name: None
         mm._refresh_status = lambda: None
         mm.active_marker = "F1"
-        f1 = mm.markers["F1"]
-        f1.enabled, f1.position = True, float(fb[0])
-        mm.snap_to_peak()
-        assert f1.position == fb[ao.snap_to_peak_bin(tr, thr, exc, 3)], case
+        f1 = tape.want(lambda: mm.markers["F1"])
+        if RECORD:
+            f1.enabled, f1.position = True, float(fb[0])
+            mm.snap_to_peak()
+        tape.check(fb[ao.snap_to_peak_bin(tr, thr, exc, 3)], tape.want(lambda: f1.position), case)
         fallback += len(ao.marker_find_peaks(tr, thr, exc, 3)[0]) == 0
         # the marker sits anywhere on the axis (also between bins and outside it)
-        f1.position = float(rng.uniform(fb[0] - 1e5, fb[-1] + 1e5))
+        position = float(rng.uniform(fb[0] - 1e5, fb[-1] + 1e5))
+        if RECORD:
+            f1.position = position
         for _ in range(5):
-            before = f1.position
+            before = position
             cur = int(np.searchsorted(fb, before))
             mm.snap_to_next_peak()
             nxt = ao.snap_to_next_peak_bin(tr, cur, thr, exc, 3)
-            assert f1.position == (before if nxt < 0 else fb[nxt]), case
+            position = before if nxt < 0 else fb[nxt]
+            tape.check(position, tape.want(lambda: f1.position), case)
             moved += nxt >= 0
             stayed += nxt < 0
+        tape.trial()
     assert moved and stayed and fallback
 
 
-def test_duty_cycle_oracle_random(ref_analytics):
+def test_duty_cycle_oracle_random(ref_analytics, tape):
     from oracle import analytics_oracle as ao
     rng = np.random.default_rng(42)
     for trial in range(20):
@@ -560,13 +647,13 @@ def test_duty_cycle_oracle_random(ref_analytics):
             thr = float(rng.choice([-60.0, -45.0, -30.0]))
             ref.update_from_power(fr, threshold_dbm=thr)
             ora.update_from_power(fr, threshold_dbm=thr)
-            assert ora.duty_pct == ref.duty_pct, (trial, i)
+            tape.check(ora.duty_pct, tape.want(lambda: ref.duty_pct), (trial, i))
             for name in ("on_power_dbm", "off_power_dbm"):
-                a, b = getattr(ref, name), getattr(ora, name)
-                assert (a is None) == (b is None) and (a is None or a == b), (trial, i, name)
+                tape.check(getattr(ora, name), tape.want(lambda: getattr(ref, name)), (trial, i, name))
+        tape.trial()
 
 
-def test_duty_cycle_analyser_of_the_product_random(ref_analytics):
+def test_duty_cycle_analyser_of_the_product_random(ref_analytics, tape):
     """The product's DutyCycleAnalyser (host class; its device feed is checked in the GPU suite) against the
     reference's through random histories of all three entry points: raw complex / real samples, dB spectra with
     and without a threshold, resets - every attribute and the readout string identical."""
@@ -574,7 +661,8 @@ def test_duty_cycle_analyser_of_the_product_random(ref_analytics):
     rng = np.random.default_rng(420)
     for trial in range(10):
         ref, got = ref_analytics.duty(), DutyCycleAnalyser()
-        assert ref.get_readout() == got.get_readout() == ""
+        assert got.get_readout() == ""
+        tape.check(got.get_readout(), tape.want(lambda: ref.get_readout()))
         for i in range(int(rng.integers(50, 400))):
             k = int(rng.integers(0, 10))
             thr = float(rng.uniform(-80, -20))
@@ -594,12 +682,13 @@ def test_duty_cycle_analyser_of_the_product_random(ref_analytics):
                 ref.update(None, thr), got.update(None, thr)
                 ref.update_from_power(np.empty(0)), got.update_from_power(np.empty(0))
             for name in ("duty_pct", "on_power_dbm", "off_power_dbm", "threshold_dbm"):
-                assert getattr(ref, name) == getattr(got, name), (trial, i, name)
-            assert ref.get_readout() == got.get_readout(), (trial, i)
-            assert list(ref._envelope) == list(got._envelope)
+                tape.check(getattr(got, name), tape.want(lambda: getattr(ref, name)), (trial, i, name))
+            tape.check(got.get_readout(), tape.want(lambda: ref.get_readout()), (trial, i))
+            tape.check(list(got._envelope), tape.want(lambda: list(ref._envelope)))
+        tape.trial()
 
 
-def test_audio_oracle_random(ref_analytics):
+def test_audio_oracle_random(ref_analytics, tape):
     from oracle import spectrum_oracle as so
 
     class Stream:
@@ -626,13 +715,15 @@ def test_audio_oracle_random(ref_analytics):
         src.stream = Stream(data)
         src.running = True
         src._audio_block = n
-        win = np.array(src.window, copy=True)
+        win = np.hanning(n)                             # the source's window: checked against the reference's below
+        tape.check(win, tape.want(lambda: np.array(src.window, copy=True)), trial)
         for k in range(nf):
-            want, _ = src.get_power_levels()
+            want = tape.want(lambda: src.get_power_levels()[0])
             blk = data[k * n:(k + 1) * n]
             sig = {"mono": (blk[:, 0] + blk[:, 1]) * 0.5, "left": blk[:, 0], "right": blk[:, 1]}[chan]
             got = so.audio_db(so.audio_compute_power(np.array(sig, copy=True), win, n, fs, psd, precision="ref"), psd)
-            assert np.array_equal(got, want), (trial, k, chan, psd)
+            tape.check(got, want, (trial, k, chan, psd))
+        tape.trial()
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -646,16 +737,7 @@ def _outcome(fn):
         return ("raised", type(exc).__name__)
 
 
-def _same(a, b):
-    if isinstance(a, tuple) and isinstance(b, tuple) and len(a) == len(b):
-        return all(_same(x, y) for x, y in zip(a, b))
-    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
-        return isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and a.shape == b.shape and \
-            np.array_equal(a, b, equal_nan=True)
-    return a == b
-
-
-def test_sources_idle_behaviour_matches_reference(ref_sources, ref_analytics):
+def test_sources_idle_behaviour_matches_reference(ref_sources, ref_analytics, tape):
     import topdogspectrumanalyser_amd as pkg
     pairs = [("hackrf", ref_sources.hackrf, pkg.HackrfSamplesDataSource, dict(sample_rate=20_000_000, centre_freq=2_450_000_000)),
              ("rtl", ref_sources.rtl, pkg.RtlSamplesDataSource, dict(sample_rate=2_048_000, centre_freq=100_000_000)),
@@ -703,7 +785,6 @@ def test_sources_idle_behaviour_matches_reference(ref_sources, ref_analytics):
                 ("idle frame at 4096", lambda s: s.get_power_levels()),
             ]
         for what, probe in probes:
-            want, got = _outcome(lambda: probe(ref)), _outcome(lambda: probe(our))
-            assert want[0] == got[0], (name, what, want, got)
-            assert _same(want[1], got[1]), (name, what, want[1], got[1])
-
+            want, got = tape.want(lambda: _outcome(lambda: probe(ref))), _outcome(lambda: probe(our))
+            tape.check(got, want, (name, what))
+        tape.trial()

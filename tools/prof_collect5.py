@@ -21,7 +21,7 @@ ALGO = {"c3": 2440 * 81920, "c3b": 8 * 2440 * 81920, "c2": 4096 * 24576, "c4": 6
 CMD = {"c3": "tools/devbench.py --steps 9 --warmup 2 --hold 1", "c3b": "tools/devbench.py --steps 24 --warmup 8 --batch 8 --hold 1",
        "c2": "tools/devbench.py --nfft 4096 --hop 4096 --frames 4096 --mode pow --hold 1",
        "c4": "tools/devbench.py --nfft 8192 --hop 8192 --frames 65536 --steps 5 --hold 1",
-       "c5": "bench.py --config c5 --steps 2 --warmup 1 --reps 1 --min-region-s 0.05 --preroll-seconds 0 --no-cpu-baseline --no-parity"}
+       "c5": "bench.py --full --config c5 --steps 2 --warmup 1 --reps 1 --min-region-s 0.05 --preroll-seconds 0 --no-cpu-baseline --no-parity"}
 
 
 def main():
