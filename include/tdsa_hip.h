@@ -348,6 +348,31 @@ int tdsa_density_read(tdsa_density d, float* hist_host, int as_log1p);
  * levels, here they are those of the whole image).  One byte per pixel over PCIe instead of four. */
 int tdsa_density_read_u8(tdsa_density d, uint8_t* img_host, float* levels2);
 
+/* -------- constellation analysis (displays/constellation_2d.py:104-160) ---------------------
+ * What Constellation2D.update_iq_data computes for one block of complex IQ (TDSA_IN_I8 / _U8 / _C64; real input - the
+ * reference's Hilbert path - is TDSA_ERR_ARG), bit for bit: rms = sqrt(mean(|iq|^2)) in float32 with numpy's summation
+ * order, the AGC iq / rms when rms > float32(1e-10), EVM = sqrt(mean(min over the reference points |iq - p|^2)) in the
+ * table's dtype, and np.histogram2d(i, q, bins, [[-range, range], [-range, range]]) laid out as the image
+ * ([q_bin][i_bin], uint32 counts; the image is log1p of them).
+ * _set_refs: n_points (<= 64) x {x, y} interleaved, float32 (is_f64 = 0) or float64; 0 points = no EVM (the
+ * reference's None for an unknown modulation).  _set_density: 1 <= bins <= 128, range > 0 and finite.
+ * _process: one host block of n <= max_host_samples samples (one host wait): rms, evm (has_evm = 0 <=> None), counts
+ * [bins][bins], and the last n_tail normalised points as float32 i[n_tail] then q[n_tail] (n_tail is clamped to n);
+ * any output may be NULL.  _process_dev: a capture already on the device, n_seg segments of seg_len samples every hop
+ * samples, each exactly what _process gives for that slice alone: rms / EVM per segment to the host (either may be
+ * NULL; EVM NaN without a table), counts [n_seg][bins][bins] to a device buffer (or NULL); p = the plan whose stream
+ * produced the capture (ordered after it), or NULL. */
+typedef struct tdsa_constellation_s* tdsa_constellation;
+int tdsa_constellation_create(int device_id, size_t max_host_samples, tdsa_constellation* out);
+int tdsa_constellation_destroy(tdsa_constellation c);
+int tdsa_constellation_set_refs(tdsa_constellation c, const void* xy, int n_points, int is_f64);
+int tdsa_constellation_set_density(tdsa_constellation c, double range, int bins);
+int tdsa_constellation_process(tdsa_constellation c, int in_format, const void* iq_host, size_t n, int n_tail,
+                               float* rms, double* evm, int* has_evm, uint32_t* counts, float* tail_iq);
+int tdsa_constellation_process_dev(tdsa_constellation c, tdsa_plan p, int in_format, const void* iq_dev,
+                                   size_t seg_len, size_t hop, int n_seg, float* rms_host, double* evm_host,
+                                   uint32_t* counts_dev);
+
 typedef struct tdsa_waterfall_s* tdsa_waterfall;
 int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float min_db, tdsa_waterfall* out);
 int tdsa_waterfall_destroy(tdsa_waterfall w);

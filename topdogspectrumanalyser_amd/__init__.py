@@ -10,7 +10,8 @@ from .datasources import (SOURCE_CLASSES, HackrfSamplesDataSource, MicrophoneSam
                           RtlSamplesDataSource, SampleDataSource, SweepDataSource)
 from .core.display_data_processor import DataProcessor  # noqa: F401
 from .core.tare_state import TareState  # noqa: F401
+from .analytics import Constellation, ConstellationView  # noqa: F401
 
 __all__ = ["SpectrumEngine", "HostPipe", "TraceState", "TraceAverager", "SampleDataSource", "SweepDataSource",
            "HackrfSamplesDataSource", "RtlSamplesDataSource", "MicrophoneSamplesDataSource",
-           "SOURCE_CLASSES", "DataProcessor", "TareState"]
+           "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView"]

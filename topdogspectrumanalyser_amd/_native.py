@@ -87,6 +87,13 @@ _SIGNATURES = {
     "tdsa_density_update": (C.c_int, [_P, _P, C.c_int]),
     "tdsa_density_read": (C.c_int, [_P, _P, C.c_int]),
     "tdsa_density_read_u8": (C.c_int, [_P, _P, _P]),
+    "tdsa_constellation_create": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_constellation_destroy": (C.c_int, [_P]),
+    "tdsa_constellation_set_refs": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "tdsa_constellation_set_density": (C.c_int, [_P, C.c_double, C.c_int]),
+    "tdsa_constellation_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_int), _P, _P]),
+    "tdsa_constellation_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.c_size_t, C.c_int, _P, _P, _P]),
     "tdsa_waterfall_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_P)]),
     "tdsa_waterfall_destroy": (C.c_int, [_P]),
     "tdsa_waterfall_push_dev": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int)]),

@@ -11,8 +11,11 @@ HostPipe) and returns scalars or a small image, so a batch user never reads the 
   DutyCycle         DutyCycleAnalyser (core/duty_cycle.py) fed with device-computed per-frame peaks
   DensityHistogram  DensityDisplay._hist (displays/density_display.py:300-320)
   WaterfallRing     Waterfall._buf / _add_row / _display_view (displays/waterfall.py:163-180, 330-336)
+  Constellation     Constellation2D.update_iq_data (displays/constellation_2d.py:104-160): AGC, EVM, IQ density, on raw
+                    IQ blocks from the host or captures in HBM; ConstellationView is the widget's data side
 """
 import ctypes as C
+import logging
 from collections import deque
 from typing import List, Optional, Tuple
 
@@ -215,3 +218,191 @@ class WaterfallRing(_Handle):
         out = np.empty((self.history_lines, self.n_bins), dtype=np.uint8)
         nat.check(nat.lib.tdsa_waterfall_view_u8(self._h, float(min_db), float(max_db), _p(out)))
         return out
+
+
+# ---- constellation analysis (displays/constellation_2d.py:104-160) --------------------------
+CONSTELLATION_BINS = 128           # Constellation2D._resolution
+_log = logging.getLogger(__name__)
+
+
+def constellation_points(name: str) -> Optional[np.ndarray]:
+    """The reference point table of a modulation ([M, 2], the reference's dtype: float64 for qpsk, float32 otherwise), or
+    None for a name the reference does not know (its EVM is then None)."""
+    name = str(name)
+    if name == "bpsk":
+        return np.array([[-1.0, 0.0], [1.0, 0.0]], dtype=np.float32)
+    if name == "qpsk":     # a float32 table divided by the float64 sqrt(2): float64 under NEP 50
+        return np.array([[-1, -1], [-1, 1], [1, -1], [1, 1]], dtype=np.float32) / np.sqrt(2.0)
+    if name == "8psk":     # cos / sin of k * pi / 4 in double, stored as float32
+        return np.array([[np.cos(a), np.sin(a)] for a in (k * np.pi / 4 for k in range(8))], dtype=np.float32)
+    if name in ("16qam", "64qam"):   # the odd-integer grid, scaled by its own float32 rms
+        side = 4 if name == "16qam" else 8
+        lv = np.arange(1 - side, side, 2, dtype=np.float32)
+        grid = np.stack([np.repeat(lv, side), np.tile(lv, side)], axis=1)
+        rms = np.sqrt(np.mean(grid[:, 0] ** 2 + grid[:, 1] ** 2))
+        return grid / rms if rms > 0 else grid
+    return None
+
+
+def _iq_input(samples, fmt: Optional[int]):
+    """(contiguous array, TDSA_IN_* format, sample count) of a host block."""
+    a = np.asarray(samples)
+    if fmt is None:
+        if np.iscomplexobj(a):
+            fmt = nat.IN_C64
+        elif a.dtype == np.int8:
+            fmt = nat.IN_I8
+        elif a.dtype == np.uint8:
+            fmt = nat.IN_U8
+        else:
+            raise ValueError(f"real input ({a.dtype}, shape {a.shape}): the device constellation pass takes complex IQ "
+                             "(complex, or interleaved int8 / uint8 pairs); the reference's Hilbert path is not supported")
+    if fmt == nat.IN_C64:
+        a = np.ascontiguousarray(a.reshape(-1), dtype=np.complex64)
+        return a, fmt, a.size
+    if fmt in (nat.IN_I8, nat.IN_U8):
+        a = np.ascontiguousarray(a.reshape(-1), dtype=np.int8 if fmt == nat.IN_I8 else np.uint8)
+        if a.size % 2:
+            raise ValueError("interleaved I/Q bytes of odd length")
+        return a, fmt, a.size // 2
+    return a, int(fmt), a.size      # the library refuses it
+
+
+class ConstellationResult:
+    """One block's analysis: rms (float32), evm_rms (float, None where the reference gives None), counts
+    ([bins][bins] uint32 in image layout [q_bin][i_bin], or None), and the scatter tail."""
+
+    def __init__(self, rms, evm_rms, counts, tail_i, tail_q):
+        self.rms, self.evm_rms, self.counts = rms, evm_rms, counts
+        self._ti, self._tq = tail_i, tail_q
+
+    def image(self) -> np.ndarray:
+        """np.log1p(hist).T of the reference: what setImage receives (float64 [q_bin][i_bin])."""
+        return np.log1p(self.counts.astype(np.float64))
+
+    def scatter(self, n: Optional[int] = None):
+        """(i, q) float32 of the last n normalised samples (n <= the n_tail processed; default all of them)."""
+        if n is None:
+            return self._ti, self._tq
+        n = int(n)
+        return self._ti[self._ti.size - n:], self._tq[self._tq.size - n:]
+
+
+class Constellation(_Handle):
+    """Constellation2D.update_iq_data on the device: RMS AGC, nearest-symbol EVM and the 2-D IQ density histogram, bit
+    for bit the reference's numpy."""
+    _destroy = staticmethod(lambda h: nat.lib.tdsa_constellation_destroy(h))
+
+    def __init__(self, max_host_samples: int = 1 << 20, device: int = 0, modulation: str = "qpsk",
+                 range_: float = 1.5, bins: int = CONSTELLATION_BINS):
+        self.max_host_samples = int(max_host_samples)
+        self.device = int(device)
+        self._h = C.c_void_p()
+        nat.check(nat.lib.tdsa_constellation_create(self.device, self.max_host_samples, C.byref(self._h)))
+        self.bins, self.range = int(bins), float(range_)
+        nat.check(nat.lib.tdsa_constellation_set_density(self._h, self.range, self.bins))
+        self.set_modulation(modulation)
+
+    def set_modulation(self, name: str) -> None:
+        pts = constellation_points(name)
+        if pts is None:
+            nat.check(nat.lib.tdsa_constellation_set_refs(self._h, None, 0, 0))
+        else:
+            xy = np.ascontiguousarray(pts)
+            nat.check(nat.lib.tdsa_constellation_set_refs(self._h, _p(xy), int(len(xy)), int(xy.dtype == np.float64)))
+        self.modulation = name
+
+    def set_range(self, r: float) -> None:
+        nat.check(nat.lib.tdsa_constellation_set_density(self._h, float(r), self.bins))
+        self.range = float(r)
+
+    def set_bins(self, n: int) -> None:
+        nat.check(nat.lib.tdsa_constellation_set_density(self._h, self.range, int(n)))
+        self.bins = int(n)
+
+    def process(self, samples, fmt: Optional[int] = None, n_tail: int = 0, counts: bool = True) -> ConstellationResult:
+        """One host block (complex, or interleaved int8 / uint8 pairs; fmt overrides the dtype's format)."""
+        a, fmt, n = _iq_input(samples, fmt)
+        rms = C.c_float()
+        evm = C.c_double()
+        has = C.c_int()
+        cnt = np.empty((self.bins, self.bins), dtype=np.uint32) if counts else None
+        nt = max(0, min(int(n_tail), n))
+        tail = np.empty(2 * nt, dtype=np.float32)
+        nat.check(nat.lib.tdsa_constellation_process(self._h, fmt, _p(a), n, nt, C.byref(rms), C.byref(evm),
+                                                     C.byref(has), _p(cnt) if cnt is not None else None,
+                                                     _p(tail) if nt else None))
+        return ConstellationResult(np.float32(rms.value), float(evm.value) if has.value else None, cnt, tail[:nt],
+                                   tail[nt:])
+
+    def process_segments(self, engine: Optional[SpectrumEngine], ptr: int, fmt: int, seg_len: int, hop: int,
+                         n_seg: int, counts_dev: Optional[int] = None):
+        """A capture already on the device (ptr): n_seg segments of seg_len samples every hop samples, each analysed as
+        its own block.  Returns (rms[n_seg] float32, evm[n_seg] float64, NaN without a table); counts_dev (a device
+        buffer of n_seg * bins * bins uint32) receives every segment's histogram.  engine = the producer, or None."""
+        rms = np.empty(int(n_seg), dtype=np.float32)
+        evm = np.empty(int(n_seg), dtype=np.float64)
+        nat.check(nat.lib.tdsa_constellation_process_dev(self._h, engine._h if engine is not None else None, int(fmt),
+                                                         C.c_void_p(ptr), int(seg_len), int(hop), int(n_seg), _p(rms),
+                                                         _p(evm), C.c_void_p(counts_dev) if counts_dev else None))
+        return rms, evm
+
+
+class ConstellationView:
+    """The data side of the reference's Constellation2D widget (same method names): a DataProcessor drives it as
+    mw.constellation_2d_widget.  After update_iq_data: last_evm_rms, and `image` (density mode: np.log1p(hist).T,
+    float64 [q_bin][i_bin]) or `scatter_xy` (scatter mode: the last max_points normalised (i, q))."""
+
+    def __init__(self, device: int = 0, max_host_samples: int = 1 << 17):
+        self._mode = "density"
+        self._range = 1.5
+        self._max_points = 2000
+        self._modulation = "qpsk"
+        self.last_evm_rms: Optional[float] = None
+        self.image: Optional[np.ndarray] = None
+        self.scatter_xy = None
+        self._device = int(device)
+        self._c = Constellation(max_host_samples, device, self._modulation, self._range)
+
+    def set_mode(self, mode: str) -> None:
+        if mode in ("density", "scatter"):
+            self._mode = mode
+
+    def set_modulation(self, mod: str) -> None:
+        self._modulation = mod
+        self._c.set_modulation(mod)
+
+    def set_range(self, r: float) -> None:
+        self._range = r
+
+    def set_max_points(self, n: int) -> None:
+        self._max_points = n
+
+    def update_iq_data(self, samples) -> None:
+        if samples is None or len(samples) == 0:
+            return
+        try:
+            n = len(samples)
+            if n > self._c.max_host_samples:           # a larger tick: a handle that stages it
+                old = self._c
+                self._c = Constellation(max(n, 2 * old.max_host_samples), self._device, self._modulation, old.range)
+                old.close()
+            density = self._mode == "density"
+            start = slice(-min(self._max_points, n), None).indices(n)[0]   # i_data[-n:] of the reference
+            range_error = None
+            if density and float(self._range) != self._c.range:
+                try:
+                    self._c.set_range(self._range)
+                except nat.TdsaError as e:             # the reference measures the EVM before histogram2d raises
+                    range_error = e
+            res = self._c.process(samples, n_tail=0 if density else n - start,
+                                  counts=density and range_error is None)
+            self.last_evm_rms = res.evm_rms
+            if range_error is not None:
+                raise range_error
+            if density:
+                self.image = res.image()
+            else:
+                self.scatter_xy = res.scatter()
+        except Exception as e:
+            _log.error(f"Constellation2D update error: {e}")
