@@ -373,6 +373,32 @@ int tdsa_constellation_process_dev(tdsa_constellation c, tdsa_plan p, int in_for
                                    size_t seg_len, size_t hop, int n_seg, float* rms_host, double* evm_host,
                                    uint32_t* counts_dev);
 
+/* -------- zoom front end: digital down-conversion ------------------------------------------
+ * Inputs are counted from the last reset, across calls: n = 0, 1, ...  x[n] is the unpacked sample (TDSA_IN_I8:
+ * (I + jQ)/128; _U8: float32 of u/127.5 - 1 in float64; _C64 as is), p[n] = p_b + (n - n_b) * phase_step mod 2^32
+ * with (p_b, n_b) the phase and the input index at the last set_nco (a reset: p = 0 at n = 0),
+ * v[n] = x[n] exp(-2 pi j p[n] / 2^32) (v[n] = 0 for n < 0), and y[m] = sum_{k < T} h[k] v[mD - k], complex64.
+ * Output m is emitted by the call that delivers input m D: after n_total inputs there are ceil(n_total / D) outputs.
+ * Any split of the input into calls gives the same bits.  2 <= D <= 4096, 1 <= T <= max_taps <= 64 D.
+ * _set_taps: float32 taps (finite), also resets history and phase.  _set_nco: the phase stays continuous.
+ * _reset: history and phase to zero (the step is kept); returns when every earlier call of the handle has finished.
+ * _process: one host block of n_in <= max_host_samples samples (one copy in, one copy back, one host wait); out_host
+ * holds up to n_in / D + 1 complex64 values.  _process_dev: input and output in device memory; on plan p's stream
+ * (ordered after its work, and its later work after this), or on the handle's own stream for p = NULL; no host wait.
+ * Both set *n_out from host-side counts.  Argument errors are reported before any HIP call. */
+typedef struct tdsa_ddc_s* tdsa_ddc;
+int tdsa_ddc_create(int device_id, int decimation, int max_taps, size_t max_host_samples, tdsa_ddc* out);
+int tdsa_ddc_destroy(tdsa_ddc d);
+int tdsa_ddc_set_taps(tdsa_ddc d, const float* taps_host, int n_taps);
+int tdsa_ddc_set_nco(tdsa_ddc d, uint32_t phase_step);
+int tdsa_ddc_reset(tdsa_ddc d);
+int tdsa_ddc_process(tdsa_ddc d, int in_format, const void* iq_host, size_t n_in, float* out_host, size_t* n_out);
+int tdsa_ddc_process_dev(tdsa_ddc d, tdsa_plan p, int in_format, const void* iq_dev, size_t n_in, void* out_dev,
+                         size_t* n_out);
+/* A copy on plan p's stream, in order with its work (device to device, or device to host); wait = 1 waits for the
+ * stream afterwards.  ZoomSpectrum moves its unframed decimated samples and reads its rows with it. */
+int tdsa_plan_copy(tdsa_plan p, void* dst, const void* src, size_t bytes, int wait);
+
 typedef struct tdsa_waterfall_s* tdsa_waterfall;
 int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float min_db, tdsa_waterfall* out);
 int tdsa_waterfall_destroy(tdsa_waterfall w);

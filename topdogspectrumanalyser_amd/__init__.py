@@ -11,7 +11,9 @@ from .datasources import (SOURCE_CLASSES, HackrfSamplesDataSource, MicrophoneSam
 from .core.display_data_processor import DataProcessor  # noqa: F401
 from .core.tare_state import TareState  # noqa: F401
 from .analytics import Constellation, ConstellationView  # noqa: F401
+from .zoom import DownConverter, ZoomSpectrum, design_decimator  # noqa: F401
 
 __all__ = ["SpectrumEngine", "HostPipe", "TraceState", "TraceAverager", "SampleDataSource", "SweepDataSource",
            "HackrfSamplesDataSource", "RtlSamplesDataSource", "MicrophoneSamplesDataSource",
-           "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView"]
+           "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView",
+           "DownConverter", "ZoomSpectrum", "design_decimator"]

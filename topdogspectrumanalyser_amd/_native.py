@@ -94,6 +94,14 @@ _SIGNATURES = {
     "tdsa_constellation_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float),
                                              C.POINTER(C.c_double), C.POINTER(C.c_int), _P, _P]),
     "tdsa_constellation_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.c_size_t, C.c_int, _P, _P, _P]),
+    "tdsa_ddc_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_ddc_destroy": (C.c_int, [_P]),
+    "tdsa_ddc_set_taps": (C.c_int, [_P, _P, C.c_int]),
+    "tdsa_ddc_set_nco": (C.c_int, [_P, C.c_uint32]),
+    "tdsa_ddc_reset": (C.c_int, [_P]),
+    "tdsa_ddc_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
+    "tdsa_ddc_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
+    "tdsa_plan_copy": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     "tdsa_waterfall_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_P)]),
     "tdsa_waterfall_destroy": (C.c_int, [_P]),
     "tdsa_waterfall_push_dev": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int)]),
