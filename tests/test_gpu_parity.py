@@ -2234,7 +2234,7 @@ def test_host_entry_points_stay_consistent_with_overlap(pkg, streams):
 def test_host_calls_of_every_staging_class_agree(pkg):
     """The host entry points move small calls through pinned, device-visible buffers (read / written in place),
     medium ones through the same buffers with DMA copies and large ones straight from the caller's memory
-    (tdsa_capi.cpp: kZeroCopyMax, kPinnedBounceMax): the rows are the same bit for bit whichever way they went."""
+    (tdsa_capi_internal.hpp: kZeroCopyMax, kPinnedBounceMax): the rows are the same bit for bit whichever way they went."""
     nfft, hop = 1024, 512
     total = 700                                            # 700 frames: 1.4 MB of int8 in, 2.8 MB of rows out
     iq = so.synth_iq_int8(hop * (total - 1) + nfft, nfft, seed=77)

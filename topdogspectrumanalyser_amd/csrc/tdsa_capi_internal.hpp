@@ -1,0 +1,272 @@
+// tdsa_capi_internal.hpp - what the translation units of the C-ABI layer (tdsa_capi_*.cpp, one per handle type or
+// concern) share: error reporting, the status macros, the host idioms they all use, the few functions that cross files,
+// and the plan itself.  The public face of the library is include/tdsa_hip.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/tdsa_hip.h"
+#include "tdsa_kernels.hpp"
+
+namespace tdsa {
+#pragma GCC visibility push(hidden)
+
+// writes the text tdsa_last_error_string returns (one thread_local buffer: tdsa_capi_plan.cpp) and hands `code` back
+int fail(int code, const char* fmt, ...);
+
+#define HIPCHK(expr)                                                                         \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess)                                                                    \
+      return tdsa::fail(TDSA_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+// a status that is not TDSA_OK leaves the function as it is
+#define TRY(expr)                              \
+  do {                                         \
+    const int rc_try_ = (expr);                \
+    if (rc_try_ != TDSA_OK) return rc_try_;    \
+  } while (0)
+
+// Order the plan's main stream after everything in flight on the auxiliary streams.  Every entry point
+// that touches plan state or enqueues on the main stream calls this first; work it enqueues afterwards
+// is in turn waited for by the next overlapped launch (state_dirty).
+int join_streams(tdsa_plan p);
+#define JOIN(p) TRY(tdsa::join_streams(p))
+
+// a consumer with a stream of its own (histogram, waterfall, constellation) behind the rows the plan has in flight:
+// the plan's main stream signals, `consumer` waits
+int plan_order_before(tdsa_plan p, hipStream_t consumer);
+
+inline int bytes_per_sample(int fmt) { return fmt == TDSA_IN_C64 ? 8 : 2; }
+
+// how a raw sample of an input format becomes a float: (float(byte ^ its byte of xor_mask) - off) * scale; complex64 as is
+struct InFormat {
+  unsigned xor_mask;
+  float off, scale;
+};
+inline InFormat in_format_consts(int fmt) {
+  if (fmt == TDSA_IN_I8) return {0x80808080u, 128.0f, 1.0f / 128.0f};
+  if (fmt == TDSA_IN_U8) return {0u, 127.5f, 1.0f / 127.5f};
+  return {0u, 0.0f, 1.0f};
+}
+
+constexpr size_t kPinnedBounceMax = size_t(1) << 20;    // host calls up to 1 MiB each way go through pinned bounce buffers
+constexpr size_t kZeroCopyMax = size_t(256) << 10;       // ... and up to 256 KiB in + out are read / written in place by the kernels
+
+inline bool avg_active(const tdsa_mode& m) { return m.avg_mode != TDSA_AVG_OFF && m.avg_n > 1; }
+
+// Buffers that grow on demand: `cap` units of `unit` bytes behind *ptr.  drain: the stream whose work may still use the
+// old buffer, waited for before it is freed (null: nobody can).  Synchronize, free, clear, allocate, record - in that
+// order, so that a failed allocation leaves pointer and capacity consistent.
+template <class T>
+int grow_device(T** ptr, size_t* cap, size_t need, hipStream_t drain, size_t unit = 1) {
+  if (need <= *cap) return TDSA_OK;
+  if (drain) HIPCHK(hipStreamSynchronize(drain));
+  if (*ptr) HIPCHK(hipFree(*ptr));
+  *ptr = nullptr;
+  *cap = 0;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(ptr), need * unit));
+  *cap = need;
+  return TDSA_OK;
+}
+// ... the same for pinned, device-visible host memory
+inline int grow_pinned(void** ptr, size_t* cap, size_t need, hipStream_t drain) {
+  if (need <= *cap) return TDSA_OK;
+  if (drain) HIPCHK(hipStreamSynchronize(drain));
+  if (*ptr) HIPCHK(hipHostFree(*ptr));
+  *ptr = nullptr;
+  *cap = 0;
+  HIPCHK(hipHostMalloc(ptr, need, hipHostMallocPortable | hipHostMallocMapped));
+  *cap = need;
+  return TDSA_OK;
+}
+
+// destroy paths: whichever of a handle's device buffers exist
+inline void free_all(std::initializer_list<void*> bufs) {
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+}
+
+// plan tables (tdsa_capi_plan.cpp): exp(-2 pi i k / n), k < n, evaluated in double, rounded once ...
+std::vector<float2> unit_circle(int n);
+// ... and the seeds of the column pass's twiddles of an n = 2^log2n point long transform ([big_seed_rows][16384])
+std::vector<float2> seed_table(int n, int log2n);
+// a host table into a device buffer of its own
+template <class T>
+int upload(const std::vector<T>& v, T** dst) {
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T)));
+  HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return TDSA_OK;
+}
+
+// tdsa_capi_process.cpp
+struct SegInfo;
+int process_dev_impl(tdsa_plan p, int in_format, const void* iq_dev, size_t n_samples, int hop, int n_frames,
+                     float* out_db_dev, hipEvent_t before, hipEvent_t after, const SegInfo* seg = nullptr);
+int ensure_pins(tdsa_plan p, size_t in_bytes, size_t out_bytes);
+int launch_spectrum_profiled(tdsa_plan p, int in_c64, const SpecParams& sp, const LaunchGeom& g, hipStream_t s = nullptr);
+AvgParams avg_params(tdsa_plan p, const float* lin, int n_frames, int n, float* out_db);
+int avg_use_ranges(tdsa_plan p, AvgParams& ap, int n_frames, hipStream_t s);
+void avg_advance(tdsa_plan p, int n_frames);
+
+// tdsa_capi_big.cpp
+int process_big(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n_frames, float* out_db_dev);
+int big_materialize_mean(tdsa_plan p);
+
+// tdsa_capi_chirp.cpp
+struct ChirpPost;
+int chirp_plan_init(tdsa_plan p);
+int chirp_transform(tdsa_plan p, const void* in, int in_format, long long stride, int n_frames, const float2* dc_sub,
+                    unsigned xor_mask, float in_off, const ChirpPost* post = nullptr);
+int process_chirp(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n_frames, float* out_db_dev);
+int smooth_radices(int n, int* radix);
+
+#pragma GCC visibility pop
+}  // namespace tdsa
+
+struct tdsa_plan_s {
+  int device = 0, nfft = 0, log2n = 0, max_frames = 0, num_cu = 256;
+  hipStream_t stream = nullptr;
+  // tdsa_set_overlap: extra streams consecutive order-independent launches rotate over, so the ragged
+  // tail of one persistent launch (and the inter-kernel gap) is filled by the head of the next
+  static constexpr int kMaxOverlap = 4;
+  hipStream_t aux[kMaxOverlap - 1] = {};
+  hipEvent_t ev_aux[kMaxOverlap - 1] = {};
+  hipEvent_t ev_state = nullptr;
+  int n_overlap = 1, rr = 0;
+  int overlap_share = 50;                // percent of the CUs an overlapped launch is sized for (3+ streams)
+  bool aux_busy = false, state_dirty = true;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  tdsa_mode mode{};
+  bool window_set = false;
+  float* d_window[3] = {nullptr, nullptr, nullptr};   // window * input scale, per input format
+  float* d_window_perm[3] = {nullptr, nullptr, nullptr};   // the same in the frame kernel's thread order (N >= 2048)
+  float2* d_tw = nullptr;
+  float* d_hold_max = nullptr;
+  float* d_hold_min = nullptr;
+  long long held_max = 0, held_min = 0;
+  double* d_avg = nullptr;
+  int avg_count = 0;
+  float* d_lin = nullptr;                // [max_frames][N] linear power scratch (averaging modes)
+  double* d_carry = nullptr;             // [chunks][N] chunk carries of the averager scan
+  size_t carry_chunks = 0;               // chunks d_carry has room for
+  float* d_agg = nullptr;                // [grid][N] chunk aggregates formed by the frame kernel's workgroups (sizes >= 4096)
+  float* d_agg_w = nullptr;              // [max_frames] weight of each frame in its workgroup's aggregate
+  double* d_chunk_a = nullptr;           // [kAvgMaxWgChunks + 64] per chunk: product of its frames' multipliers
+  float* d_chunk_v = nullptr;            // [kAvgMaxWgChunks + 64] per chunk: 1 = has frames
+  long long agg_w_key[7] = {-1, -1, -1, -1, -1, -1, -1};   // (count, mode, n, frames, chunks, frames per unit, path) the weights in d_agg_w were made for
+  float2* d_cplx = nullptr;              // [max_frames][N] complex spectra (real-input path)
+  float2* d_real = nullptr;              // real-input path: the selected signal(s) as complex streams (two for stereo)
+  size_t real_bytes = 0;
+  float* d_lin1 = nullptr;               // [max_frames][2][N/2+1] one-sided linear power (real-input path)
+  float* d_db1 = nullptr;                // same shape, dB
+  float2* d_dc_state = nullptr;
+  float2* d_sums = nullptr;
+  float2* d_dc_sub = nullptr;
+  float* d_tare_base = nullptr;
+  float* d_tare_acc = nullptr;
+  bool tare_active = false;
+  int tare_count = 0;
+  void* d_in_stage = nullptr;
+  size_t in_stage_bytes = 0;
+  // pinned bounce buffers of the host entry points for small calls (the one-frame-per-GUI-tick case): a copy from / to
+  // pageable memory costs ~10 us each way in the runtime's own staging, a memcpy through pinned memory ~2 us
+  void* h_in_pin = nullptr;
+  void* h_out_pin = nullptr;
+  size_t in_pin_bytes = 0, out_pin_bytes = 0;
+  float* d_out_stage = nullptr;
+  float* d_trace_in = nullptr;
+  float* d_trace_live = nullptr;
+  long long frames_seen = 0;             // frames processed since the last hold reset (nan_safe rule)
+  unsigned long long* d_dbg = nullptr;   // TDSA_TIMELINE developer builds
+  // long-frame plans, N = 2^15 .. 2^20 = N1 x 16384 (tdsa_big.hip)
+  bool big = false;
+  float2* d_z = nullptr;                 // [group][N1][16384] complex64 rows after the column pass
+  float* d_acc = nullptr;                // [N1][16384] power sums of the current call (row pass output)
+  double* d_sum = nullptr;               // [N] fftshift-ed sums over the segments averaged so far
+  void* d_welch = nullptr;               // staging of tdsa_welch_export (one partial) / tdsa_welch_combine (all of them)
+  size_t welch_bytes = 0;
+  float* d_clock = nullptr;              // scratch of tdsa_shader_clock
+  bool big_mean_in_sum = false;          // Welch calls leave the running mean as d_sum / avg_count; d_avg is formed when someone asks
+  double* d_lin64 = nullptr;             // [N] fftshift-ed power of one frame (exp / capped lin averaging)
+  double* d_sums64 = nullptr;            // [max_frames][2] exact I / Q sums of the frames of a call
+  float2* d_tw_seed = nullptr;           // [big_seed_rows][16384] per-column twiddle seeds of the column pass
+  float2* d_tw_row = nullptr;            // W_16384^m : the row pass's twiddle table
+  float* d_ones = nullptr;               // [16384] unit window for the row pass
+  tdsa::BigWindow big_win[3] = {};             // the column pass's window per input format (tdsa_set_window: table or one value)
+  int avg_wg_min = 128;                  // batches of more frames than this take the workgroup-chunk scan (tdsa_debug_knob "avg_wg_min")
+  bool avg_f64_chunks = false;           // tdsa_debug_knob "avg_f64_chunks": always the scan over fixed 64-frame chunks with float64 aggregates
+  // frame lengths made of 2, 3, 5 only (up to 10 000 points in one LDS pass, two passes above): mixed-radix FFT of exactly nfft points (tdsa_smooth.hip) for the
+  // complex path; the plan stays a chirp-z plan for everything else (real input)
+  bool smooth = false;
+  int smooth_on = 1;                     // tdsa_debug_knob "smooth": 0 = such sizes run as chirp-z convolutions like every other
+  int smooth_stages = 0;
+  int smooth_radix[tdsa::kSmoothMaxStages] = {0};
+  // ... above 10 000 points (up to 2^20): two passes, nfft = smooth_n1 * smooth_n2, both within the LDS limit
+  int smooth_n1 = 0, smooth_n2 = 0;
+  int smooth_stages2 = 0;
+  int smooth_radix2[tdsa::kSmoothMaxStages] = {0};   // the stages of smooth_n2 (smooth_radix: those of smooth_n1)
+  float2* d_smooth_z = nullptr;          // [max_frames][n1][n2] between the passes
+  float2* d_smooth_tw = nullptr;         // [nfft] exp(-2 pi i k / nfft)
+  int chirp_fuse_big = 1;                // tdsa_debug_knob "chirp_fuse_big": 0 = long chirp-z frames run chirp_pre / chirp_post as their own passes
+  int chirp_single = 1;                  // tdsa_debug_knob "chirp_single": 0 = chirp-z plans run chirp_pre / two transforms / chirp_post as separate
+                                         // kernels (M <= 16384; developer builds: two launches that carry the passes), separate row passes (M > 16384)
+  int big_pre_wgs = 0;                   // developer builds, tdsa_debug_knob "big_pre_wgs": empty workgroups launched ahead of every column pass
+  int big_group = 64;                    // segments per column-pass / row-pass round (one round for the K = 64 Welch capture)
+  int big_fuse_gather = 0;               // tdsa_debug_knob "big_fuse_gather": 1 = Welch captures of one round run row pass + gather + finish as ONE
+                                         // launch with a ticket queue (measured: profiles/r06_c5_fused_gather.txt)
+  void* d_bigq = nullptr;                // the queue's counters (32 bytes, zeroed once; they only grow)
+  unsigned long long bigq_tickets = 0, bigq_rows = 0;   // what the next launch starts from
+  // frame lengths that are not a power of two (tdsa_chirp.hip): chirp-z on the m_fft-point frame kernel
+  bool chirp = false;
+  int m_fft = 0, log2m = 0;              // M = 2^log2m >= 2 nfft - 1
+  bool chirp_big = false;                // M > 16384: the two M-point transforms run on the long-frame kernels (N1 x 16384)
+  int chirp_split = 0;                   // frames above 2^19 points: H = ceil(N / 2); the convolution runs as four half-length
+                                         // sub-convolutions of M = 2^20 points on rows [2F][M] (tdsa_chirp.hip)
+  float2* d_chirp_bm = nullptr;          // [M] spectra of the filter segments b[m - H], b[m + H] (d_chirp_b: b[m]), split plans only
+  float2* d_chirp_bp = nullptr;
+  float2* d_chirp_a = nullptr;           // [nfft] a[n] = exp(-i pi n^2 / nfft)
+  float2* d_chirp_b = nullptr;           // [M]    FFT_M of conj(a) wrapped around M
+  float2* d_chirp_aw[3] = {nullptr, nullptr, nullptr};   // [nfft] window * input scale * a[n] per input format (M <= 16384: the
+                                         // unpack / window / chirp pass rides the first transform's loads)
+  float2* d_u0 = nullptr;                // [max_frames][M] work rows (allocated on first use)
+  float2* d_u1 = nullptr;
+  void* d_scratch = nullptr;             // grows on demand: results of tdsa_rows_stats / tdsa_rows_top_peaks
+  size_t scratch_bytes = 0;
+  // per-frame scalars (tdsa_set_frame_stats): the results of the last kFsKeep calls.  A call takes the next of ITS stream's
+  // kFsKeep slots, so a slot is only ever rewritten by later work of the stream that wrote it (in order, no events between
+  // the frame-kernel launches), and the last kFsKeep calls overall are always still there.
+  static constexpr int kFsKeep = 4;
+  struct FsSlot {
+    void* d_part = nullptr;              // [frames][waves per frame] records of the frame kernel's STATS epilogue
+    float* d_peak = nullptr;             // [frames]
+    int* d_bin = nullptr;
+    double* d_band = nullptr;
+    size_t cap = 0;
+    int n_frames = 0;
+    int state = 0;                       // 0: nothing, 1: results (in flight on `stream`), 2: the call produced no rows to take them from
+    bool pending = false;                // the frame kernel's records are there, frame_stats_finish_kernel has not run yet
+    int wpf = 1;
+    double cal_lin = 1.0;
+    hipStream_t stream = nullptr;
+  } fs[kMaxOverlap][kFsKeep];
+  unsigned fs_count[kMaxOverlap] = {};   // calls that took a slot, per stream
+  FsSlot* fs_hist[kFsKeep] = {};         // the slots of the last calls, newest at fs_seq - 1
+  bool fs_on = false;
+  int fs_lo = 1, fs_hi = 0;              // band: inclusive display-bin range, lo > hi = none
+  unsigned long long fs_seq = 0;         // calls that left (or tried to leave) statistics
+  hipStream_t fs_stream = nullptr;       // folds and reads back a slot
+  bool profiling = false;
+  bool sync_call = false;                // set by the synchronous host entry points around their device call
+  std::vector<hipEvent_t> prof_events;   // pairs (begin, end) around frame-kernel launches
+  size_t prof_used = 0;
+};

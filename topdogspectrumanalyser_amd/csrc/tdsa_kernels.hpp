@@ -1,5 +1,5 @@
 // tdsa_kernels.hpp - kernel parameter blocks and launcher prototypes shared by the kernel TUs
-// and the C-ABI layer (tdsa_capi.cpp).
+// and the C-ABI layer (tdsa_capi_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -209,7 +209,7 @@ constexpr int big_seed_rows(int log2n) {
 }
 // The window as the column threads get it.  mode 0: `table` [N] (window * input scale), one load per sample.
 // mode 2: `flat` for every sample (rectangular windows, the chirp-z path's all-ones window): no loads at all.
-// tdsa_set_window decides (tdsa_capi.cpp).
+// tdsa_set_window decides (tdsa_capi_plan.cpp).
 struct BigWindow {
   int mode;
   const float* table;
