@@ -399,6 +399,60 @@ int tdsa_ddc_process_dev(tdsa_ddc d, tdsa_plan p, int in_format, const void* iq_
  * stream afterwards.  ZoomSpectrum moves its unframed decimated samples and reads its rows with it. */
 int tdsa_plan_copy(tdsa_plan p, void* dst, const void* src, size_t bytes, int wait);
 
+/* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
+ * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
+ * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by
+ * frequency, np.interp onto the fixed grid of _create_frequency_grid, :32-40), with the rows never leaving the device.
+ * Geometry: n_steps centres c_s (float64 Hz, strictly ascending), one frame length nfft, one bin width bin_hz, one
+ * kept range [k0, k1) of the fftshift-ed row (K = k1 - k0).  Kept bin k of step s lies at x = c_s + (k - nfft/2) *
+ * bin_hz, one float64 multiply then one float64 add (with bin_hz = 1.0 / (nfft * (1.0 / fs)) that is
+ * np.fft.fftshift(np.fft.fftfreq(nfft, 1 / fs)) + c_s bit for bit).  The concatenation xp of the steps' frequencies
+ * must be strictly increasing - x_last(s) < x_first(s + 1), checked with that expression, TDSA_ERR_ARG otherwise; gaps
+ * between steps are allowed and interpolated across.  _set_geometry also takes the grid (n_grid finite float64 values),
+ * waits for the handle's work in flight and clears the steps.
+ * Detector: the F dB rows of a step become T[s][k - k0] (float32): _SAMPLE the last frame, _MAX / _MIN np.max / np.min
+ * over the frames (a NaN stays), _AVG 10 log10(max(mean_f(10^(d_f / 10)), 1e-30)) with the sum in float64 in frame
+ * order (display_data_processor.py:400-402; -inf counts as no power, a NaN stays; rows within +-300 dB; exp2 / log2
+ * in float32, within 1e-3 dB of the float64 formula).
+ * _update_dev: rows of steps [first_step, first_step + n_steps) already on the device, step i at rows_dev + i *
+ * step_stride_floats (0: back to back, frames_per_step * nfft), its frames nfft apart; those steps become present.
+ * On plan p's stream, after its work (p = NULL: the handle's own stream); no host wait.
+ * _run_dev: the same from raw IQ: tdsa_process_dev_batch of plan p (one capture per step, step i at iq_dev + i *
+ * step_stride_bytes) into a row scratch the handle owns, then the detector, chunk of steps by chunk of steps so that
+ * the scratch stays within the bound of _set_chunk_bytes (default 256 MiB, at least one step); no host wait.  Any
+ * split into calls and any bound give the same bits.
+ * _read: stitches the steps present onto the grid, float64 [n_grid], to out_f64_dev and / or out_f64_host (either may
+ * be NULL; with a host pointer the call waits, otherwise the next _read with one, _get_steps or _timer_end does).
+ * TDSA_SWEEP_INTERP: np.interp(grid, xp, fp) bit for bit, fp = T as float64.  TDSA_SWEEP_PEAK, for grids coarser than
+ * the bins: with h = grid[1] - grid[0] (> 0), out[i] = the maximum of fp over the bins with grid[i] - 0.5 h <= xp <
+ * grid[i] + 0.5 h (a NaN stays; one lane walks one cell), an empty cell takes the INTERP value.  With no step present
+ * every output is NaN (the reference before its first sweep).  _reset: no step is present.  _get_steps: T [n_steps][K]
+ * and one byte per step (1 = present) to the host, for tests and tools.  _timer_begin / _end: HIP events on the
+ * handle's own stream (where _read runs).  Limits: n_steps <= 4096, 2 <= nfft <= 2^20, 1 <= K <= nfft, 2 <= n_grid <=
+ * 2^24, frames_per_step >= 1.  Argument errors are reported before any HIP call. */
+#define TDSA_SWEEP_DET_SAMPLE 0
+#define TDSA_SWEEP_DET_MAX 1
+#define TDSA_SWEEP_DET_MIN 2
+#define TDSA_SWEEP_DET_AVG 3
+#define TDSA_SWEEP_INTERP 0
+#define TDSA_SWEEP_PEAK 1
+typedef struct tdsa_sweep_s* tdsa_sweep;
+int tdsa_sweep_create(int device_id, int nfft, int n_steps, int n_grid, tdsa_sweep* out);
+int tdsa_sweep_destroy(tdsa_sweep w);
+int tdsa_sweep_set_geometry(tdsa_sweep w, const double* centres_hz, double bin_hz, int k0, int k1,
+                            const double* grid_hz_host);
+int tdsa_sweep_reset(tdsa_sweep w);
+int tdsa_sweep_set_chunk_bytes(tdsa_sweep w, size_t bytes);
+int tdsa_sweep_update_dev(tdsa_sweep w, tdsa_plan p, int first_step, int n_steps, const float* rows_dev,
+                          int frames_per_step, size_t step_stride_floats, int detector);
+int tdsa_sweep_run_dev(tdsa_sweep w, tdsa_plan p, int in_format, const void* iq_dev, size_t step_stride_bytes,
+                       int first_step, int n_steps, size_t n_samples_per_step, int hop, int frames_per_step,
+                       int detector);
+int tdsa_sweep_read(tdsa_sweep w, int mode, double* out_f64_host, double* out_f64_dev);
+int tdsa_sweep_get_steps(tdsa_sweep w, float* T_host, unsigned char* valid_host);
+int tdsa_sweep_timer_begin(tdsa_sweep w);
+int tdsa_sweep_timer_end(tdsa_sweep w, float* elapsed_ms);
+
 typedef struct tdsa_waterfall_s* tdsa_waterfall;
 int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float min_db, tdsa_waterfall* out);
 int tdsa_waterfall_destroy(tdsa_waterfall w);

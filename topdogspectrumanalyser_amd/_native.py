@@ -17,6 +17,8 @@ DB_MAG, DB_POW = 0, 1
 AVG_OFF, AVG_EXP, AVG_LIN = 0, 1, 2
 HOLD_MAX, HOLD_MIN = 1, 2
 CH_MONO, CH_LEFT, CH_RIGHT, CH_STEREO = 0, 1, 2, 3
+SWEEP_DET_SAMPLE, SWEEP_DET_MAX, SWEEP_DET_MIN, SWEEP_DET_AVG = 0, 1, 2, 3
+SWEEP_INTERP, SWEEP_PEAK = 0, 1
 RESET_AVG, RESET_HOLD_MAX, RESET_HOLD_MIN, RESET_DC, RESET_TARE, RESET_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -101,6 +103,18 @@ _SIGNATURES = {
     "tdsa_ddc_reset": (C.c_int, [_P]),
     "tdsa_ddc_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
     "tdsa_ddc_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
+    "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "tdsa_sweep_destroy": (C.c_int, [_P]),
+    "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),
+    "tdsa_sweep_reset": (C.c_int, [_P]),
+    "tdsa_sweep_set_chunk_bytes": (C.c_int, [_P, C.c_size_t]),
+    "tdsa_sweep_update_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_size_t, C.c_int]),
+    "tdsa_sweep_run_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int,
+                                     C.c_int]),
+    "tdsa_sweep_read": (C.c_int, [_P, C.c_int, _P, _P]),
+    "tdsa_sweep_get_steps": (C.c_int, [_P, _P, _P]),
+    "tdsa_sweep_timer_begin": (C.c_int, [_P]),
+    "tdsa_sweep_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_plan_copy": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     "tdsa_waterfall_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_P)]),
     "tdsa_waterfall_destroy": (C.c_int, [_P]),

@@ -7,8 +7,8 @@ classes unchanged.  Nothing here computes; a concrete sample source does its ari
 GpuSpectrumMixin.
 
   SweepDataSource    something that delivers finished dB sweeps (the reference wraps external command
-                     line tools; none is built here, the interface exists for code that type-checks
-                     against it)
+                     line tools; here sweep.IqSweepDataSource retunes, captures IQ per step and stitches
+                     the steps on the GPU)
   SampleDataSource   something that delivers IQ / audio samples and turns N of them into a spectrum:
                      `get_power_levels() -> (power_db[N], frequency_bins[N])`
 """
