@@ -453,6 +453,70 @@ int tdsa_sweep_get_steps(tdsa_sweep w, float* T_host, unsigned char* valid_host)
 int tdsa_sweep_timer_begin(tdsa_sweep w);
 int tdsa_sweep_timer_end(tdsa_sweep w, float* elapsed_ms);
 
+/* -------- zero span: detector ring, trigger search, trace view ---------------------------
+ * Amplitude against time.  Samples count from the last reset, n = 0, 1, ...; x[n] is the unpacked sample (TDSA_IN_I8:
+ * (I + jQ) / 128; _U8: (float(u) - 127.5f) * (1.0f / 127.5f) per component, the frame kernels' unpack; _C64 as is;
+ * TDSA_IN_F32R, real float32, is accepted by tdsa_zspan_push* alone).  The detector gives one float32 e[n] per sample:
+ * _DET_REAL e = Re x (F32R passes through); _DET_MAG e = sqrt(re * re + im * im), every operation rounded to float32,
+ * the root correctly; _DET_DB e = log2(re * re + im * im + log_floor) * float32(10 / log2(10)) + offset_db, within
+ * 1e-3 dB of the float64 formula.
+ * Ring: the last `capacity` values of e.  With `total` samples pushed, held = min(total, capacity), base = total -
+ * held; a push of more than `capacity` samples only processes its last `capacity`; any split of a stream into pushes
+ * gives the same ring.
+ * _create: capacity is int(2.0 * rate) for the reference's _ZS_BUFFER_SECONDS (core/display_data_processor.py:275,
+ * :277-282 - the np.concatenate and the [-max_buf:] slice of every tick).  _set_detector resets (the ring holds
+ * detected values); _reset empties the ring (DisplayManager._set_zero_span / _exit_zero_span writing None, core/display_manager.py:541, :553).
+ * _push: one host block through pinned staging in chunks of max_host_samples; it returns when the block has left the
+ * caller's memory, not when the ring is written (:264-272: read_samples_only, stereo mean and .real stay with the
+ * caller; the history append is this call).  _push_dev: samples already on the device; on plan p's stream after its
+ * work (p = NULL: the handle's own stream); no host wait.
+ * _view (:284-311): level is rounded to float32 first, since the reference compares a float32 array with a Python
+ * float and numpy does that in float32.  held < n_display: the chunk is everything held, untriggered.  _FREE_RUN:
+ * start = total - n_display.  _RISE / _FALL: se = held - n_display, ss = max(0, se - 8 * n_display); over the
+ * ring-relative pairs (i, i + 1), ss <= i <= se - 2, a rise is e[i] < level && e[i + 1] >= level, a fall e[i] >= level
+ * && e[i + 1] < level (a NaN never matches); the last hit gives start = base + i + 1, triggered = 1; no hit or an
+ * empty range gives the free-run start, triggered = 0.  The chunk is e[start : start + length].  n_points = 0: the
+ * chunk itself, float32 [length].  Otherwise P = min(n_points, length) columns; column c covers chunk indices
+ * [floor(c L / P), floor((c + 1) L / P)): _COL_MINMAX two rows [2][P], np.min then np.max of the cell (a NaN stays -
+ * what the widget's peak-downsampled curve draws, displays/zero_span.py:55); _COL_SAMPLE the cell's first value;
+ * _COL_MEAN its float64 sum divided by its length, rounded once.  The output goes to out_dev and / or out_host (either
+ * may be NULL; room for max(n_display, 1) floats with n_points = 0, for 2 * n_points otherwise).  Every view fills
+ * *info and waits once for the device.  Statistics are over the chunk: min / max as np.min / np.max, mean from a
+ * float64 sum, n_at_or_above counts e >= level (duty cycle = that / length), n_rise / n_fall the crossings inside the
+ * chunk (pulse count, PRF).  An empty chunk has NaN min / max / mean.
+ * _timer_begin / _end: HIP events on the handle's own stream (where _view runs, behind the pushes).
+ * Limits: 4 <= capacity <= 2^28, 1 <= n_display <= 2^28, 0 <= n_points <= 16384.  Argument errors are reported before
+ * any HIP call. */
+#define TDSA_IN_F32R 3
+#define TDSA_ZS_DET_REAL 0
+#define TDSA_ZS_DET_MAG 1
+#define TDSA_ZS_DET_DB 2
+#define TDSA_ZS_FREE_RUN 0
+#define TDSA_ZS_RISE 1
+#define TDSA_ZS_FALL 2
+#define TDSA_ZS_COL_MINMAX 0
+#define TDSA_ZS_COL_SAMPLE 1
+#define TDSA_ZS_COL_MEAN 2
+typedef struct tdsa_zspan_info {
+  int64_t start, total;      /* absolute index of the chunk's first sample; samples pushed since the last reset */
+  int32_t length, triggered, n_columns;
+  float min, max;
+  double mean;
+  int64_t n_at_or_above;
+  int32_t n_rise, n_fall;
+} tdsa_zspan_info;
+typedef struct tdsa_zspan_s* tdsa_zspan;
+int tdsa_zspan_create(int device_id, size_t capacity, size_t max_host_samples, tdsa_zspan* out);
+int tdsa_zspan_destroy(tdsa_zspan z);
+int tdsa_zspan_set_detector(tdsa_zspan z, int detector, float log_floor, float offset_db);
+int tdsa_zspan_reset(tdsa_zspan z);
+int tdsa_zspan_push(tdsa_zspan z, int in_format, const void* samples_host, size_t n);
+int tdsa_zspan_push_dev(tdsa_zspan z, tdsa_plan p, int in_format, const void* samples_dev, size_t n);
+int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int n_points, int col_detector,
+                    tdsa_zspan_info* info, float* out_host, float* out_dev);
+int tdsa_zspan_timer_begin(tdsa_zspan z);
+int tdsa_zspan_timer_end(tdsa_zspan z, float* elapsed_ms);
+
 typedef struct tdsa_waterfall_s* tdsa_waterfall;
 int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float min_db, tdsa_waterfall* out);
 int tdsa_waterfall_destroy(tdsa_waterfall w);

@@ -13,12 +13,16 @@ LIB_PATH = os.environ.get("TDSA_HIP_LIB", os.path.join(_HERE, "libtdsa_hip.so"))
 
 TDSA_OK = 0
 IN_I8, IN_U8, IN_C64 = 0, 1, 2
+IN_F32R = 3                                   # real float32: tdsa_zspan_push* only
 DB_MAG, DB_POW = 0, 1
 AVG_OFF, AVG_EXP, AVG_LIN = 0, 1, 2
 HOLD_MAX, HOLD_MIN = 1, 2
 CH_MONO, CH_LEFT, CH_RIGHT, CH_STEREO = 0, 1, 2, 3
 SWEEP_DET_SAMPLE, SWEEP_DET_MAX, SWEEP_DET_MIN, SWEEP_DET_AVG = 0, 1, 2, 3
 SWEEP_INTERP, SWEEP_PEAK = 0, 1
+ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
+ZS_FREE_RUN, ZS_RISE, ZS_FALL = 0, 1, 2
+ZS_COL_MINMAX, ZS_COL_SAMPLE, ZS_COL_MEAN = 0, 1, 2
 RESET_AVG, RESET_HOLD_MAX, RESET_HOLD_MIN, RESET_DC, RESET_TARE, RESET_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -34,6 +38,12 @@ class Info(C.Structure):
                 ("lds_bytes", C.c_int32), ("num_cu", C.c_int32),
                 ("frames_held_max", C.c_int64), ("frames_held_min", C.c_int64),
                 ("avg_count", C.c_int32), ("version", C.c_int32)]
+
+
+class ZspanInfo(C.Structure):
+    _fields_ = [("start", C.c_int64), ("total", C.c_int64), ("length", C.c_int32), ("triggered", C.c_int32),
+                ("n_columns", C.c_int32), ("min", C.c_float), ("max", C.c_float), ("mean", C.c_double),
+                ("n_at_or_above", C.c_int64), ("n_rise", C.c_int32), ("n_fall", C.c_int32)]
 
 
 # every symbol include/tdsa_hip.h declares: name -> (restype, argtypes)
@@ -115,6 +125,15 @@ _SIGNATURES = {
     "tdsa_sweep_get_steps": (C.c_int, [_P, _P, _P]),
     "tdsa_sweep_timer_begin": (C.c_int, [_P]),
     "tdsa_sweep_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_zspan_create": (C.c_int, [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_zspan_destroy": (C.c_int, [_P]),
+    "tdsa_zspan_set_detector": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
+    "tdsa_zspan_reset": (C.c_int, [_P]),
+    "tdsa_zspan_push": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "tdsa_zspan_push_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t]),
+    "tdsa_zspan_view": (C.c_int, [_P, C.c_int, C.c_double, C.c_size_t, C.c_int, C.c_int, C.POINTER(ZspanInfo), _P, _P]),
+    "tdsa_zspan_timer_begin": (C.c_int, [_P]),
+    "tdsa_zspan_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_plan_copy": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     "tdsa_waterfall_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_P)]),
     "tdsa_waterfall_destroy": (C.c_int, [_P]),

@@ -13,9 +13,16 @@ Scope notes
     are switched on for the same first frame (SURVEY.md 8(a) quirk ii), after which both just follow
     the live trace; that accident is pinned in the oracle (golden max_hold_both / min_hold_both) and is
     reproduced only on request: DataProcessor(..., reference_hold_alias=True).
-  * The GUI feeds around the spectrum path (sweep traces, constellation + EVM read-out, zero-span with
-    its rise / fall trigger, peak-list read-out) behave as the reference's do, on the host: they are
-    per-tick scalar work with no GPU side; batch users go through `analytics.py` instead.
+  * The GUI feeds around the spectrum path (sweep traces, constellation + EVM read-out, peak-list
+    read-out) behave as the reference's do, on the host: they are per-tick scalar work with no GPU side;
+    batch users go through `analytics.py` instead.
+  * Zero span with its rise / fall trigger has both.  By default it is the reference's host code: two
+    seconds of float32 history rebuilt with np.concatenate on every tick, fine at audio rates.
+    DataProcessor(..., zero_span_on_device=True) keeps that history in a `zerospan.ZeroSpan` ring on the
+    device instead: the tick uploads its block, the trigger search and the window run there, and only the
+    displayed chunk comes back - the same (time_s, chunk) bits.  `dm.zero_span_buffer` then carries a
+    token instead of the history; a None written there (DisplayManager._set_zero_span / _exit_zero_span)
+    restarts the ring, a changed sample rate makes a new one.  Batch users go through `zerospan.py`.
 """
 import logging
 import time
@@ -44,7 +51,8 @@ def _plural(n: int, word: str) -> str:
 
 
 class DataProcessor:
-    def __init__(self, main_window, display_manager, gpu_device: int = 0, reference_hold_alias: bool = False):
+    def __init__(self, main_window, display_manager, gpu_device: int = 0, reference_hold_alias: bool = False,
+                 zero_span_on_device: bool = False):
         self.mw = main_window
         self.dm = display_manager
         self._device = gpu_device
@@ -55,6 +63,8 @@ class DataProcessor:
         self._sweep_averager = TraceAverager(device=gpu_device)
         self._sweeps_since_axis_refresh = 0
         self._fused: Optional[dict] = None                # results of the current frame's fused device call
+        self.zero_span_on_device = bool(zero_span_on_device)
+        self._zero_span = None                            # zerospan.ZeroSpan, made on the first tick that needs it
 
     # ================================================================== public
     def reset_sweep_averager(self) -> None:
@@ -452,6 +462,9 @@ class DataProcessor:
         block = mw.current_source.read_samples_only()
         if block is None or len(block) == 0:
             return
+        if getattr(self, "zero_span_on_device", False):
+            self._zero_span_device_tick(block)
+            return
         if block.ndim == 2:
             block = block.mean(axis=1)                    # stereo -> mono
         block = np.real(block).ravel().astype(np.float32)
@@ -465,3 +478,23 @@ class DataProcessor:
             start = self._trigger_start(history, n_shown, mode, getattr(dm, "zero_span_trigger_level", 0.0))
         shown = history[-n_shown:] if start is None else history[start:start + n_shown]
         mw.zero_span_widget.update_zero_span_data(np.arange(shown.size, dtype=np.float32) / rate, shown)
+
+    def _zero_span_device_tick(self, block: np.ndarray) -> None:
+        """The same tick with the history in a device ring: the block goes up, the displayed chunk comes back."""
+        from ..zerospan import ZeroSpan
+        mw, dm = self.mw, self.dm
+        rate = float(getattr(mw.current_source, "sample_rate", 44100))
+        ring = getattr(self, "_zero_span", None)
+        if ring is not None and ring.sample_rate != rate:
+            ring.close()
+            ring = None
+        if ring is None:
+            ring = self._zero_span = ZeroSpan(rate, device=getattr(self, "_device", 0))
+            dm.zero_span_buffer = None
+        if dm.zero_span_buffer is None:                   # the display manager cleared the history
+            ring.reset()
+            dm.zero_span_buffer = ring                    # the token: the history lives behind this handle
+        ring.push(np.asarray(block))
+        shown = ring.view(mode=getattr(dm, "zero_span_trigger_mode", "free_run"),
+                          level=getattr(dm, "zero_span_trigger_level", 0.0), window_s=dm.zero_span_time_window)
+        mw.zero_span_widget.update_zero_span_data(shown.time_s, shown.samples)
