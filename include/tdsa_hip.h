@@ -517,6 +517,72 @@ int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int 
 int tdsa_zspan_timer_begin(tdsa_zspan z);
 int tdsa_zspan_timer_end(tdsa_zspan z, float* elapsed_ms);
 
+/* -------- 3-D history views: trace ring, ribbon / line-stack / surface passes -------------
+ * The device side of the reference's ThreeD, RibbonWidget and Surface displays (displays/three_dimension.py, ribbon.py,
+ * surface.py): a ring [depth][n_bins] of the last rows, a running hold row, and view passes that return what the three
+ * widgets hand their GL items, newest row first.  kind TDSA_HIST_HEIGHTS stores z = clip((dB - (ref - range)) / range
+ * * 8, 0, 8), every operation in float32 with the amplitude in force at the push (rows already held keep their z);
+ * TDSA_HIST_LEVELS stores the rows as pushed and normalises at view time.  Rows never pushed are 0.  Rows are float32
+ * without NaN (+-inf are fine); n_bins >= 2, depth * n_bins <= 2^28, range_db > 0 for heights.
+ *
+ * push: one host row, optionally with the max trace the hold follows (hold = maximum(hold, z(max)); without it the
+ * hold follows the row itself) and the min trace (kept as z(min) until the next push); update_hold = 0 leaves the hold
+ * alone.  push_dev: n_rows device rows in order, on the plan's stream (NULL: the handle's own), the same as n_rows
+ * single pushes.  Each push also keeps the row's maximum and the index of its first occurrence (np.argmax).
+ *
+ * Views.  columns = 0: every bin; columns = P: column c covers bins [(c n) / P, ((c + 1) n) / P) and yields the cell's
+ * maximum and the bin of its first maximum (out->bins, [rows][P]); colours follow the reduced value.  Destinations
+ * (tdsa_history_out) are all host or all device pointers (on_device; device ones aligned to 16 bytes); NULL = not
+ * wanted.  Every view waits for its results.
+ *   ribbon   rows 0 .. min(30, depth) - 1; primary = vertices float32 [rows][2 n][3] (x from x_host[n_bins], gathered
+ *            through the bins of a reduced view), colours = RGBA float32 [rows][2 n][4]  (Ribbon._row_verts_colors)
+ *   lines    lines first .. first + count - 1; primary = z float32 [count][n]; colours = uint8 [count][n], int32(8 - z)
+ *            % 11, 255 for a line no row has reached (TDSA_HIST_COLOUR_INDEX), or float32 [count][n][4] through
+ *            palette_host [11][4] (TDSA_HIST_COLOUR_RGBA; 255 -> 0); hold, min_row: float32 [n] (+ hold_bins, min_bins
+ *            when reduced); info: live and hold peak
+ *   surface  all depth rows; primary = float32(clip((level - zmin) / (zmax - zmin), 0, 1)) evaluated in float64, 0.5
+ *            when zmax == zmin; colours = float32 [depth][n][3] = (t, 0, 1 - t); info: live peak and live_norm */
+#define TDSA_HIST_HEIGHTS 0
+#define TDSA_HIST_LEVELS 1
+#define TDSA_HIST_COLOUR_INDEX 0
+#define TDSA_HIST_COLOUR_RGBA 1
+typedef struct tdsa_history_info {
+  long long pushed;        /* rows since the last reset */
+  int rows, cols;          /* rows and columns of the arrays written */
+  int valid_rows, has_min; /* rows of the view a push has reached; 1: min_row was written */
+  int live_bin;            /* first maximum of the newest row (full-width bin) ... */
+  float live_value;        /* ... and its z / level */
+  int hold_bin;            /* lines: first maximum of the hold row */
+  float hold_value;
+  double live_norm;        /* surface: normalised z of the live peak, evaluated in float32 as the widget's marker is */
+} tdsa_history_info;
+typedef struct tdsa_history_out {
+  int on_device, reserved;
+  void* primary;
+  void* colours;
+  int* bins;
+  float* hold;
+  int* hold_bins;
+  float* min_row;
+  int* min_bins;
+} tdsa_history_out;
+typedef struct tdsa_history_s* tdsa_history;
+int tdsa_history_create(int device_id, int depth, int n_bins, int kind, tdsa_history* out);
+int tdsa_history_destroy(tdsa_history h);
+int tdsa_history_set_amplitude(tdsa_history h, double ref_level, double range_db);
+int tdsa_history_reset(tdsa_history h);
+int tdsa_history_reset_hold(tdsa_history h);
+int tdsa_history_push(tdsa_history h, const float* live_host, const float* max_host, const float* min_host,
+                      int update_hold);
+int tdsa_history_push_dev(tdsa_history h, tdsa_plan p, const float* rows_dev, int n_rows);
+int tdsa_history_ribbon(tdsa_history h, const float* x_host, int columns, const tdsa_history_out* out,
+                        tdsa_history_info* info);
+int tdsa_history_lines(tdsa_history h, int first, int count, int colour_mode, const float* palette_host, int columns,
+                       const tdsa_history_out* out, tdsa_history_info* info);
+int tdsa_history_surface(tdsa_history h, int columns, const tdsa_history_out* out, tdsa_history_info* info);
+int tdsa_history_timer_begin(tdsa_history h);
+int tdsa_history_timer_end(tdsa_history h, float* elapsed_ms);
+
 typedef struct tdsa_waterfall_s* tdsa_waterfall;
 int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float min_db, tdsa_waterfall* out);
 int tdsa_waterfall_destroy(tdsa_waterfall w);

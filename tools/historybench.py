@@ -1,0 +1,219 @@
+#!/usr/bin/env python3
+"""Timing of the 3-D history views at n = 16384 bins, rows resident in HBM.
+
+  copy     the box's device-to-device copy rate (1 GiB, torch), which the view passes are stated against
+  push     256 dB rows already in HBM into the ring in one call, per row
+  ribbon   30 rows -> vertices and colours; lines: 300 lines -> z and colour index / RGBA; surface: 100 rows -> z and
+           colours.  Each at full width and at columns=1024, into device memory (the pass alone) and into host
+           memory (with the read-back), with the bytes each moves and the bytes that cross to the host
+  host     the numpy restatement of the same tick (tests/history_contract.py) on the host's CPU, for scale
+
+Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per step: warm-up
+calls, then the median of `--reps` (at least 20) single calls, each between device events on the handle's stream.
+
+    python tools/historybench.py [--out profiles/historybench.txt] [--reps 20]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+N = 16384
+PUSH_ROWS = 256
+STEPS = ("copy", "push", "ribbon", "lines", "surface", "host")
+LIMIT_S = {"copy": 120, "push": 120, "ribbon": 180, "lines": 240, "surface": 180, "host": 300}
+
+
+def dev(nat, nbytes):
+    p = C.c_void_p()
+    nat.check(nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(p)))
+    return p
+
+
+def rows_db(rng, n_rows):
+    return rng.normal(-80.0, 12.0, size=(n_rows, N)).astype(np.float32)
+
+
+def median_us(h, f, warm, reps):
+    for _ in range(warm):
+        f()
+    t = []
+    for _ in range(reps):
+        h.timer_begin()
+        f()
+        t.append(h.timer_end() * 1e3)
+    return float(np.median(t)), float(np.min(t)), float(np.max(t))
+
+
+def fill(nat, h, rng, n_rows):
+    rows = rows_db(rng, n_rows)
+    d = dev(nat, rows.nbytes)
+    nat.check(nat.lib.tdsa_memcpy_h2d(0, d, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+    h.push_rows(None, d.value, n_rows)
+    h.lines(0, 1) if h.kind == "heights" else h.surface(columns=1)
+    nat.lib.tdsa_dev_free(0, d)
+
+
+def step_copy(args):
+    import torch
+    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    y = torch.empty_like(x)
+    x.fill_(1.0)
+    for _ in range(3):
+        y.copy_(x)
+    t = []
+    for _ in range(args.reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        y.copy_(x)
+        b.record()
+        b.synchronize()
+        t.append(a.elapsed_time(b) * 1e-3)
+    moved = 2 * x.numel() * 4
+    return dict(copy_bps=moved / float(np.median(t)), text=[
+        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
+
+
+def step_push(args):
+    from topdogspectrumanalyser_amd import TraceHistory, _native as nat
+    rng = np.random.default_rng(1)
+    rows = rows_db(rng, PUSH_ROWS)
+    d = dev(nat, rows.nbytes)
+    nat.check(nat.lib.tdsa_memcpy_h2d(0, d, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+    text = []
+    for kind, depth in (("heights", 300), ("levels", 100)):
+        with TraceHistory(depth, N, kind) as h:
+            us, lo, hi = median_us(h, lambda: h.push_rows(None, d.value, PUSH_ROWS), args.warm, args.reps)
+            one = median_us(h, lambda: h.push_rows(None, d.value, 1), args.warm, args.reps)[0]
+            moved = PUSH_ROWS * N * 8
+            text.append(f"push {kind:8s}: {PUSH_ROWS} rows in one call {us:9.1f} us (min {lo:.1f}, max {hi:.1f}) = "
+                        f"{us / PUSH_ROWS:7.3f} us per row, {moved / us / 1e6:7.3f} TB/s = "
+                        f"{100 * moved / us * 1e6 / args.copy_bps:5.1f}% of the copy rate; one row per call {one:7.1f} us")
+    nat.lib.tdsa_dev_free(0, d)
+    return dict(text=text)
+
+
+def view_step(args, name):
+    from topdogspectrumanalyser_amd import TraceHistory, _native as nat
+    rng = np.random.default_rng(2)
+    x = np.linspace(-10, 10, N, dtype=np.float32)
+    kind, depth = ("levels", 100) if name == "surface" else ("heights", 30 if name == "ribbon" else 300)
+    text = []
+    with TraceHistory(depth, N, kind) as h:
+        fill(nat, h, rng, depth + 5)
+        variants = [("index",), ("rgba",)] if name == "lines" else [()]
+        for var in variants:
+            for cols in (None, 1024):
+                n = cols or N
+                R = min(depth, 30) if name == "ribbon" else depth
+                per = {"ribbon": (24, 32), "surface": (4, 12), "lines": (4, 16 if var == ("rgba",) else 1)}[name]
+                out_bytes = R * n * (per[0] + per[1])
+                read_bytes = R * N * 4 + (R * n * 12 if cols else 0)       # the rows; reduced: values + bins written, values read
+                d0, d1 = dev(nat, R * n * per[0]), dev(nat, R * n * per[1])
+                dest = dict(primary=d0.value, colours=d1.value)
+                if name == "ribbon":
+                    on_dev, on_host = (lambda: h.ribbon(x, cols, device_out=dest)), (lambda: h.ribbon(x, cols))
+                elif name == "lines":
+                    on_dev = lambda: h.lines(0, None, var[0], cols, device_out=dest)      # noqa: E731
+                    on_host = lambda: h.lines(0, None, var[0], cols)                      # noqa: E731
+                else:
+                    on_dev, on_host = (lambda: h.surface(cols, device_out=dest)), (lambda: h.surface(cols))
+                us_d = median_us(h, on_dev, args.warm, args.reps)
+                us_h = median_us(h, on_host, args.warm, args.reps)
+                walls = []
+                for _ in range(args.reps):
+                    t0 = time.perf_counter()
+                    on_host()
+                    walls.append((time.perf_counter() - t0) * 1e6)
+                moved = out_bytes + read_bytes
+                d2h = out_bytes + (R * n * 4 if cols else 0) + (2 * n * 4 if name == "lines" else 0)
+                text.append(f"{name:7s} {'/'.join(var) or '-':5s} columns={str(cols):5s}: device destination {us_d[0]:9.1f} us "
+                            f"(min {us_d[1]:.1f}, max {us_d[2]:.1f}), {moved / 1e6:8.2f} MB moved = {moved / us_d[0] / 1e6:6.3f} TB/s = "
+                            f"{100 * moved / us_d[0] * 1e6 / args.copy_bps:5.1f}% of the copy rate; host destination "
+                            f"{us_h[0]:9.1f} us on the stream, {np.median(walls):9.1f} us wall, {d2h / 1e6:8.2f} MB to the host")
+                nat.lib.tdsa_dev_free(0, d0)
+                nat.lib.tdsa_dev_free(0, d1)
+    return dict(text=text)
+
+
+def step_host(args):
+    import history_contract as hc
+    rng = np.random.default_rng(3)
+    x = np.linspace(-10, 10, N, dtype=np.float32)
+    text = []
+    for name, depth, kind in (("ribbon", 30, "heights"), ("lines", 300, "heights"), ("surface", 100, "levels")):
+        m = hc.HistoryModel(depth, N, kind)
+        rows = rows_db(rng, 8)
+        t = []
+        for r in rows:
+            t0 = time.perf_counter()
+            m.push(r)
+            v = m.ribbon(x) if name == "ribbon" else m.lines() if name == "lines" else m.surface()
+            t.append((time.perf_counter() - t0) * 1e3)
+        del v
+        text.append(f"host numpy tick {name:7s} (push + full-width view, {depth} rows x {N} bins): median {np.median(t[1:]):8.2f} ms")
+    return dict(text=text)
+
+
+def run_step(args):
+    if args.step == "copy":
+        return step_copy(args)
+    if args.step == "push":
+        return step_push(args)
+    if args.step == "host":
+        return step_host(args)
+    return view_step(args, args.step)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warm", type=int, default=3)
+    ap.add_argument("--step", choices=STEPS, default=None)
+    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
+    args = ap.parse_args()
+    args.reps = max(args.reps, 20)
+    if args.step:
+        print("RESULT " + json.dumps(run_step(args)), flush=True)
+        return
+    lines = [f"3-D history views at n = {N} bins; every figure is the median of {args.reps} single calls after {args.warm} "
+             "warm-up calls, between device events on the handle's stream unless it says wall"]
+    print(lines[0], flush=True)
+    copy_bps = 0.0
+    for step in STEPS:
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
+               "--copy-bps", repr(copy_bps)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S[step])
+        except subprocess.TimeoutExpired:
+            lines.append(f"{step}: no result within {LIMIT_S[step]} s; stopping")
+            print(lines[-1], flush=True)
+            break
+        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+        if r.returncode != 0 or not res:
+            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
+            print(lines[-1], flush=True)
+            break
+        res = json.loads(res[-1][7:])
+        copy_bps = res.get("copy_bps", copy_bps)
+        for ln in res["text"]:
+            print(ln, flush=True)
+            lines.append(ln)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -13,9 +13,11 @@ from .core.tare_state import TareState  # noqa: F401
 from .analytics import Constellation, ConstellationView  # noqa: F401
 from .zoom import DownConverter, ZoomSpectrum, design_decimator  # noqa: F401
 from .zerospan import ZeroSpan, view_plan  # noqa: F401
+from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401
 
 __all__ = ["SpectrumEngine", "HostPipe", "TraceState", "TraceAverager", "SampleDataSource", "SweepDataSource",
            "HackrfSamplesDataSource", "RtlSamplesDataSource", "MicrophoneSamplesDataSource",
            "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView",
-           "DownConverter", "ZoomSpectrum", "design_decimator", "ZeroSpan", "view_plan", "IqSweepDataSource", "SweepAssembler", "plan_steps"]
+           "DownConverter", "ZoomSpectrum", "design_decimator", "ZeroSpan", "view_plan", "IqSweepDataSource", "SweepAssembler", "plan_steps",
+           "TraceHistory", "RibbonView", "ThreeDView", "SurfaceView"]

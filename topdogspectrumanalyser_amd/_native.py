@@ -23,6 +23,8 @@ SWEEP_INTERP, SWEEP_PEAK = 0, 1
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
 ZS_FREE_RUN, ZS_RISE, ZS_FALL = 0, 1, 2
 ZS_COL_MINMAX, ZS_COL_SAMPLE, ZS_COL_MEAN = 0, 1, 2
+HIST_HEIGHTS, HIST_LEVELS = 0, 1
+HIST_COLOUR_INDEX, HIST_COLOUR_RGBA = 0, 1
 RESET_AVG, RESET_HOLD_MAX, RESET_HOLD_MIN, RESET_DC, RESET_TARE, RESET_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -44,6 +46,18 @@ class ZspanInfo(C.Structure):
     _fields_ = [("start", C.c_int64), ("total", C.c_int64), ("length", C.c_int32), ("triggered", C.c_int32),
                 ("n_columns", C.c_int32), ("min", C.c_float), ("max", C.c_float), ("mean", C.c_double),
                 ("n_at_or_above", C.c_int64), ("n_rise", C.c_int32), ("n_fall", C.c_int32)]
+
+
+class HistoryInfo(C.Structure):
+    _fields_ = [("pushed", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("valid_rows", C.c_int32),
+                ("has_min", C.c_int32), ("live_bin", C.c_int32), ("live_value", C.c_float), ("hold_bin", C.c_int32),
+                ("hold_value", C.c_float), ("live_norm", C.c_double)]
+
+
+class HistoryOut(C.Structure):
+    _fields_ = [("on_device", C.c_int32), ("reserved", C.c_int32), ("primary", C.c_void_p), ("colours", C.c_void_p),
+                ("bins", C.c_void_p), ("hold", C.c_void_p), ("hold_bins", C.c_void_p), ("min_row", C.c_void_p),
+                ("min_bins", C.c_void_p)]
 
 
 # every symbol include/tdsa_hip.h declares: name -> (restype, argtypes)
@@ -134,6 +148,19 @@ _SIGNATURES = {
     "tdsa_zspan_view": (C.c_int, [_P, C.c_int, C.c_double, C.c_size_t, C.c_int, C.c_int, C.POINTER(ZspanInfo), _P, _P]),
     "tdsa_zspan_timer_begin": (C.c_int, [_P]),
     "tdsa_zspan_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_history_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "tdsa_history_destroy": (C.c_int, [_P]),
+    "tdsa_history_set_amplitude": (C.c_int, [_P, C.c_double, C.c_double]),
+    "tdsa_history_reset": (C.c_int, [_P]),
+    "tdsa_history_reset_hold": (C.c_int, [_P]),
+    "tdsa_history_push": (C.c_int, [_P, _P, _P, _P, C.c_int]),
+    "tdsa_history_push_dev": (C.c_int, [_P, _P, _P, C.c_int]),
+    "tdsa_history_ribbon": (C.c_int, [_P, _P, C.c_int, C.POINTER(HistoryOut), C.POINTER(HistoryInfo)]),
+    "tdsa_history_lines": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(HistoryOut),
+                                     C.POINTER(HistoryInfo)]),
+    "tdsa_history_surface": (C.c_int, [_P, C.c_int, C.POINTER(HistoryOut), C.POINTER(HistoryInfo)]),
+    "tdsa_history_timer_begin": (C.c_int, [_P]),
+    "tdsa_history_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_plan_copy": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     "tdsa_waterfall_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_P)]),
     "tdsa_waterfall_destroy": (C.c_int, [_P]),
