@@ -428,8 +428,10 @@ int tdsa_plan_copy(tdsa_plan p, void* dst, const void* src, size_t bytes, int wa
  * grid[i] + 0.5 h (a NaN stays; one lane walks one cell), an empty cell takes the INTERP value.  With no step present
  * every output is NaN (the reference before its first sweep).  _reset: no step is present.  _get_steps: T [n_steps][K]
  * and one byte per step (1 = present) to the host, for tests and tools.  _timer_begin / _end: HIP events on the
- * handle's own stream (where _read runs).  Limits: n_steps <= 4096, 2 <= nfft <= 2^20, 1 <= K <= nfft, 2 <= n_grid <=
- * 2^24, frames_per_step >= 1.  Argument errors are reported before any HIP call. */
+ * handle's own stream (where _read runs); both first put that stream behind the handle's last launch, so updates that
+ * went on a plan's stream before _timer_end are inside the interval, as with the zero span and history timers.
+ * Limits: n_steps <= 4096, 2 <= nfft <= 2^20, 1 <= K <= nfft, 2 <= n_grid <= 2^24, frames_per_step >= 1.  Argument
+ * errors are reported before any HIP call. */
 #define TDSA_SWEEP_DET_SAMPLE 0
 #define TDSA_SWEEP_DET_MAX 1
 #define TDSA_SWEEP_DET_MIN 2

@@ -1,0 +1,162 @@
+"""A handle's launches are totally ordered whichever stream each goes on (the ordering rule of Lane in
+csrc/tdsa_capi_internal.hpp).  Each of the four handle types that can launch on a producer plan's stream is fed the same
+input in six pieces, hopping engine A's stream -> its own -> engine B's stream -> ..., and has to return exactly what a
+second handle returns that was fed the same pieces on its own stream throughout.  Every piece depends on the state the
+piece before it left (filter history, ring position, hold row, a step written twice), so a launch that overtakes its
+predecessor shows.  Every comparison is np.array_equal on arrays of the same dtype and shape; there is no tolerance."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from topdogspectrumanalyser_amd import (DownConverter, SpectrumEngine, SweepAssembler, TraceHistory, ZeroSpan,
+                                        _native as nat)
+
+pytestmark = pytest.mark.gpu
+
+PIECES = 6
+
+
+class _Dev:
+    """A device buffer holding `a` (freed on exit)."""
+
+    def __init__(self, a=None, nbytes=0):
+        self.p = C.c_void_p()
+        a = None if a is None else np.ascontiguousarray(a)
+        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes if a is None else a.nbytes), 16), C.byref(self.p)))
+        if a is not None:
+            nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
+
+    def get(self, n, dtype):
+        a = np.empty(n, dtype)
+        nat.check(nat.lib.tdsa_memcpy_d2h(0, a.ctypes.data_as(C.c_void_p), self.p, a.nbytes))
+        return a
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        nat.lib.tdsa_dev_free(0, self.p)
+
+
+def _same(a, b):
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is b
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+
+
+@pytest.fixture(scope="module")
+def engines():
+    with SpectrumEngine(64) as a, SpectrumEngine(64) as b:
+        yield a, b
+
+
+def _hopping(engines):
+    a, b = engines
+    return [(a, None, b)[i % 3] for i in range(PIECES)]
+
+
+SINGLE = [None] * PIECES
+
+
+# ---- down-converter: D = 3, 7 taps, pieces of 10 complex64 samples ---------------------------------------------------
+def _ddc_run(streams):
+    rng = np.random.default_rng(11)
+    x = (rng.normal(size=10 * PIECES) + 1j * rng.normal(size=10 * PIECES)).astype(np.complex64)
+    taps = np.array([0.05, 0.12, 0.2, 0.26, 0.2, 0.12, 0.05], dtype=np.float32)
+    with DownConverter(3, 48000.0, 5000.0, taps=taps, max_host_samples=64) as ddc, _Dev(x) as d_in, \
+            _Dev(nbytes=8 * (x.size // 3 + 1)) as d_out:
+        got = 0
+        for i, eng in enumerate(streams):
+            got += ddc.process_device(eng, nat.IN_C64, d_in.p.value + 8 * 10 * i, 10, d_out.p.value + 8 * got)
+        ddc.reset()              # waits on the handle's own stream, which it first puts behind the last launch
+        return got, d_out.get(got, np.complex64).view(np.uint64)
+
+
+def test_down_converter_hopping_streams(engines):
+    n, y = _ddc_run(_hopping(engines))
+    n1, y1 = _ddc_run(SINGLE)
+    assert n == n1 == 10 * PIECES // 3
+    assert _same(y, y1)
+
+
+# ---- sweep assembler: 4 steps of nfft 64, one step per piece (steps 0 and 1 are written twice) -----------------------
+SW_N, SW_S, SW_F, SW_K0, SW_K1 = 64, 4, 2, 8, 56
+
+
+def _sweep_run(streams, timer=False):
+    rng = np.random.default_rng(12)
+    rows = rng.normal(-80.0, 12.0, size=(PIECES, SW_F, SW_N)).astype(np.float32)
+    bin_hz = 1000.0
+    centres = 100e6 + np.arange(SW_S) * (SW_K1 - SW_K0) * bin_hz
+    grid = np.linspace(centres[0] - 40e3, centres[-1] + 40e3, 97)
+    with SweepAssembler(SW_N, centres, (SW_K0, SW_K1), bin_hz, grid) as asm, _Dev(rows) as d:
+        if timer:
+            asm.timer_begin()
+        for i, eng in enumerate(streams):
+            asm.update_device(eng, i % SW_S, 1, d.p.value + 4 * i * SW_F * SW_N, SW_F, "max")
+        ms = asm.timer_end() if timer else None
+        T, present = asm.steps()
+        return dict(T=T, present=present, interp=asm.read("interp"), peak=asm.read("peak")), ms
+
+
+@pytest.fixture(scope="module")
+def sweep_single():
+    return _sweep_run(SINGLE)[0]
+
+
+def test_sweep_assembler_hopping_streams(engines, sweep_single):
+    got, _ = _sweep_run(_hopping(engines))
+    assert got["present"].all()
+    assert _same(got, sweep_single)
+
+
+def test_sweep_timer_around_updates_on_an_engine_stream(engines, sweep_single):
+    """timer_end puts the assembler's stream behind updates that went on a plan's stream before it records."""
+    got, ms = _sweep_run([engines[0]] * PIECES, timer=True)
+    assert math.isfinite(ms) and ms >= 0.0
+    assert _same(got, sweep_single)
+
+
+# ---- zero span: capacity 64, pieces of 24 samples (the ring wraps inside the third piece) ----------------------------
+def _zspan_run(streams):
+    rng = np.random.default_rng(13)
+    x = (rng.normal(size=24 * PIECES) + 1j * rng.normal(size=24 * PIECES)).astype(np.complex64)
+    with ZeroSpan(64.0, detector="mag", buffer_s=1.0, max_host_samples=64) as zs, _Dev(x) as d:
+        assert zs.capacity == 64
+        for i, eng in enumerate(streams):
+            assert zs.push_device(eng, nat.IN_C64, d.p.value + 8 * 24 * i, 24) == 24
+        out = {}
+        for name, v in (("free", zs.view("free_run", n_display=64)), ("rise", zs.view("rise", level=1.0, n_display=8))):
+            out[name] = dict(samples=v.samples, start=v.start, total=v.total, length=v.length, triggered=v.triggered,
+                             min=v.min, max=v.max, mean=v.mean, n_at_or_above=v.n_at_or_above, n_rise=v.n_rise,
+                             n_fall=v.n_fall)
+        return out
+
+
+def test_zero_span_hopping_streams(engines):
+    got, one = _zspan_run(_hopping(engines)), _zspan_run(SINGLE)
+    assert got["free"]["total"] == 24 * PIECES and got["free"]["length"] == 64
+    assert _same(got, one)
+
+
+# ---- history: depth 4, 16 bins, pieces of 3 rows ---------------------------------------------------------------------
+def _history_run(streams):
+    rng = np.random.default_rng(14)
+    rows = rng.normal(-60.0, 20.0, size=(3 * PIECES, 16)).astype(np.float32)
+    with TraceHistory(4, 16) as h, _Dev(rows) as d:
+        for i, eng in enumerate(streams):
+            h.push_rows(eng, d.p.value + 4 * 3 * 16 * i, 3)
+        return h.lines()
+
+
+def test_history_hopping_streams(engines):
+    got, one = _history_run(_hopping(engines)), _history_run(SINGLE)
+    assert got["pushed"] == 3 * PIECES and got["valid"] == 4
+    assert _same(got, one)

@@ -33,12 +33,6 @@ STEPS = ("copy", "push", "ribbon", "lines", "surface", "host")
 LIMIT_S = {"copy": 120, "push": 120, "ribbon": 180, "lines": 240, "surface": 180, "host": 300}
 
 
-def dev(nat, nbytes):
-    p = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(p)))
-    return p
-
-
 def rows_db(rng, n_rows):
     return rng.normal(-80.0, 12.0, size=(n_rows, N)).astype(np.float32)
 
@@ -56,7 +50,7 @@ def median_us(h, f, warm, reps):
 
 def fill(nat, h, rng, n_rows):
     rows = rows_db(rng, n_rows)
-    d = dev(nat, rows.nbytes)
+    d = nat._dev_alloc(0, rows.nbytes)
     nat.check(nat.lib.tdsa_memcpy_h2d(0, d, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
     h.push_rows(None, d.value, n_rows)
     h.lines(0, 1) if h.kind == "heights" else h.surface(columns=1)
@@ -87,7 +81,7 @@ def step_push(args):
     from topdogspectrumanalyser_amd import TraceHistory, _native as nat
     rng = np.random.default_rng(1)
     rows = rows_db(rng, PUSH_ROWS)
-    d = dev(nat, rows.nbytes)
+    d = nat._dev_alloc(0, rows.nbytes)
     nat.check(nat.lib.tdsa_memcpy_h2d(0, d, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
     text = []
     for kind, depth in (("heights", 300), ("levels", 100)):
@@ -118,7 +112,7 @@ def view_step(args, name):
                 per = {"ribbon": (24, 32), "surface": (4, 12), "lines": (4, 16 if var == ("rgba",) else 1)}[name]
                 out_bytes = R * n * (per[0] + per[1])
                 read_bytes = R * N * 4 + (R * n * 12 if cols else 0)       # the rows; reduced: values + bins written, values read
-                d0, d1 = dev(nat, R * n * per[0]), dev(nat, R * n * per[1])
+                d0, d1 = nat._dev_alloc(0, R * n * per[0]), nat._dev_alloc(0, R * n * per[1])
                 dest = dict(primary=d0.value, colours=d1.value)
                 if name == "ribbon":
                     on_dev, on_host = (lambda: h.ribbon(x, cols, device_out=dest)), (lambda: h.ribbon(x, cols))

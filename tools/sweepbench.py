@@ -26,6 +26,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from topdogspectrumanalyser_amd import SpectrumEngine, SweepAssembler, _native as nat, plan_steps  # noqa: E402
+from topdogspectrumanalyser_amd._native import _dev_alloc  # noqa: E402
 from topdogspectrumanalyser_amd.sweep import frequency_grid  # noqa: E402
 from topdogspectrumanalyser_amd.zoom import zoom_window  # noqa: E402
 
@@ -34,34 +35,17 @@ GRIDS = ((6000, 1_000_000), (600_000, 10_000))          # points, bin_size
 DETECTORS = ("sample", "max", "min", "avg")
 
 
-def dev(nbytes):
-    p = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(p)))
-    return p
-
-
-def plan_timed(eng, f, warm, reps):
-    """us per call, events on the plan's stream."""
+def timed(h, f, warm, reps):
+    """us per call, events on the stream of h: an engine's plan or an assembler.  The assembler's timer_end first puts
+    its stream behind a launch that went on a plan's stream; everything timed on an assembler here is a read, which
+    runs on the assembler's own stream, so that wait never applies and the figures mean what they did before the timer
+    had it."""
     for _ in range(warm):
         f()
-    nat.check(nat.lib.tdsa_timer_begin(eng._h))
+    h.timer_begin()
     for _ in range(reps):
         f()
-    ms = C.c_float()
-    nat.check(nat.lib.tdsa_timer_end(eng._h, C.byref(ms)))
-    return ms.value * 1e3 / reps
-
-
-def sweep_timed(asm, f, warm, reps):
-    """us per call, events on the assembler's own stream."""
-    for _ in range(warm):
-        f()
-    nat.check(nat.lib.tdsa_sweep_timer_begin(asm._h))
-    for _ in range(reps):
-        f()
-    ms = C.c_float()
-    nat.check(nat.lib.tdsa_sweep_timer_end(asm._h, C.byref(ms)))
-    return ms.value * 1e3 / reps
+    return h.timer_end() * 1e3 / reps
 
 
 def main():
@@ -82,7 +66,7 @@ def main():
     rng = np.random.default_rng(1)
     raw = rng.integers(-128, 128, (S, 2 * n_per)).astype(np.int8)
     row_bytes, det_bytes = 4 * S * F * N, 4 * S * F * K
-    d_iq, d_rows, d_copy = dev(raw.nbytes), dev(row_bytes), dev(det_bytes)
+    d_iq, d_rows, d_copy = _dev_alloc(0, raw.nbytes), _dev_alloc(0, row_bytes), _dev_alloc(0, det_bytes)
     nat.check(nat.lib.tdsa_memcpy_h2d(0, d_iq, raw.ctypes.data_as(C.c_void_p), raw.nbytes))
     say(f"sweep {START / 1e9:.0f} .. {STOP / 1e9:.0f} GHz: fs {FS / 1e6:.0f} MHz, N {N}, kept bins [{k0}, {k1}) of {bin_hz:.3f} Hz, "
         f"{S} steps x {F} frames at hop {N}, int8 IQ in HBM ({raw.nbytes / 1e6:.1f} MB), rows {row_bytes / 1e6:.1f} MB, "
@@ -96,22 +80,22 @@ def main():
             def batch():
                 eng.process_device_batch(nat.IN_I8, d_iq.value, 2 * n_per, S, n_per, N, F, d_rows.value)
 
-            us_a = plan_timed(eng, batch, args.warm, args.reps)
+            us_a = timed(eng, batch, args.warm, args.reps)
             say(f"(a) tdsa_process_dev_batch, rows alone: {us_a:9.1f} us")
-            us_d = plan_timed(eng, lambda: nat.check(nat.lib.tdsa_plan_copy(eng._h, d_copy, d_rows, det_bytes, 0)),
+            us_d = timed(eng, lambda: nat.check(nat.lib.tdsa_plan_copy(eng._h, d_copy, d_rows, det_bytes, 0)),
                               args.warm, args.reps)
             say(f"(d) device-to-device copy of {det_bytes / 1e6:.1f} MB: {us_d:9.1f} us "
                 f"({det_bytes / us_d / 1e3:.0f} GB/s read, as much written)")
             for n_grid, bin_size in GRIDS:
                 grid = frequency_grid(START, STOP, bin_size)
                 assert grid.size == n_grid
-                d_out = dev(8 * n_grid)
+                d_out = _dev_alloc(0, 8 * n_grid)
                 try:
                     with SweepAssembler(N, centres, (k0, k1), bin_hz, grid) as asm:
                         say(f"--- grid of {n_grid} points ({bin_size / 1e3:.0f} kHz cells, {bin_size / bin_hz:.1f} bins each)")
                         batch()
                         for det in DETECTORS:
-                            us = plan_timed(eng, lambda: asm.update_device(eng, 0, S, d_rows.value, F, det),
+                            us = timed(eng, lambda: asm.update_device(eng, 0, S, d_rows.value, F, det),
                                             args.warm, args.reps)
                             rd = 4 * S * K if det == "sample" else det_bytes
                             say(f"(c) detector {det:>6s} alone: {us:9.1f} us, reads {rd / 1e6:7.1f} MB, {rd / us / 1e3:6.0f} GB/s"
@@ -119,7 +103,7 @@ def main():
                                    if det != "sample" else ""))
                         eng.synchronize()
                         for mode in ("interp", "peak"):
-                            us = sweep_timed(asm, lambda: asm.read(mode, out_dev=d_out.value, to_host=False),
+                            us = timed(asm, lambda: asm.read(mode, out_dev=d_out.value, to_host=False),
                                              args.warm, args.reps)
                             rd = 8 * n_grid + 4 * S * K
                             say(f"(c) stitch {mode:>6s} alone: {us:9.1f} us, reads <= {rd / 1e6:6.1f} MB "
@@ -127,9 +111,9 @@ def main():
                         for det in DETECTORS:
                             def run():
                                 asm.run_device(eng, nat.IN_I8, d_iq.value, 2 * n_per, 0, S, n_per, N, F, det)
-                            us_run = plan_timed(eng, run, args.warm, args.reps)
+                            us_run = timed(eng, run, args.warm, args.reps)
                             for mode in ("interp", "peak"):
-                                us_read = sweep_timed(asm, lambda: asm.read(mode, out_dev=d_out.value, to_host=False),
+                                us_read = timed(asm, lambda: asm.read(mode, out_dev=d_out.value, to_host=False),
                                                       1, args.reps)
                                 run()
                                 asm.read(mode)
@@ -143,7 +127,7 @@ def main():
                         if n_grid == GRIDS[0][0]:
                             for mib in (8, 16, 32, 64, 128, 256):
                                 asm.set_chunk_bytes(mib << 20)
-                                us = plan_timed(eng, lambda: asm.run_device(eng, nat.IN_I8, d_iq.value, 2 * n_per, 0, S,
+                                us = timed(eng, lambda: asm.run_device(eng, nat.IN_I8, d_iq.value, 2 * n_per, 0, S,
                                                                             n_per, N, F, "avg"), args.warm, args.reps)
                                 steps = max(1, min(S, (mib << 20) // (4 * F * N)))
                                 say(f"    run_dev avg, row scratch bound {mib:4d} MiB ({steps:3d} steps per chunk): {us:9.1f} us")

@@ -24,17 +24,12 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from topdogspectrumanalyser_amd import DataProcessor, ZeroSpan, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd._native import _dev_alloc  # noqa: E402
 
 FS = 20e6
 N_IN = 20_000_000
 TICK = 400_000
 HBM_BPS = 6.29e12
-
-
-def dev(nbytes):
-    p = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(p)))
-    return p
 
 
 def timed(zs, f, warm, reps):
@@ -79,7 +74,7 @@ def main():
 
     rng = np.random.default_rng(1)
     raw = pulse_train(rng, 2 * N_IN)                       # two seconds: fills the ring
-    d_i8, d_c64 = dev(raw.nbytes // 2), dev(8 * N_IN)
+    d_i8, d_c64 = _dev_alloc(0, raw.nbytes // 2), _dev_alloc(0, 8 * N_IN)
     try:
         nat.check(nat.lib.tdsa_memcpy_h2d(0, d_i8, raw.ctypes.data_as(C.c_void_p), raw.nbytes // 2))
         cplx = to_c64(raw[:2 * N_IN])

@@ -19,6 +19,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from topdogspectrumanalyser_amd import SpectrumEngine, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd._native import _dev_alloc  # noqa: E402
 from topdogspectrumanalyser_amd.zoom import DownConverter, ZoomSpectrum  # noqa: E402
 
 FS = 20e6
@@ -28,21 +29,13 @@ HBM_BPS = 6.29e12
 TARGET_US = 45.0
 
 
-def dev(nbytes):
-    p = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(p)))
-    return p
-
-
 def timed(eng, f, warm, reps):
     for _ in range(warm):
         f()
-    nat.check(nat.lib.tdsa_timer_begin(eng._h))
+    eng.timer_begin()
     for _ in range(reps):
         f()
-    ms = C.c_float()
-    nat.check(nat.lib.tdsa_timer_end(eng._h, C.byref(ms)))
-    return ms.value * 1e3 / reps
+    return eng.timer_end() * 1e3 / reps
 
 
 def main():
@@ -60,8 +53,8 @@ def main():
     rng = np.random.default_rng(1)
     raw = rng.integers(-128, 128, 2 * N_IN).astype(np.int8)
     cplx = (raw[0::2].astype(np.float32) / 128 + 1j * raw[1::2].astype(np.float32) / 128).astype(np.complex64)
-    d_i8, d_c64 = dev(raw.nbytes), dev(cplx.nbytes)
-    d_out = dev(8 * (N_IN // 2 + 8))
+    d_i8, d_c64 = _dev_alloc(0, raw.nbytes), _dev_alloc(0, cplx.nbytes)
+    d_out = _dev_alloc(0, 8 * (N_IN // 2 + 8))
     nat.check(nat.lib.tdsa_memcpy_h2d(0, d_i8, raw.ctypes.data_as(C.c_void_p), raw.nbytes))
     nat.check(nat.lib.tdsa_memcpy_h2d(0, d_c64, cplx.ctypes.data_as(C.c_void_p), cplx.nbytes))
     del cplx
@@ -88,7 +81,7 @@ def main():
         with ZoomSpectrum(FS, D, N, offset_hz=0.1 * FS, hop=hop) as z:
             z.engine.configure(hold_max=True)
             frames = z.frames_completed_by(N_IN) + 4
-            d_rows = dev(4 * frames * N)
+            d_rows = _dev_alloc(0, 4 * frames * N)
             try:
                 us = timed(z.engine, lambda: z.process_device(nat.IN_I8, d_i8.value, N_IN, d_rows.value),
                            args.warm, args.reps)

@@ -225,3 +225,47 @@ class TdsaError(RuntimeError):
 def check(rc: int) -> None:
     if rc != TDSA_OK:
         raise TdsaError(f"tdsa error {rc}: {lib.tdsa_last_error_string().decode()}")
+
+
+def _dev_alloc(device: int, nbytes: int) -> C.c_void_p:
+    p = C.c_void_p()
+    check(lib.tdsa_dev_alloc(device, max(int(nbytes), 8), C.byref(p)))
+    return p
+
+
+class _Handle:
+    """Lifetime of an object that owns device resources: close() once, from __del__ and on leaving a `with` block.  The
+    plain case is one library handle in self._h, which close() hands to the library function _destroy names; a class that
+    owns something else (several handles, a pipe's _q, a source's engine) overrides close() and needs neither."""
+    _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            getattr(lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class _Timer:
+    """HIP-event timer of a handle: _timer names the library's (begin, end) pair."""
+    _timer = ("", "")
+
+    def timer_begin(self) -> None:
+        check(getattr(lib, self._timer[0])(self._h))
+
+    def timer_end(self) -> float:
+        """Milliseconds of device time on the handle's stream since timer_begin."""
+        ms = C.c_float()
+        check(getattr(lib, self._timer[1])(self._h, C.byref(ms)))
+        return float(ms.value)

@@ -22,6 +22,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _native as nat
+from ._native import _Handle
 from .engine import SpectrumEngine
 
 AMP_BINS = 512
@@ -112,30 +113,9 @@ class DutyCycle(DutyCycleAnalyser):
     """The analyser of core/duty_cycle.py under the name earlier callers of this module use."""
 
 
-class _Handle:
-    _destroy = None
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            type(self)._destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
 class DensityHistogram(_Handle):
     """DensityDisplay._hist on the device: [n_bins, 512] float32."""
-    _destroy = staticmethod(lambda h: nat.lib.tdsa_density_destroy(h))
+    _destroy = "tdsa_density_destroy"
 
     def __init__(self, n_bins: int, decay: float = 0.96, device: int = 0):
         self.n_bins = int(n_bins)
@@ -180,7 +160,7 @@ class DensityHistogram(_Handle):
 class WaterfallRing(_Handle):
     """Waterfall._buf on the device ([H, n_bins] float32, every line once; the reference doubles it to make the view one
     slice) with the reference's pointer walk and dedup."""
-    _destroy = staticmethod(lambda h: nat.lib.tdsa_waterfall_destroy(h))
+    _destroy = "tdsa_waterfall_destroy"
 
     def __init__(self, history_lines: int, n_bins: int, min_db: float, device: int = 0):
         self.history_lines = int(history_lines)
@@ -291,7 +271,7 @@ class ConstellationResult:
 class Constellation(_Handle):
     """Constellation2D.update_iq_data on the device: RMS AGC, nearest-symbol EVM and the 2-D IQ density histogram, bit
     for bit the reference's numpy."""
-    _destroy = staticmethod(lambda h: nat.lib.tdsa_constellation_destroy(h))
+    _destroy = "tdsa_constellation_destroy"
 
     def __init__(self, max_host_samples: int = 1 << 20, device: int = 0, modulation: str = "qpsk",
                  range_: float = 1.5, bins: int = CONSTELLATION_BINS):

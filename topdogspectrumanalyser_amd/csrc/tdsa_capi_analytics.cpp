@@ -195,8 +195,8 @@ int tdsa_rows_marker_peaks(tdsa_plan p, const float* rows_dev, int n_rows, int n
 }
 
 // ---- density histogram --------------------------------------------------------------------------
-struct tdsa_density_s {
-  int device = 0, n = 0;
+struct tdsa_density_s : Lane {
+  int n = 0;
   float decay = 0.96f;
   float* d_hist = nullptr;     // [n][512]
   float* d_img = nullptr;      // log1p image scratch
@@ -204,7 +204,6 @@ struct tdsa_density_s {
   float* h_row[2] = {nullptr, nullptr};   // pinned, device-visible staging of host rows (the kernel reads them in place)
   hipEvent_t ev_row[2] = {nullptr, nullptr};   // ... free again when the update that read them has run
   unsigned tick = 0;
-  hipStream_t stream = nullptr;
 };
 
 int tdsa_density_create(int device_id, int n_bins, float decay, tdsa_density* out) {
@@ -237,14 +236,13 @@ int tdsa_density_create(int device_id, int n_bins, float decay, tdsa_density* ou
 
 int tdsa_density_destroy(tdsa_density d) {
   if (!d) return TDSA_OK;
-  (void)hipSetDevice(d->device);
-  if (d->stream) (void)hipStreamSynchronize(d->stream);
+  d->drain();
   free_all({d->d_hist, d->d_img, d->d_u8});
   for (int k = 0; k < 2; ++k) {
     if (d->h_row[k]) (void)hipHostFree(d->h_row[k]);
     if (d->ev_row[k]) (void)hipEventDestroy(d->ev_row[k]);
   }
-  if (d->stream) (void)hipStreamDestroy(d->stream);
+  d->close();
   delete d;
   return TDSA_OK;
 }
@@ -330,8 +328,8 @@ int tdsa_density_read_u8(tdsa_density d, uint8_t* img_host, float* levels2) {
 }
 
 // ---- waterfall ring -----------------------------------------------------------------------------
-struct tdsa_waterfall_s {
-  int device = 0, n = 0, history = 0;
+struct tdsa_waterfall_s : Lane {
+  int n = 0, history = 0;
   int ptr = 0;
   bool have_last = false;
   float* d_ring = nullptr;     // [history][n]: every line once, the view is two copies
@@ -343,7 +341,6 @@ struct tdsa_waterfall_s {
   int* d_info = nullptr;       // {new rows, last new row} of the push in flight, for the scatter
   int* h_info = nullptr;       // the same two words, pinned: what the host waits for
   size_t cap = 0;
-  hipStream_t stream = nullptr;
 };
 
 int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float min_db, tdsa_waterfall* out) {
@@ -377,12 +374,11 @@ int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float mi
 
 int tdsa_waterfall_destroy(tdsa_waterfall w) {
   if (!w) return TDSA_OK;
-  (void)hipSetDevice(w->device);
-  if (w->stream) (void)hipStreamSynchronize(w->stream);
+  w->drain();
   free_all({w->d_ring, w->d_last, w->d_u8, w->d_row, w->d_flags, w->d_info});
   if (w->h_row) (void)hipHostFree(w->h_row);
   if (w->h_info) (void)hipHostFree(w->h_info);
-  if (w->stream) (void)hipStreamDestroy(w->stream);
+  w->close();
   delete w;
   return TDSA_OK;
 }

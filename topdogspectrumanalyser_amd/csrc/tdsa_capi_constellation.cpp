@@ -5,22 +5,20 @@
 using namespace tdsa;
 
 // ---- constellation analysis (tdsa_constellation.hip) ---------------------------------------------
-struct tdsa_constellation_s {
-  int device = 0;
+struct tdsa_constellation_s : Lane {
   size_t max_host = 0;
-  hipStream_t stream = nullptr;
   void* h_in = nullptr;          // pinned staging of a host block (up to 8 bytes per sample)
   void* d_in = nullptr;
   void* d_tab = nullptr;         // [2][kCstMaxPoints] doubles (floats for a float32 table)
   CstTable tab;
   int bins = kCstMaxBins;
   double range = 1.5;
-  float* d_bs_pow = nullptr;     // per-block sums, grown on demand
+  float* d_bs_pow = nullptr;     // per-block sums, grown on demand, each with its own capacity
   void* d_bs_evm = nullptr;
-  size_t bs_cap = 0;
+  size_t bs_pow_cap = 0, bs_evm_cap = 0;
   float* d_rms = nullptr;        // per-segment results, grown on demand
   double* d_evm = nullptr;
-  size_t seg_cap = 0;
+  size_t rms_cap = 0, evm_cap = 0;
   unsigned char* d_res = nullptr;   // the host path's results: evm, rms, counts, tail i[n_tail] then q[n_tail] ...
   unsigned char* h_out = nullptr;   // ... and their pinned read-back (one copy)
 };
@@ -30,36 +28,18 @@ namespace {
 constexpr size_t kCstOutCounts = 16;   // byte offsets in d_res / h_out
 constexpr size_t kCstOutTail = kCstOutCounts + size_t(kCstMaxBins) * kCstMaxBins * sizeof(unsigned);
 
-int cst_in_bytes(int fmt) { return fmt == TDSA_IN_C64 ? 8 : 2; }
-
 int cst_check_format(int fmt) {
   if (fmt == TDSA_IN_I8 || fmt == TDSA_IN_U8 || fmt == TDSA_IN_C64) return TDSA_OK;
   return fail(TDSA_ERR_ARG, "in_format=%d: the constellation pass takes complex IQ (TDSA_IN_I8 / _U8 / _C64); real input "
               "(the reference's Hilbert transform) is not supported", fmt);
 }
 
+// no stream to drain: every call that launches ends with a wait
 int cst_reserve(tdsa_constellation c, size_t n_blocks, size_t n_seg) {
-  if (n_blocks > c->bs_cap) {
-    if (c->d_bs_pow) HIPCHK(hipFree(c->d_bs_pow));
-    if (c->d_bs_evm) HIPCHK(hipFree(c->d_bs_evm));
-    c->d_bs_pow = nullptr;
-    c->d_bs_evm = nullptr;
-    c->bs_cap = 0;
-    HIPCHK(hipMalloc(&c->d_bs_pow, n_blocks * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_bs_evm, n_blocks * sizeof(double)));
-    c->bs_cap = n_blocks;
-  }
-  if (n_seg > c->seg_cap) {
-    if (c->d_rms) HIPCHK(hipFree(c->d_rms));
-    if (c->d_evm) HIPCHK(hipFree(c->d_evm));
-    c->d_rms = nullptr;
-    c->d_evm = nullptr;
-    c->seg_cap = 0;
-    HIPCHK(hipMalloc(&c->d_rms, n_seg * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_evm, n_seg * sizeof(double)));
-    c->seg_cap = n_seg;
-  }
-  return TDSA_OK;
+  TRY(grow_device(&c->d_bs_pow, &c->bs_pow_cap, n_blocks, nullptr, sizeof(float)));
+  TRY(grow_device(&c->d_bs_evm, &c->bs_evm_cap, n_blocks, nullptr, sizeof(double)));
+  TRY(grow_device(&c->d_rms, &c->rms_cap, n_seg, nullptr, sizeof(float)));
+  return grow_device(&c->d_evm, &c->evm_cap, n_seg, nullptr, sizeof(double));
 }
 
 CstLaunch cst_args(tdsa_constellation c, int fmt, const void* in, size_t seg_len, size_t hop, int n_seg) {
@@ -116,12 +96,11 @@ int tdsa_constellation_create(int device_id, size_t max_host_samples, tdsa_const
 
 int tdsa_constellation_destroy(tdsa_constellation c) {
   if (!c) return TDSA_OK;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  c->drain();
   free_all({c->d_in, c->d_tab, c->d_bs_pow, c->d_bs_evm, c->d_rms, c->d_evm, c->d_res});
   if (c->h_in) (void)hipHostFree(c->h_in);
   if (c->h_out) (void)hipHostFree(c->h_out);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  c->close();
   delete c;
   return TDSA_OK;
 }
@@ -194,7 +173,7 @@ int tdsa_constellation_process(tdsa_constellation c, int in_format, const void* 
   if (n_tail < 0) return fail(TDSA_ERR_ARG, "n_tail=%d", n_tail);
   const size_t nt = tail_iq ? (size_t(n_tail) < n ? size_t(n_tail) : n) : 0;
   HIPCHK(hipSetDevice(c->device));
-  const size_t bytes = n * size_t(cst_in_bytes(in_format));
+  const size_t bytes = n * size_t(bytes_per_sample(in_format));
   std::memcpy(c->h_in, iq_host, bytes);   // the previous call has waited: the staging is free
   HIPCHK(hipMemcpyAsync(c->d_in, c->h_in, bytes, hipMemcpyHostToDevice, c->stream));
   const size_t cnt_bytes = size_t(c->bins) * c->bins * sizeof(unsigned);

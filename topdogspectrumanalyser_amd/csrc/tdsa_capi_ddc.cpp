@@ -5,12 +5,9 @@
 using namespace tdsa;
 
 // ---- zoom front end: digital down-conversion (tdsa_ddc.hip) ------------------------------------------------------
-struct tdsa_ddc_s {
-  int device = 0, D = 2, max_taps = 1, max_phases = kDdcBlock;
+struct tdsa_ddc_s : Lane {
+  int D = 2, max_taps = 1, max_phases = kDdcBlock;
   size_t max_host = 0;
-  hipStream_t stream = nullptr;       // the host entry points' stream
-  hipEvent_t ev_done = nullptr;       // the last launch, on whichever stream it went
-  hipStream_t last = nullptr;
   float2* d_nco = nullptr;            // [kDdcNcoTable]
   float* d_taps = nullptr;            // [max_phases][D], zero beyond n_taps
   float2* d_hist[2] = {nullptr, nullptr};   // [max_phases * D] mixed inputs each, ping-pong
@@ -39,13 +36,11 @@ uint32_t ddc_phase_at(const tdsa_ddc d, long long n) {
 
 // zero history, input count and phase (the step is kept)
 int ddc_clear(tdsa_ddc d) {
-  HIPCHK(hipSetDevice(d->device));
-  if (d->last && d->last != d->stream) HIPCHK(hipStreamWaitEvent(d->stream, d->ev_done, 0));
+  TRY(d->own_stream());
   const size_t hb = size_t(d->max_phases) * d->D * sizeof(float2);
   HIPCHK(hipMemsetAsync(d->d_hist[0], 0, hb, d->stream));
   HIPCHK(hipMemsetAsync(d->d_hist[1], 0, hb, d->stream));
-  HIPCHK(hipEventRecord(d->ev_done, d->stream));
-  d->last = d->stream;
+  TRY(d->done(d->stream));
   d->n_total = 0;
   d->n_b = 0;
   d->p_b = 0;
@@ -72,7 +67,7 @@ int ddc_run(tdsa_ddc d, hipStream_t s, int fmt, const void* in, size_t n_in, flo
   const long long m_end = (d->n_total + (long long)n_in + D - 1) / D;
   *n_out = size_t(m_end - m_first);
   if (n_in == 0) return TDSA_OK;
-  if (d->last && d->last != s) HIPCHK(hipStreamWaitEvent(s, d->ev_done, 0));
+  TRY(d->order(s));
   DdcLaunch a;
   a.in = in;
   a.fmt = fmt;
@@ -91,8 +86,7 @@ int ddc_run(tdsa_ddc d, hipStream_t s, int fmt, const void* in, size_t n_in, flo
   a.m_first = m_first;
   a.n_out = m_end - m_first;
   HIPCHK(launch_ddc(a, s));
-  HIPCHK(hipEventRecord(d->ev_done, s));
-  d->last = s;
+  TRY(d->done(s));
   d->cur ^= 1;
   d->n_total += (long long)n_in;
   return TDSA_OK;
@@ -125,8 +119,7 @@ int tdsa_ddc_create(int device_id, int decimation, int max_taps, size_t max_host
     const double th = 2.0 * M_PI * double(k) / double(kDdcNcoTable);
     nco[k] = make_float2(float(std::cos(th)), float(-std::sin(th)));
   }
-  hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming);
+  hipError_t e = d->open(false);
   if (e == hipSuccess) e = hipMalloc(&d->d_nco, kDdcNcoTable * sizeof(float2));
   if (e == hipSuccess) e = hipMalloc(&d->d_taps, tb);
   if (e == hipSuccess) e = hipMalloc(&d->d_hist[0], hb);
@@ -153,14 +146,11 @@ int tdsa_ddc_create(int device_id, int decimation, int max_taps, size_t max_host
 
 int tdsa_ddc_destroy(tdsa_ddc d) {
   if (!d) return TDSA_OK;
-  (void)hipSetDevice(d->device);
-  if (d->ev_done) (void)hipEventSynchronize(d->ev_done);
-  if (d->stream) (void)hipStreamSynchronize(d->stream);
+  d->drain();
   free_all({d->d_nco, d->d_taps, d->d_hist[0], d->d_hist[1], d->d_in, d->d_out});
   if (d->h_in) (void)hipHostFree(d->h_in);
   if (d->h_out) (void)hipHostFree(d->h_out);
-  if (d->ev_done) (void)hipEventDestroy(d->ev_done);
-  if (d->stream) (void)hipStreamDestroy(d->stream);
+  d->close();
   delete d;
   return TDSA_OK;
 }
@@ -174,10 +164,8 @@ int tdsa_ddc_set_taps(tdsa_ddc d, const float* taps_host, int n_taps) {
     if (!std::isfinite(taps_host[k])) return fail(TDSA_ERR_ARG, "tap %d is not finite", k);
   std::vector<float> pad(size_t(d->max_phases) * d->D, 0.0f);   // [phase][residue]: tap q D + r at q * D + r
   std::memcpy(pad.data(), taps_host, size_t(n_taps) * sizeof(float));
-  HIPCHK(hipSetDevice(d->device));
-  if (d->last && d->last != d->stream) HIPCHK(hipStreamWaitEvent(d->stream, d->ev_done, 0));
+  TRY(d->own_stream());
   HIPCHK(hipMemcpyAsync(d->d_taps, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
-  d->last = d->stream;
   d->n_taps = n_taps;
   d->phases = ddc_phases(n_taps, d->D);
   TRY(ddc_clear(d));
@@ -227,11 +215,7 @@ int tdsa_ddc_process_dev(tdsa_ddc d, tdsa_plan p, int in_format, const void* iq_
     return fail(TDSA_ERR_ARG, "output pointer must be aligned to one complex64 sample");
   *n_out = 0;
   if (n_in == 0) return TDSA_OK;
-  HIPCHK(hipSetDevice(d->device));
-  hipStream_t s = d->stream;
-  if (p) {   // on the producer's stream: ordered after it, and its later work after us
-    JOIN(p);
-    s = p->stream;
-  }
+  hipStream_t s;
+  TRY(d->producer_stream(p, &s));
   return ddc_run(d, s, in_format, iq_dev, n_in, static_cast<float2*>(out_dev), n_out);
 }

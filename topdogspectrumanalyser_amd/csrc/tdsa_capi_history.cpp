@@ -8,17 +8,13 @@ static_assert(sizeof(tdsa_history_info) == 48, "tdsa_history_info is part of the
 static_assert(sizeof(tdsa_history_out) == 64, "tdsa_history_out is part of the ABI");
 
 // ---- 3-D history views: trace ring, hold row, ribbon / line-stack / surface passes (tdsa_history.hip) ----------------
-struct tdsa_history_s {
-  int device = 0, depth = 0, n = 0, kind = TDSA_HIST_HEIGHTS;
+struct tdsa_history_s : Lane {         // its stream: host pushes, views, the timer
+  int depth = 0, n = 0, kind = TDSA_HIST_HEIGHTS;
   double ref_level = 0.0, range_db = 100.0;
   long long pushed = 0;               // rows since the last reset
   int head = 0;                       // slot of the next row
   int has_min = 0;                    // the newest push brought a min trace
-  hipStream_t stream = nullptr;       // host pushes, views, the timer
-  hipEvent_t ev_done = nullptr;       // the last launch, on whichever stream it went
-  hipStream_t last = nullptr;
   hipEvent_t ev_in = nullptr;         // the last host rows have left their pinned staging
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
   float* d_ring = nullptr;            // [depth][n]
   float* d_hold = nullptr;            // [n]
   float* d_min = nullptr;             // [n]
@@ -45,22 +41,10 @@ constexpr size_t kSmallBytes = 256;
 
 int hist_check(tdsa_history h) { return h ? TDSA_OK : fail(TDSA_ERR_ARG, "null history"); }
 
-int hist_own_stream(tdsa_history h) {
-  HIPCHK(hipSetDevice(h->device));
-  if (h->last && h->last != h->stream) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_done, 0));
-  return TDSA_OK;
-}
-
-int hist_done(tdsa_history h, hipStream_t s) {
-  HIPCHK(hipEventRecord(h->ev_done, s));
-  h->last = s;
-  return TDSA_OK;
-}
-
 // enqueue n_rows rows at `rows` (device) on stream s
 int hist_run(tdsa_history h, hipStream_t s, const float* rows, int n_rows, const float* hold_in, const float* min_in,
              int update_hold) {
-  if (h->last && h->last != s) HIPCHK(hipStreamWaitEvent(s, h->ev_done, 0));
+  TRY(h->order(s));
   const int skip = n_rows > h->depth ? n_rows - h->depth : 0;
   const int first = (h->head + skip) % h->depth, count = n_rows - skip;   // the slots this push writes: their keys start at 0
   const int piece = count < h->depth - first ? count : h->depth - first;
@@ -85,7 +69,7 @@ int hist_run(tdsa_history h, hipStream_t s, const float* rows, int n_rows, const
   a.range = float(h->range_db);
   a.zscale = 8.0f;
   HIPCHK(launch_hist_push(a, s));
-  TRY(hist_done(h, s));
+  TRY(h->done(s));
   h->head = int((static_cast<long long>(h->head) + n_rows) % h->depth);
   h->pushed += n_rows;
   h->has_min = a.heights && min_in != nullptr;
@@ -161,7 +145,7 @@ int hist_finish(tdsa_history h, tdsa_history_info* info, int rows, int cols, int
     r.bins = &d->hold_bin;
     HIPCHK(launch_hist_reduce(r, h->stream));
   }
-  TRY(hist_done(h, h->stream));
+  TRY(h->done(h->stream));
   HIPCHK(hipMemcpyAsync(h->h_small, d, sizeof(Small), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   Small sm;
@@ -214,11 +198,8 @@ int tdsa_history_create(int device_id, int depth, int n_bins, int kind, tdsa_his
   h->n = n_bins;
   h->kind = kind;
   const size_t cells = size_t(depth) * size_t(n_bins);
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming);
+  hipError_t e = h->open(true);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev_t0);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev_t1);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_ring), cells * 4);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_hold), size_t(n_bins) * 4);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_min), size_t(n_bins) * 4);
@@ -239,15 +220,12 @@ int tdsa_history_create(int device_id, int depth, int n_bins, int kind, tdsa_his
 
 int tdsa_history_destroy(tdsa_history h) {
   if (!h) return TDSA_OK;
-  (void)hipSetDevice(h->device);
-  if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  h->drain();
   free_all({h->d_ring, h->d_hold, h->d_min, h->d_keys, h->d_in, h->d_tmp});
   if (h->h_in) (void)hipHostFree(h->h_in);
   if (h->h_small) (void)hipHostFree(h->h_small);
-  for (hipEvent_t ev : {h->ev_done, h->ev_in, h->ev_t0, h->ev_t1})
-    if (ev) (void)hipEventDestroy(ev);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (h->ev_in) (void)hipEventDestroy(h->ev_in);
+  h->close();
   delete h;
   return TDSA_OK;
 }
@@ -264,7 +242,7 @@ int tdsa_history_set_amplitude(tdsa_history h, double ref_level, double range_db
 
 int tdsa_history_reset(tdsa_history h) {
   TRY(hist_check(h));
-  TRY(hist_own_stream(h));
+  TRY(h->own_stream());
   HIPCHK(hipMemsetAsync(h->d_ring, 0, size_t(h->depth) * size_t(h->n) * 4, h->stream));
   HIPCHK(hipMemsetAsync(h->d_hold, 0, size_t(h->n) * 4, h->stream));
   HIPCHK(hipMemsetAsync(h->d_min, 0, size_t(h->n) * 4, h->stream));
@@ -272,21 +250,21 @@ int tdsa_history_reset(tdsa_history h) {
   h->pushed = 0;
   h->head = 0;
   h->has_min = 0;
-  return hist_done(h, h->stream);
+  return h->done(h->stream);
 }
 
 int tdsa_history_reset_hold(tdsa_history h) {
   TRY(hist_check(h));
-  TRY(hist_own_stream(h));
+  TRY(h->own_stream());
   HIPCHK(hipMemsetAsync(h->d_hold, 0, size_t(h->n) * 4, h->stream));
-  return hist_done(h, h->stream);
+  return h->done(h->stream);
 }
 
 int tdsa_history_push(tdsa_history h, const float* live_host, const float* max_host, const float* min_host, int update_hold) {
   TRY(hist_check(h));
   if (!live_host) return fail(TDSA_ERR_ARG, "null row");
   if (h->kind != TDSA_HIST_HEIGHTS && (max_host || min_host)) return fail(TDSA_ERR_ARG, "max / min traces go with heights only");
-  TRY(hist_own_stream(h));
+  TRY(h->own_stream());
   const size_t n = size_t(h->n), row = round256(n * 4);
   TRY(grow_pinned(&h->h_in, &h->h_in_bytes, 3 * row, h->stream));
   TRY(grow_device(&h->d_in, &h->d_in_floats, 3 * row / 4, h->stream, 4));
@@ -309,12 +287,8 @@ int tdsa_history_push_dev(tdsa_history h, tdsa_plan p, const float* rows_dev, in
   if (reinterpret_cast<uintptr_t>(rows_dev) % 4 != 0) return fail(TDSA_ERR_ARG, "rows pointer must be aligned to one float");
   if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and history live on different devices");
   if (n_rows == 0) return TDSA_OK;
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  if (p) {   // on the producer's stream: ordered after it, and its later work after us
-    JOIN(p);
-    s = p->stream;
-  }
+  hipStream_t s;
+  TRY(h->producer_stream(p, &s));
   return hist_run(h, s, rows_dev, n_rows, nullptr, nullptr, 1);
 }
 
@@ -322,7 +296,7 @@ int tdsa_history_ribbon(tdsa_history h, const float* x_host, int columns, const 
   TRY(hist_check_view(h, columns, out, info));
   if (h->kind != TDSA_HIST_HEIGHTS) return fail(TDSA_ERR_ARG, "the ribbon view needs a history of heights");
   if (!x_host) return fail(TDSA_ERR_ARG, "null x");
-  TRY(hist_own_stream(h));
+  TRY(h->own_stream());
   const int rows = h->depth < kHistRibbonRows ? h->depth : kHistRibbonRows;
   const int cols = columns ? columns : h->n;
   const size_t cells = size_t(rows) * size_t(cols);
@@ -373,7 +347,7 @@ int tdsa_history_lines(tdsa_history h, int first, int count, int colour_mode, co
   if (colour_mode == TDSA_HIST_COLOUR_RGBA && !palette_host) return fail(TDSA_ERR_ARG, "null palette");
   if (first < 0 || count < 0 || first > h->depth || count > h->depth - first)
     return fail(TDSA_ERR_ARG, "first=%d, count=%d: lines 0 .. %d", first, count, h->depth);
-  TRY(hist_own_stream(h));
+  TRY(h->own_stream());
   const int cols = columns ? columns : h->n;
   const size_t cells = size_t(count) * size_t(cols);
   const size_t px = colour_mode == TDSA_HIST_COLOUR_RGBA ? 16 : 1;
@@ -420,7 +394,7 @@ int tdsa_history_lines(tdsa_history h, int first, int count, int colour_mode, co
 int tdsa_history_surface(tdsa_history h, int columns, const tdsa_history_out* out, tdsa_history_info* info) {
   TRY(hist_check_view(h, columns, out, info));
   if (h->kind != TDSA_HIST_LEVELS) return fail(TDSA_ERR_ARG, "the surface view needs a history of levels");
-  TRY(hist_own_stream(h));
+  TRY(h->own_stream());
   const int rows = h->depth, cols = columns ? columns : h->n;
   const size_t cells = size_t(rows) * size_t(cols);
   const bool own = !out->on_device;
@@ -463,17 +437,11 @@ int tdsa_history_surface(tdsa_history h, int columns, const tdsa_history_out* ou
 
 int tdsa_history_timer_begin(tdsa_history h) {
   TRY(hist_check(h));
-  TRY(hist_own_stream(h));
-  HIPCHK(hipEventRecord(h->ev_t0, h->stream));
-  return TDSA_OK;
+  return h->timer_begin();
 }
 
 int tdsa_history_timer_end(tdsa_history h, float* elapsed_ms) {
   TRY(hist_check(h));
   if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  TRY(hist_own_stream(h));
-  HIPCHK(hipEventRecord(h->ev_t1, h->stream));
-  HIPCHK(hipEventSynchronize(h->ev_t1));
-  HIPCHK(hipEventElapsedTime(elapsed_ms, h->ev_t0, h->ev_t1));
-  return TDSA_OK;
+  return h->timer_end(elapsed_ms);
 }

@@ -1,6 +1,8 @@
 // tdsa_capi_internal.hpp - what the translation units of the C-ABI layer (tdsa_capi_*.cpp, one per handle type or
 // concern) share: error reporting, the status macros, the host idioms they all use, the few functions that cross files,
-// and the plan itself.  The public face of the library is include/tdsa_hip.h.
+// the plan itself, and - at the end, because it needs the plan - Lane, the base of the handle types: their stream,
+// their lifetime, and the one rule that orders a handle's launches whichever stream each goes on.  The public face of
+// the library is include/tdsa_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,7 +48,8 @@ int join_streams(tdsa_plan p);
 // the plan's main stream signals, `consumer` waits
 int plan_order_before(tdsa_plan p, hipStream_t consumer);
 
-inline int bytes_per_sample(int fmt) { return fmt == TDSA_IN_C64 ? 8 : 2; }
+// of a format its caller has range-checked (TDSA_IN_I8 .. _C64, zero span: .. _F32R)
+inline int bytes_per_sample(int fmt) { return fmt == TDSA_IN_C64 ? 8 : fmt == TDSA_IN_F32R ? 4 : 2; }
 
 // how a raw sample of an input format becomes a float: (float(byte ^ its byte of xor_mask) - off) * scale; complex64 as is
 struct InFormat {
@@ -270,3 +273,88 @@ struct tdsa_plan_s {
   std::vector<hipEvent_t> prof_events;   // pairs (begin, end) around frame-kernel launches
   size_t prof_used = 0;
 };
+
+namespace tdsa {
+#pragma GCC visibility push(hidden)
+
+// The base of the handle types: a device, a stream of the handle's own and what creates, drains and destroys them.
+//
+// The down-converter, the sweep assembler, zero span and the history also launch on a producer plan's stream, and ONE
+// rule keeps their state coherent when it moves between streams: a handle's launches are totally ordered through
+// ev_done, whichever stream each goes on.  Every launch on a stream s is bracketed by order(s) and done(s): s first
+// waits for ev_done if the last launch went elsewhere, and afterwards ev_done stands for this one.  The handles that
+// wait for their stream in every call (constellation, density, waterfall, trace) use device, stream, drain and close
+// only; they go behind a producer with plan_order_before.
+struct Lane {
+  int device = 0;
+  hipStream_t stream = nullptr;    // the handle's own: host entry points, views, the timer
+  hipEvent_t ev_done = nullptr;    // the last launch, on whichever stream it went
+  hipStream_t last = nullptr;      // that stream
+  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;   // timer_begin / timer_end
+
+  // create: the stream, ev_done and, for a handle with a timer, its two events
+  hipError_t open(bool timer) {
+    hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_done, hipEventDisableTiming);
+    if (e == hipSuccess && timer) e = hipEventCreate(&ev_t0);
+    if (e == hipSuccess && timer) e = hipEventCreate(&ev_t1);
+    return e;
+  }
+  // destroy, before the buffers are freed: nothing of the handle's is in flight any more, on any stream ...
+  void drain() {
+    (void)hipSetDevice(device);
+    if (ev_done) (void)hipEventSynchronize(ev_done);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+  // ... and after: the events, then the stream (also of a handle whose create failed half way)
+  void close() {
+    for (hipEvent_t ev : {ev_done, ev_t0, ev_t1})
+      if (ev) (void)hipEventDestroy(ev);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+
+  // order stream s behind the last launch if that went elsewhere
+  int order(hipStream_t s) {
+    if (last && last != s) HIPCHK(hipStreamWaitEvent(s, ev_done, 0));
+    return TDSA_OK;
+  }
+  // the launch on s is the last one
+  int done(hipStream_t s) {
+    HIPCHK(hipEventRecord(ev_done, s));
+    last = s;
+    return TDSA_OK;
+  }
+  // the handle's own stream behind whatever ran last on another
+  int own_stream() {
+    HIPCHK(hipSetDevice(device));
+    return order(stream);
+  }
+  // where a call fed by plan p launches: on the producer's main stream - ordered after everything the plan has in
+  // flight, and the plan's later work after us - or without a plan on the handle's own
+  int producer_stream(tdsa_plan p, hipStream_t* s) {
+    HIPCHK(hipSetDevice(device));
+    *s = stream;
+    if (!p) return TDSA_OK;
+    JOIN(p);
+    *s = p->stream;
+    return TDSA_OK;
+  }
+
+  // device time on the handle's stream between the two calls; both first put it behind the last launch, so work that
+  // went on a plan's stream in between is inside the interval
+  int timer_begin() {
+    TRY(own_stream());
+    HIPCHK(hipEventRecord(ev_t0, stream));
+    return TDSA_OK;
+  }
+  int timer_end(float* elapsed_ms) {
+    TRY(own_stream());
+    HIPCHK(hipEventRecord(ev_t1, stream));
+    HIPCHK(hipEventSynchronize(ev_t1));
+    HIPCHK(hipEventElapsedTime(elapsed_ms, ev_t0, ev_t1));
+    return TDSA_OK;
+  }
+};
+
+#pragma GCC visibility pop
+}  // namespace tdsa

@@ -8,13 +8,9 @@
 using namespace tdsa;
 
 // ---- stepped sweeps: step detector and stitch (tdsa_sweep.hip) -----------------------------------------------------
-struct tdsa_sweep_s {
-  int device = 0, nfft = 0, S = 0, n_grid = 0;
-  hipStream_t stream = nullptr;       // _read, _get_steps, and updates without a plan
-  hipEvent_t ev_done = nullptr;       // the last launch, on whichever stream it went
-  hipStream_t last = nullptr;
+struct tdsa_sweep_s : Lane {           // its stream: _read, _get_steps, the timer, and updates without a plan
+  int nfft = 0, S = 0, n_grid = 0;
   hipEvent_t ev_tab = nullptr;        // the last upload of the step table has left its pinned staging
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;   // _timer_begin / _end
   bool geometry = false;
   std::vector<double> centres;
   double bin_hz = 0.0, h = 0.0;
@@ -59,7 +55,7 @@ int sweep_check_update(tdsa_sweep w, tdsa_plan p, int first_step, int n_steps, c
 // the detector over rows of n_steps steps on stream s; those steps become present
 int sweep_detect(tdsa_sweep w, hipStream_t s, int first_step, int n_steps, const float* rows, int frames,
                  size_t step_stride, int det) {
-  if (w->last && w->last != s) HIPCHK(hipStreamWaitEvent(s, w->ev_done, 0));
+  TRY(w->order(s));
   SweepDetLaunch a;
   a.rows = rows;
   a.step_stride = (long long)step_stride;
@@ -71,8 +67,7 @@ int sweep_detect(tdsa_sweep w, hipStream_t s, int first_step, int n_steps, const
   a.detector = det;
   a.T = w->d_T + size_t(first_step) * size_t(w->k1 - w->k0);
   HIPCHK(launch_sweep_detector(a, s));
-  HIPCHK(hipEventRecord(w->ev_done, s));
-  w->last = s;
+  TRY(w->done(s));
   for (int i = 0; i < n_steps; ++i) {
     if (!w->valid[first_step + i]) w->tab_dirty = true;
     w->valid[first_step + i] = 1;
@@ -102,13 +97,6 @@ int sweep_upload_table(tdsa_sweep w) {
   return TDSA_OK;
 }
 
-// the handle's stream behind whatever ran last on another
-int sweep_own_stream(tdsa_sweep w) {
-  HIPCHK(hipSetDevice(w->device));
-  if (w->last && w->last != w->stream) HIPCHK(hipStreamWaitEvent(w->stream, w->ev_done, 0));
-  return TDSA_OK;
-}
-
 }  // namespace
 
 int tdsa_sweep_create(int device_id, int nfft, int n_steps, int n_grid, tdsa_sweep* out) {
@@ -126,11 +114,8 @@ int tdsa_sweep_create(int device_id, int nfft, int n_steps, int n_grid, tdsa_swe
   w->n_grid = n_grid;
   w->valid.assign(size_t(n_steps), 0);
   const size_t S = size_t(n_steps);
-  hipError_t e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev_done, hipEventDisableTiming);
+  hipError_t e = w->open(true);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev_tab, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&w->ev_t0);
-  if (e == hipSuccess) e = hipEventCreate(&w->ev_t1);
   if (e == hipSuccess) e = hipMalloc(&w->d_grid, size_t(n_grid) * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&w->d_out, size_t(n_grid) * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&w->d_tab, S * sizeof(double2));
@@ -146,14 +131,11 @@ int tdsa_sweep_create(int device_id, int nfft, int n_steps, int n_grid, tdsa_swe
 
 int tdsa_sweep_destroy(tdsa_sweep w) {
   if (!w) return TDSA_OK;
-  (void)hipSetDevice(w->device);
-  if (w->ev_done) (void)hipEventSynchronize(w->ev_done);
-  if (w->stream) (void)hipStreamSynchronize(w->stream);
+  w->drain();
   free_all({w->d_T, w->d_grid, w->d_out, w->d_tab, w->d_step_of, w->d_rows});
   if (w->h_tab) (void)hipHostFree(w->h_tab);
-  for (hipEvent_t ev : {w->ev_done, w->ev_tab, w->ev_t0, w->ev_t1})
-    if (ev) (void)hipEventDestroy(ev);
-  if (w->stream) (void)hipStreamDestroy(w->stream);
+  if (w->ev_tab) (void)hipEventDestroy(w->ev_tab);
+  w->close();
   delete w;
   return TDSA_OK;
 }
@@ -211,12 +193,8 @@ int tdsa_sweep_update_dev(tdsa_sweep w, tdsa_plan p, int first_step, int n_steps
   if ((reinterpret_cast<uintptr_t>(rows_dev) % 4) != 0) return fail(TDSA_ERR_ARG, "rows pointer must be aligned to one float");
   if (n_steps == 0) return TDSA_OK;
   if (step_stride_floats == 0) step_stride_floats = size_t(frames_per_step) * size_t(w->nfft);
-  HIPCHK(hipSetDevice(w->device));
-  hipStream_t s = w->stream;
-  if (p) {   // on the producer's stream: ordered after it, and its later work after us
-    JOIN(p);
-    s = p->stream;
-  }
+  hipStream_t s;
+  TRY(w->producer_stream(p, &s));
   return sweep_detect(w, s, first_step, n_steps, rows_dev, frames_per_step, step_stride_floats, detector);
 }
 
@@ -256,7 +234,7 @@ int tdsa_sweep_read(tdsa_sweep w, int mode, double* out_f64_host, double* out_f6
     return fail(TDSA_ERR_ARG, "peak mode needs an ascending grid (grid[1] - grid[0] = %g)", w->h);
   if (out_f64_dev && (reinterpret_cast<uintptr_t>(out_f64_dev) % 8) != 0)
     return fail(TDSA_ERR_ARG, "output pointer must be aligned to one float64");
-  TRY(sweep_own_stream(w));
+  TRY(w->own_stream());
   TRY(sweep_upload_table(w));
   SweepStitchLaunch a;
   a.tab = w->d_tab;
@@ -272,8 +250,7 @@ int tdsa_sweep_read(tdsa_sweep w, int mode, double* out_f64_host, double* out_f6
   a.mode = mode;
   a.out = out_f64_dev ? out_f64_dev : w->d_out;
   HIPCHK(launch_sweep_stitch(a, w->stream));
-  HIPCHK(hipEventRecord(w->ev_done, w->stream));
-  w->last = w->stream;
+  TRY(w->done(w->stream));
   if (out_f64_host) {
     HIPCHK(hipMemcpyAsync(out_f64_host, a.out, size_t(w->n_grid) * sizeof(double), hipMemcpyDeviceToHost, w->stream));
     HIPCHK(hipStreamSynchronize(w->stream));
@@ -284,7 +261,7 @@ int tdsa_sweep_read(tdsa_sweep w, int mode, double* out_f64_host, double* out_f6
 int tdsa_sweep_get_steps(tdsa_sweep w, float* T_host, unsigned char* valid_host) {
   if (!w) return fail(TDSA_ERR_ARG, "null sweep");
   if (!w->geometry) return fail(TDSA_ERR_STATE, "no geometry: call tdsa_sweep_set_geometry first");
-  TRY(sweep_own_stream(w));
+  TRY(w->own_stream());
   if (T_host)
     HIPCHK(hipMemcpyAsync(T_host, w->d_T, size_t(w->S) * size_t(w->k1 - w->k0) * sizeof(float), hipMemcpyDeviceToHost,
                           w->stream));
@@ -295,17 +272,11 @@ int tdsa_sweep_get_steps(tdsa_sweep w, float* T_host, unsigned char* valid_host)
 
 int tdsa_sweep_timer_begin(tdsa_sweep w) {
   if (!w) return fail(TDSA_ERR_ARG, "null sweep");
-  TRY(sweep_own_stream(w));
-  HIPCHK(hipEventRecord(w->ev_t0, w->stream));
-  return TDSA_OK;
+  return w->timer_begin();
 }
 
 int tdsa_sweep_timer_end(tdsa_sweep w, float* elapsed_ms) {
   if (!w) return fail(TDSA_ERR_ARG, "null sweep");
   if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  HIPCHK(hipSetDevice(w->device));
-  HIPCHK(hipEventRecord(w->ev_t1, w->stream));
-  HIPCHK(hipEventSynchronize(w->ev_t1));
-  HIPCHK(hipEventElapsedTime(elapsed_ms, w->ev_t0, w->ev_t1));
-  return TDSA_OK;
+  return w->timer_end(elapsed_ms);
 }

@@ -3,9 +3,8 @@
 
 using namespace tdsa;
 
-struct tdsa_trace_s {
-  int device = 0, n = 0;
-  hipStream_t stream = nullptr;
+struct tdsa_trace_s : Lane {
+  int n = 0;
   float* d_in = nullptr;
   float* d_live = nullptr;
   float* d_hold_max = nullptr;
@@ -53,12 +52,11 @@ int tdsa_trace_create(int device_id, int n, tdsa_trace* out) {
 
 int tdsa_trace_destroy(tdsa_trace t) {
   if (!t) return TDSA_OK;
-  (void)hipSetDevice(t->device);
-  if (t->stream) (void)hipStreamSynchronize(t->stream);
+  t->drain();
   free_all({t->d_in, t->d_live, t->d_hold_max, t->d_hold_min, t->d_tare_base, t->d_tare_acc, t->d_avg, t->d_avg_in});
   if (t->h_pin) (void)hipHostFree(t->h_pin);
   if (t->h_pin_avg) (void)hipHostFree(t->h_pin_avg);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
+  t->close();
   delete t;
   return TDSA_OK;
 }

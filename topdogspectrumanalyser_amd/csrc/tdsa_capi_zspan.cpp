@@ -7,15 +7,10 @@ using namespace tdsa;
 static_assert(sizeof(tdsa_zspan_info) == 64, "tdsa_zspan_info is part of the ABI");
 
 // ---- zero span: detector ring, trigger search, trace view (tdsa_zerospan.hip) ---------------------------------------
-struct tdsa_zspan_s {
-  int device = 0;
+struct tdsa_zspan_s : Lane {           // its stream: host pushes, views, the timer
   long long cap = 0;
   size_t max_host = 0;
-  hipStream_t stream = nullptr;       // host pushes, views, the timer
-  hipEvent_t ev_done = nullptr;       // the last launch, on whichever stream it went
-  hipStream_t last = nullptr;
   hipEvent_t ev_in = nullptr;         // the last host chunk has left its pinned staging
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;   // _timer_begin / _end
   int detector = TDSA_ZS_DET_REAL;
   float log_floor = 0.f, offset_db = 0.f;
   long long total = 0;                // samples pushed since the last reset
@@ -23,7 +18,7 @@ struct tdsa_zspan_s {
   void* h_in = nullptr;               // pinned staging of one host chunk (up to 8 bytes per sample) ...
   void* d_in = nullptr;               // ... and where it lands
   unsigned char* d_res = nullptr;     // ZsCtrl, kZsMaxBlocks ZsPart, then the trace of a view without a device pointer
-  size_t res_floats = 0;              // floats of trace it has room for
+  size_t res_bytes = 0;
   void* h_res = nullptr;              // pinned: what one view reads back
   size_t h_res_bytes = 0;
 };
@@ -31,8 +26,6 @@ struct tdsa_zspan_s {
 namespace {
 
 constexpr size_t kZsBounceMax = size_t(8) << 20;   // traces up to 8 MiB come back through the pinned block, larger ones directly
-
-int zspan_bytes_per_sample(int fmt) { return fmt == TDSA_IN_C64 ? 8 : fmt == TDSA_IN_F32R ? 4 : 2; }
 
 int zspan_check_format(int fmt) {
   if (fmt >= TDSA_IN_I8 && fmt <= TDSA_IN_F32R) return TDSA_OK;
@@ -54,11 +47,11 @@ int zspan_check_push(tdsa_zspan z, int fmt, const void* src, size_t n) {
 
 // enqueue the detector over n samples at `dev` on stream s: the last `cap` of them, in up to two contiguous pieces
 int zspan_run(tdsa_zspan z, hipStream_t s, int fmt, const void* dev, size_t n) {
-  if (z->last && z->last != s) HIPCHK(hipStreamWaitEvent(s, z->ev_done, 0));
+  TRY(z->order(s));
   const long long skip = (long long)n > z->cap ? (long long)n - z->cap : 0;
   long long left = (long long)n - skip;
   long long t = z->total + skip;
-  const unsigned char* src = static_cast<const unsigned char*>(dev) + size_t(skip) * zspan_bytes_per_sample(fmt);
+  const unsigned char* src = static_cast<const unsigned char*>(dev) + size_t(skip) * bytes_per_sample(fmt);
   while (left > 0) {
     const long long pos = t % z->cap;
     const long long piece = left < z->cap - pos ? left : z->cap - pos;
@@ -71,31 +64,12 @@ int zspan_run(tdsa_zspan z, hipStream_t s, int fmt, const void* dev, size_t n) {
     a.log_floor = z->log_floor;
     a.offset_db = z->offset_db;
     HIPCHK(launch_zspan_push(a, s));
-    src += size_t(piece) * zspan_bytes_per_sample(fmt);
+    src += size_t(piece) * bytes_per_sample(fmt);
     t += piece;
     left -= piece;
   }
-  HIPCHK(hipEventRecord(z->ev_done, s));
-  z->last = s;
+  TRY(z->done(s));
   z->total += (long long)n;
-  return TDSA_OK;
-}
-
-// the handle's stream behind whatever ran last on another
-int zspan_own_stream(tdsa_zspan z) {
-  HIPCHK(hipSetDevice(z->device));
-  if (z->last && z->last != z->stream) HIPCHK(hipStreamWaitEvent(z->stream, z->ev_done, 0));
-  return TDSA_OK;
-}
-
-int zspan_grow_result(tdsa_zspan z, size_t floats) {
-  if (floats <= z->res_floats && z->d_res) return TDSA_OK;
-  HIPCHK(hipStreamSynchronize(z->stream));
-  if (z->d_res) HIPCHK(hipFree(z->d_res));
-  z->d_res = nullptr;
-  z->res_floats = 0;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&z->d_res), kZsOutOffset + floats * sizeof(float)));
-  z->res_floats = floats;
   return TDSA_OK;
 }
 
@@ -113,11 +87,8 @@ int tdsa_zspan_create(int device_id, size_t capacity, size_t max_host_samples, t
   z->device = device_id;
   z->cap = (long long)capacity;
   z->max_host = max_host_samples;
-  hipError_t e = hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&z->ev_done, hipEventDisableTiming);
+  hipError_t e = z->open(true);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&z->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&z->ev_t0);
-  if (e == hipSuccess) e = hipEventCreate(&z->ev_t1);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&z->d_ring), capacity * sizeof(float));
   if (e == hipSuccess) e = hipHostMalloc(&z->h_in, max_host_samples * 8, hipHostMallocDefault);
   if (e == hipSuccess) e = hipMalloc(&z->d_in, max_host_samples * 8);
@@ -131,15 +102,12 @@ int tdsa_zspan_create(int device_id, size_t capacity, size_t max_host_samples, t
 
 int tdsa_zspan_destroy(tdsa_zspan z) {
   if (!z) return TDSA_OK;
-  (void)hipSetDevice(z->device);
-  if (z->ev_done) (void)hipEventSynchronize(z->ev_done);
-  if (z->stream) (void)hipStreamSynchronize(z->stream);
+  z->drain();
   free_all({z->d_ring, z->d_in, z->d_res});
   if (z->h_in) (void)hipHostFree(z->h_in);
   if (z->h_res) (void)hipHostFree(z->h_res);
-  for (hipEvent_t ev : {z->ev_done, z->ev_in, z->ev_t0, z->ev_t1})
-    if (ev) (void)hipEventDestroy(ev);
-  if (z->stream) (void)hipStreamDestroy(z->stream);
+  if (z->ev_in) (void)hipEventDestroy(z->ev_in);
+  z->close();
   delete z;
   return TDSA_OK;
 }
@@ -164,8 +132,8 @@ int tdsa_zspan_reset(tdsa_zspan z) {
 int tdsa_zspan_push(tdsa_zspan z, int in_format, const void* samples_host, size_t n) {
   TRY(zspan_check_push(z, in_format, samples_host, n));
   if (n == 0) return TDSA_OK;
-  TRY(zspan_own_stream(z));
-  const size_t bps = size_t(zspan_bytes_per_sample(in_format));
+  TRY(z->own_stream());
+  const size_t bps = size_t(bytes_per_sample(in_format));
   const unsigned char* src = static_cast<const unsigned char*>(samples_host);
   if (n > size_t(z->cap)) {   // only the last `capacity` samples can be seen again
     const size_t skip = n - size_t(z->cap);
@@ -187,15 +155,11 @@ int tdsa_zspan_push(tdsa_zspan z, int in_format, const void* samples_host, size_
 int tdsa_zspan_push_dev(tdsa_zspan z, tdsa_plan p, int in_format, const void* samples_dev, size_t n) {
   TRY(zspan_check_push(z, in_format, samples_dev, n));
   if (p && p->device != z->device) return fail(TDSA_ERR_ARG, "plan and zero span live on different devices");
-  if ((reinterpret_cast<uintptr_t>(samples_dev) % uintptr_t(zspan_bytes_per_sample(in_format))) != 0)
-    return fail(TDSA_ERR_ARG, "samples pointer must be aligned to one sample (%d bytes)", zspan_bytes_per_sample(in_format));
+  if ((reinterpret_cast<uintptr_t>(samples_dev) % uintptr_t(bytes_per_sample(in_format))) != 0)
+    return fail(TDSA_ERR_ARG, "samples pointer must be aligned to one sample (%d bytes)", bytes_per_sample(in_format));
   if (n == 0) return TDSA_OK;
-  HIPCHK(hipSetDevice(z->device));
-  hipStream_t s = z->stream;
-  if (p) {   // on the producer's stream: ordered after it, and its later work after us
-    JOIN(p);
-    s = p->stream;
-  }
+  hipStream_t s;
+  TRY(z->producer_stream(p, &s));
   return zspan_run(z, s, in_format, samples_dev, n);
 }
 
@@ -231,8 +195,8 @@ int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int 
     n_pairs = se - 1 - ss > 0 ? se - 1 - ss : 0;   // i = ss .. se - 2
   }
   const size_t out_floats = P == 0 ? size_t(length) : size_t(P) * (col_detector == TDSA_ZS_COL_MINMAX ? 2 : 1);
-  TRY(zspan_own_stream(z));
-  TRY(zspan_grow_result(z, out_dev ? 0 : out_floats));
+  TRY(z->own_stream());
+  TRY(grow_device(&z->d_res, &z->res_bytes, kZsOutOffset + (out_dev ? 0 : out_floats) * sizeof(float), z->stream));
   ZsCtrl* ctrl = reinterpret_cast<ZsCtrl*>(z->d_res);
   float* d_out = out_dev ? out_dev : reinterpret_cast<float*>(z->d_res + kZsOutOffset);
   HIPCHK(hipMemsetAsync(z->d_res, 0, kZsCtrlZeroed, z->stream));
@@ -263,8 +227,7 @@ int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int 
   v.out = d_out;
   v.blocks = zs_view_blocks(v);
   HIPCHK(launch_zspan_view(v, z->stream));
-  HIPCHK(hipEventRecord(z->ev_done, z->stream));
-  z->last = z->stream;
+  TRY(z->done(z->stream));
   // one read-back: the control block, the partials and - when it is ours and small - the trace behind them
   const size_t head_bytes = sizeof(ZsCtrl) + size_t(v.blocks) * sizeof(ZsPart);
   const bool bounce = out_host && !out_dev && out_floats * sizeof(float) <= kZsBounceMax;
@@ -301,17 +264,11 @@ int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int 
 
 int tdsa_zspan_timer_begin(tdsa_zspan z) {
   if (!z) return fail(TDSA_ERR_ARG, "null zero span");
-  TRY(zspan_own_stream(z));
-  HIPCHK(hipEventRecord(z->ev_t0, z->stream));
-  return TDSA_OK;
+  return z->timer_begin();
 }
 
 int tdsa_zspan_timer_end(tdsa_zspan z, float* elapsed_ms) {
   if (!z) return fail(TDSA_ERR_ARG, "null zero span");
   if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  TRY(zspan_own_stream(z));
-  HIPCHK(hipEventRecord(z->ev_t1, z->stream));
-  HIPCHK(hipEventSynchronize(z->ev_t1));
-  HIPCHK(hipEventElapsedTime(elapsed_ms, z->ev_t0, z->ev_t1));
-  return TDSA_OK;
+  return z->timer_end(elapsed_ms);
 }

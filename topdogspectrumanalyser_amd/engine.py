@@ -20,7 +20,9 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-class SpectrumEngine:
+class SpectrumEngine(nat._Handle, nat._Timer):
+    _timer = ("tdsa_timer_begin", "tdsa_timer_end")
+
     def __init__(self, nfft: int, max_frames: int = 1, device: int = 0):
         self.nfft = int(nfft)
         self.max_frames = int(max_frames)
@@ -37,18 +39,6 @@ class SpectrumEngine:
         if getattr(self, "_h", None) is not None and self._h:
             nat.lib.tdsa_destroy(self._h)
             self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ------------------------------------------------------------------ configuration
     def set_window(self, window: np.ndarray) -> None:
@@ -296,37 +286,20 @@ class SpectrumEngine:
         nat.check(nat.lib.tdsa_profile_read(self._h, C.byref(n), C.byref(ms)))
         return n.value, float(ms.value)
 
-    # ------------------------------------------------------------------ timing (HIP events, plan stream)
-    def timer_begin(self) -> None:
-        nat.check(nat.lib.tdsa_timer_begin(self._h))
-
-    def timer_end(self) -> float:
-        ms = C.c_float()
-        nat.check(nat.lib.tdsa_timer_end(self._h, C.byref(ms)))
-        return float(ms.value)
+    # timing (HIP events, plan stream): timer_begin / timer_end of nat._Timer
 
 
-class TraceState:
+class TraceState(nat._Handle):
     """Device-side state of ONE displayed trace of n bins (any n): hold traces, tare accumulator and
     baseline, TraceAverager buffer.  The arithmetic of DataProcessor._apply_cal_offset / _apply_tare /
     _update_max_hold / _update_min_hold and TraceAverager.process runs in HIP kernels."""
+    _destroy = "tdsa_trace_destroy"
 
     def __init__(self, n: int, device: int = 0):
         self.n = int(n)
         self.device = int(device)
         self._h = C.c_void_p()
         nat.check(nat.lib.tdsa_trace_create(self.device, self.n, C.byref(self._h)))
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            nat.lib.tdsa_trace_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, what: int = nat.RESET_ALL) -> None:
         nat.check(nat.lib.tdsa_trace_reset(self._h, what))
@@ -375,7 +348,7 @@ class TraceState:
         return out
 
 
-class HostPipe:
+class HostPipe(nat._Handle):
     """Batch front end over `tdsa_pipe_*`: the producer fills pinned slots, H2D / frame kernel / D2H of
     neighbouring slots overlap.  Counterpart of the reader thread + queue of HackrfSamplesDataSource
     (datasources/hackrf_samples.py:191-305 of the reference) for recorders and offline analysis.
@@ -406,18 +379,6 @@ class HostPipe:
             self._q = C.c_void_p()
             if self in self._eng._pipes:
                 self._eng._pipes.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def acquire(self) -> np.ndarray:
         """Next free pinned input slot as a numpy view (int8/uint8: interleaved I,Q; complex64: samples)."""

@@ -78,10 +78,12 @@ def _row(a, n: int, what: str) -> np.ndarray:
     return a
 
 
-class TraceHistory:
+class TraceHistory(nat._Handle, nat._Timer):
     """The last `depth` rows of `n_bins` bins on the device.  kind "heights": rows are stored as
     z = clip((dB - (ref - range)) / range * 8, 0, 8) with the amplitude in force at the push (ribbon, lines);
     "levels": as pushed, normalised at view time (surface)."""
+    _destroy = "tdsa_history_destroy"
+    _timer = ("tdsa_history_timer_begin", "tdsa_history_timer_end")
 
     def __init__(self, depth: int, n_bins: int, kind: str = "heights", device: int = 0):
         if kind not in KINDS:
@@ -90,24 +92,6 @@ class TraceHistory:
         self.ref_level, self.range_db = 0.0, 100.0
         self._h = C.c_void_p()
         nat.check(nat.lib.tdsa_history_create(self.device, self.depth, self.n_bins, KINDS[kind], C.byref(self._h)))
-
-    # ------------------------------------------------------------------ lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            nat.lib.tdsa_history_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ------------------------------------------------------------------ input
     def set_amplitude(self, ref_level: float, range_db: float) -> None:
@@ -226,15 +210,6 @@ class TraceHistory:
 
     ribbon_faces = staticmethod(ribbon_faces)
     line_palette = staticmethod(line_palette)
-
-    def timer_begin(self) -> None:
-        nat.check(nat.lib.tdsa_history_timer_begin(self._h))
-
-    def timer_end(self) -> float:
-        """Milliseconds of device time on the handle's stream since timer_begin."""
-        ms = C.c_float()
-        nat.check(nat.lib.tdsa_history_timer_end(self._h, C.byref(ms)))
-        return float(ms.value)
 
 
 # ---------------------------------------------------------------------------------------------------- the widgets

@@ -23,7 +23,8 @@ from . import _native as nat
 from .datasources.base import SweepDataSource
 from .engine import SpectrumEngine
 from .utils.constants import DSPConstants
-from .zoom import _dev_alloc, zoom_window
+from ._native import _dev_alloc
+from .zoom import zoom_window
 
 MAX_STEPS = 4096
 DETECTORS = {"sample": nat.SWEEP_DET_SAMPLE, "max": nat.SWEEP_DET_MAX, "min": nat.SWEEP_DET_MIN,
@@ -88,9 +89,11 @@ def frequency_grid(start_hz: float, stop_hz: float, bin_size: float) -> np.ndarr
     return np.linspace(start_hz, stop_hz, int((stop_hz - start_hz) / bin_size))
 
 
-class SweepAssembler:
+class SweepAssembler(nat._Handle, nat._Timer):
     """Detector and stitch of one sweep geometry (tdsa_sweep_*): T[steps][K] and the flags of the steps present stay on
     the device between calls."""
+    _destroy = "tdsa_sweep_destroy"
+    _timer = ("tdsa_sweep_timer_begin", "tdsa_sweep_timer_end")
 
     def __init__(self, nfft: int, centres, kept: Tuple[int, int], bin_hz: float, grid, device: int = 0):
         self.nfft = int(nfft)
@@ -112,24 +115,6 @@ class SweepAssembler:
         except Exception:
             self.close()
             raise
-
-    # ------------------------------------------------------------------ lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            nat.lib.tdsa_sweep_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ------------------------------------------------------------------ geometry
     @property
@@ -184,7 +169,7 @@ class SweepAssembler:
         return T, valid.astype(bool)
 
 
-class IqSweepDataSource(SweepDataSource):
+class IqSweepDataSource(nat._Handle, SweepDataSource):
     """Sweeps [start_freq, stop_freq] by retuning: `capture(centre_hz, n_samples)` returns one block of IQ per step
     (complex, or interleaved int8 / uint8 pairs, as in_format says), the steps' rows are made by `.engine` (window, dB
     mode, PSD scale, calibration and DC removal are set there, as on any SpectrumEngine) and stitched onto the
@@ -284,12 +269,6 @@ class IqSweepDataSource(SweepDataSource):
         if getattr(self, "engine", None) is not None and self.engine._h:
             self._release()
             self.engine.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def sweep_once(self) -> np.ndarray:
         """One sweep, synchronously: a capture per step into one staging buffer, one copy, one run_device, one read."""

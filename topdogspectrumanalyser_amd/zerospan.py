@@ -19,7 +19,8 @@ import numpy as np
 
 from . import _native as nat
 from .engine import SpectrumEngine
-from .zoom import DownConverter, _dev_alloc
+from ._native import _dev_alloc
+from .zoom import DownConverter
 
 BUFFER_SECONDS = 2.0            # the reference's _ZS_BUFFER_SECONDS
 MIN_CAPACITY, MAX_CAPACITY = 4, 1 << 28
@@ -100,8 +101,9 @@ def _zs_input(samples):
     return a, nat.IN_F32R, a.size
 
 
-class ZeroSpan:
+class ZeroSpan(nat._Handle, nat._Timer):
     """Detector ring of the last `buffer_s` seconds on the device, and views of it."""
+    _timer = ("tdsa_zspan_timer_begin", "tdsa_zspan_timer_end")
 
     def __init__(self, sample_rate: float, window_s: float = 0.01, detector: str = "real",
                  decimation: Optional[int] = None, offset_hz: float = 0.0, taps=None, device: int = 0,
@@ -152,18 +154,6 @@ class ZeroSpan:
             self.ddc.close()
         if eng is not None:
             eng.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ------------------------------------------------------------------ configuration
     @property
@@ -263,12 +253,3 @@ class ZeroSpan:
         P = int(info.n_columns)
         cols = out[:rows * P].reshape(rows, P) if rows == 2 else out[:P]
         return ZeroSpanView(info, self.rate, None, cols)
-
-    def timer_begin(self) -> None:
-        nat.check(nat.lib.tdsa_zspan_timer_begin(self._h))
-
-    def timer_end(self) -> float:
-        """Milliseconds of device time on the handle's stream since timer_begin."""
-        ms = C.c_float()
-        nat.check(nat.lib.tdsa_zspan_timer_end(self._h, C.byref(ms)))
-        return float(ms.value)

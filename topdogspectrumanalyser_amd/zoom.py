@@ -19,6 +19,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as nat
+from ._native import _dev_alloc
 from .analytics import _iq_input
 from .engine import SpectrumEngine
 from .utils.constants import DSPConstants
@@ -71,14 +72,9 @@ def alias_free_bins(nfft: int, decimation: int, sample_rate: float) -> slice:
     return slice(int(idx[0]), int(idx[-1]) + 1)
 
 
-def _dev_alloc(device: int, nbytes: int) -> C.c_void_p:
-    p = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(device, max(int(nbytes), 8), C.byref(p)))
-    return p
-
-
-class DownConverter:
+class DownConverter(nat._Handle):
     """Mixes `offset_hz` to 0 Hz and decimates by `decimation` (complex64 out, one output per D inputs)."""
+    _destroy = "tdsa_ddc_destroy"
 
     def __init__(self, decimation: int, sample_rate: float, offset_hz: float = 0.0, taps=None, device: int = 0,
                  max_host_samples: int = 1 << 22):
@@ -95,24 +91,6 @@ class DownConverter:
         self.phase_step = 0
         self.offset_hz = 0.0
         self.set_offset(offset_hz)
-
-    # ------------------------------------------------------------------ lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            nat.lib.tdsa_ddc_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ------------------------------------------------------------------ configuration
     @property
@@ -171,7 +149,7 @@ def zoom_window(nfft: int) -> np.ndarray:
     return w
 
 
-class ZoomSpectrum:
+class ZoomSpectrum(nat._Handle):
     """Spectra of the band offset_hz +- fs / (2 D) at RBW fs / (D nfft).  Frame k is y[m0 + k hop : m0 + k hop + nfft]
     of the decimated stream; framing continues across calls, and decimated samples not yet framed stay on the device.
 
@@ -212,18 +190,6 @@ class ZoomSpectrum:
             self.ddc.close()
         if eng is not None:
             eng.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ------------------------------------------------------------------ axis
     @property
