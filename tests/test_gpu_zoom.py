@@ -174,15 +174,24 @@ def test_zoom_spectrum_chunking_rows_and_holds_are_bit_identical():
         assert np.array_equal(r, r0) and np.array_equal(mx, mx0) and np.array_equal(mn, mn0)
 
 
-@pytest.mark.parametrize("fmt", [zc.FMT_I8, zc.FMT_U8])
-def test_raw_input_equals_its_complex_unpacking(fmt):
-    D = 8
+def _raw_against_unpacked(D, fmt):
     rng = np.random.default_rng(fmt + 11)
     raw = _raw(rng, 30000, fmt)
     with DownConverter(D, FS, 0.17 * FS) as a, DownConverter(D, FS, 0.17 * FS) as b:
         ya = a.process(raw)
         yb = b.process(zc.unpack(raw, fmt))
     assert np.array_equal(ya.view(np.uint64), yb.view(np.uint64))
+
+
+@pytest.mark.parametrize("fmt", [zc.FMT_I8, zc.FMT_U8])
+def test_raw_input_equals_its_complex_unpacking(fmt):
+    _raw_against_unpacked(8, fmt)
+
+
+@pytest.mark.parametrize("D", [13, 24])
+@pytest.mark.parametrize("fmt", [zc.FMT_I8, zc.FMT_U8])
+def test_raw_input_equals_its_complex_unpacking_at_lanes_16_and_32(D, fmt):
+    _raw_against_unpacked(D, fmt)
 
 
 def _oracle_rows(y, N, hop, m0, fs_out):

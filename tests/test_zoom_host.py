@@ -68,6 +68,56 @@ def test_restatement_phase_track_is_continuous():
     assert p[40] == (40 * s1) % (1 << 32) and p[41] == (40 * s1 + s2) % (1 << 32)
 
 
+def test_integer_reference_checks_itself():
+    """zc.integer_fir (the exact reference of test_gpu_zoom_shapes.py) against np.convolve in int64."""
+    rng = np.random.default_rng(5)
+    for D, T in [(2, 1), (3, 7), (5, 11), (13, 3 * 13 + 1), (64, 130)]:
+        n = 3 * T + 9 * D + 4
+        re, im = rng.integers(-7, 8, (2, n))
+        h = rng.integers(-7, 8, T).astype(np.float32)
+        yr, yi = zc.integer_fir(re, im, h, D)
+        hi = h.astype(np.int64)
+        assert np.array_equal(yr, np.convolve(re, hi)[::D][:zc.n_outputs(n, D)])
+        assert np.array_equal(yi, np.convolve(im, hi)[::D][:zc.n_outputs(n, D)])
+    assert [zc.lanes(D) for D in (2, 3, 4, 5, 8, 9, 16, 17, 63, 64, 4096)] == [2, 4, 4, 8, 8, 16, 16, 32, 32, 64, 64]
+
+
+def _fmaf(a, b, c):
+    """fmaf of float32 arrays: the float64 product of two float32 values is exact, so this is one float64 addition
+    rounded to float32."""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def test_rotator_arithmetic_stays_within_one_ulp():
+    """ddc_mix's rotator (tdsa_ddc.hip) written out in numpy float32, operation by operation, for x = 1: every one of
+    the 4096 table entries against some 200 values of the low 20 phase bits, their extremes included.  DESIGN.md section 4.8
+    documents 1.5 ulp of |h|; the arithmetic itself stays within 1.0 x spacing(1) (0.50 measured), which pins the
+    documented margin without a GPU.  test_gpu_zoom_shapes.py measures the kernel."""
+    f32 = np.float32
+    rng = np.random.default_rng(20)
+    lows = np.unique(np.concatenate([[0, 1, 0x7FFFF, 0x80000, 0xFFFFE, 0xFFFFF], rng.integers(0, 1 << 20, 200)]))
+    assert lows.size >= 200
+    top = np.arange(4096)
+    th = 2.0 * np.pi * top / 4096.0
+    hx = np.cos(th).astype(f32)[:, None]                   # the table: (cos, -sin) rounded from float64
+    hy = (-np.sin(th)).astype(f32)[:, None]
+    low = np.broadcast_to(lows[None, :], (4096, lows.size))
+    t = low.astype(f32) * f32(1.46291807926715968e-9)      # 2 pi / 2^32
+    t2 = t * t
+    sl = _fmaf(t * t2, np.full_like(t, f32(0.16666667)), -t)
+    cm1 = t2 * f32(-0.5)
+    rr = hx + _fmaf(np.broadcast_to(hx, t.shape), cm1, -(hy * sl))
+    ri = hy + _fmaf(np.broadcast_to(hy, t.shape), cm1, hx * sl)
+    for a in (t, t2, sl, cm1, rr, ri):
+        assert a.dtype == f32
+    # x = 1 + 0j: (fma(1, rr, -(0 * ri)), fma(1, ri, 0 * rr)) = (rr, ri)
+    p = (top[:, None].astype(np.int64) << 20) + low
+    want = np.exp(-2j * np.pi * (p.astype(np.float64) / 2.0 ** 32))
+    err = np.maximum(np.abs(rr.astype(np.float64) - want.real), np.abs(ri.astype(np.float64) - want.imag))
+    worst = err.max() / float(np.spacing(f32(1)))
+    assert worst <= 1.0, (worst, hex(int(p.reshape(-1)[np.argmax(err)])))
+
+
 def test_offset_quantisation_and_wrapping():
     fs = 20e6
     step, actual = nco_step(1e6, fs)

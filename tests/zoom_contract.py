@@ -62,6 +62,28 @@ def by_convolution(v: np.ndarray, h: np.ndarray, D: int) -> np.ndarray:
     return np.convolve(v, np.asarray(h, dtype=np.float64))[::D][:n_outputs(len(v), D)]
 
 
+def lanes(D: int) -> int:
+    """Residue lanes of the FIR kernel the launcher picks for D (a workgroup owns 2048 / lanes outputs)."""
+    return 64 if D >= 64 else 32 if D > 16 else 16 if D > 8 else 8 if D > 4 else 4 if D > 2 else 2
+
+
+def integer_fir(re, im, h, D: int):
+    """y[m] = sum_k h[k] x[mD - k] of integer-valued x = re + j im and integer-valued taps, every output, in int64:
+    one dot product per output (as direct() does), so a long filter stays cheap.  Returns (real, imag) int64."""
+    hr = np.asarray(h).astype(np.int64)[::-1].copy()
+    assert np.array_equal(hr[::-1], np.asarray(h)), "taps must be integers"
+    T = hr.size
+    pr = np.concatenate([np.zeros(T - 1, np.int64), np.asarray(re, dtype=np.int64)])
+    pi = np.concatenate([np.zeros(T - 1, np.int64), np.asarray(im, dtype=np.int64)])
+    n_out = n_outputs(len(re), D)
+    yr = np.empty(n_out, np.int64)
+    yi = np.empty(n_out, np.int64)
+    for m in range(n_out):                      # window x[mD - T + 1 .. mD] against the reversed taps
+        yr[m] = hr @ pr[m * D:m * D + T]
+        yi[m] = hr @ pi[m * D:m * D + T]
+    return yr, yi
+
+
 def reference(raw, fmt: int, h, D: int, retunes, ms=None) -> np.ndarray:
     """y of a whole stream (ms = None) or of the chosen outputs, in float64."""
     x = unpack(raw, fmt)
