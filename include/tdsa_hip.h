@@ -399,6 +399,33 @@ int tdsa_ddc_process_dev(tdsa_ddc d, tdsa_plan p, int in_format, const void* iq_
  * stream afterwards.  ZoomSpectrum moves its unframed decimated samples and reads its rows with it. */
 int tdsa_plan_copy(tdsa_plan p, void* dst, const void* src, size_t bytes, int wait);
 
+/* -------- polyphase channelizer: every fs / M channel of a capture in one pass ------------
+ * M channels (a power of two, 4 .. 256), oversampling os = 1 or 2, decimation D = M / os, a prototype of T float32
+ * taps (1 <= T <= max_taps <= 40 M), x[n] the unpack of the down-converter above, counted from the last reset:
+ *   y_c[m] = sum_{k < T} h[k] x[mD - k] exp(-2 pi j c (mD - k) / M), c = 0 .. M - 1, complex64
+ * - the down-converter at phase step c 2^32 / M, decimation D and the same taps.  Channel c is centred at c fs / M for
+ * c < M / 2 and at (c - M) fs / M from there on.  Output m of every channel is emitted by the call that delivers input
+ * m D; any split of the input into calls gives the same bits.  Evaluated as branch sums w_m[r] = sum_q h[qM + r]
+ * x[mD - qM - r] (one fma chain over q), placed at p = (r - mD) mod M, and an unnormalised radix-2 inverse DFT over p.
+ * The outputs of a call are stored channel-major: y_c[m_first + i] at out + c * out_stride + i (complex64 units),
+ * i < n_out <= out_stride.  flags: TDSA_CHAN_BRANCHES stores the shifted branch sums W_m[p] at row p instead of y_c[m].
+ * _set_taps: finite taps, also resets the history.  _reset: history and input count to zero; returns when every earlier
+ * call of the handle has finished.  _process: one host block of n_in <= max_host_samples samples (one copy in, one
+ * copy back, one host wait).  _process_dev: input and output in device memory; on plan p's stream (ordered after its
+ * work, and its later work after this), or on the handle's own stream for p = NULL; no host wait.  Both set *n_out
+ * (per channel) from host-side counts.  Argument errors are reported before any HIP call. */
+#define TDSA_CHAN_BRANCHES 1u
+typedef struct tdsa_chan_s* tdsa_chan;
+int tdsa_chan_create(int device_id, int channels, int oversample, int max_taps, size_t max_host_samples,
+                     tdsa_chan* out);
+int tdsa_chan_destroy(tdsa_chan c);
+int tdsa_chan_set_taps(tdsa_chan c, const float* taps_host, int n_taps);
+int tdsa_chan_reset(tdsa_chan c);
+int tdsa_chan_process(tdsa_chan c, int in_format, const void* iq_host, size_t n_in, float* out_host,
+                      size_t out_stride, unsigned flags, size_t* n_out);
+int tdsa_chan_process_dev(tdsa_chan c, tdsa_plan p, int in_format, const void* iq_dev, size_t n_in, void* out_dev,
+                          size_t out_stride, unsigned flags, size_t* n_out);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

@@ -1,0 +1,96 @@
+"""tdsa_chan.hip cross-compiled for gfx950 (no GPU): every kernel of the channelizer is free of scratch and of spilled
+registers, its static LDS is what the launcher budgets for, and the dynamic LDS the launcher asks for stays within a
+CU's 160 KiB for every shape the library accepts."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+CSRC = os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+KERNELS = {"chan_bank_kernel": 2, "chan_history_kernel": 1}      # name -> instantiations (oversampling 1 and 2)
+
+
+def _const(name):
+    m = re.search(r"constexpr int %s = ([^;]+);" % name, open(os.path.join(CSRC, "tdsa_chan.hpp")).read())
+    return int(eval(m.group(1)))
+
+
+def _flags():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "$(B)/tdsa_chan.o" in mk and re.search(r"^CAPI\s*=.*\bchan\b", mk, re.M)
+    assert re.search(r"^HDRS\s*=.*\btdsa_chan\.hpp\b", mk, re.M)
+    extra = re.search(r"^EXTRA\s*\?=\s*(.*)$", mk, re.M).group(1).split()
+    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["--cuda-device-only"]
+
+
+@pytest.fixture(scope="module")
+def compiled(tmp_path_factory):
+    if not shutil.which(HIPCC):
+        pytest.skip("hipcc not available")
+    asm = str(tmp_path_factory.mktemp("chan") / "tdsa_chan.s")
+    r = subprocess.run(_flags() + ["-Rpass-analysis=kernel-resource-usage", "-S", "tdsa_chan.hip", "-o", asm],
+                       capture_output=True, text=True, cwd=CSRC)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stderr, open(asm).read()
+
+
+def test_chan_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(compiled):
+    remarks, _ = compiled
+    kernels, cur = {}, None
+    for ln in remarks.splitlines():
+        m = re.search(r"Function Name: (\S+)", ln)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = m.group(2)
+    assert sorted(k for k in kernels if "chan_" in k) == sorted(k for k in kernels), sorted(kernels)
+    for name, count in KERNELS.items():
+        found = [k for k in kernels if name in k]
+        assert len(found) == count, (name, sorted(kernels))
+        for k in found:
+            print(k, kernels[k])
+            assert kernels[k]["ScratchSize [bytes/lane]"] == "0", (k, kernels[k])
+            assert kernels[k].get("VGPRs Spill", "0") == "0", (k, kernels[k])
+            assert kernels[k].get("SGPRs Spill", "0") == "0", (k, kernels[k])
+            assert int(kernels[k]["LDS Size [bytes/block]"]) <= _const("kChanStaticLdsBytes"), (k, kernels[k])
+            assert int(kernels[k]["VGPRs"]) <= 128, (k, kernels[k])      # 256 threads: four workgroups fit a CU's registers
+
+
+def test_chan_fir_is_packed_and_nothing_goes_through_scratch(compiled):
+    _, asm = compiled
+    body = "\n".join(ln for ln in asm.splitlines() if not ln.lstrip().startswith((";", "//", ".")))
+    assert "v_pk_fma_f32" in body                      # the branch FIR over (re, im)
+    assert "ds_read_b64" in body or "ds_read2_b64" in body or "ds_read_b128" in body
+    assert "scratch_" not in body
+
+
+def _lds_samples(M, os_, P):
+    """chan_lds_samples of tdsa_chan.hpp."""
+    D, F, blk = M // os_, _const("kChanTilePoints") // M, _const("kChanBlock")
+    staged = (F + P * os_ - 1) * D
+    padded = staged + staged // (blk * D) * (M if M < 64 else 0)
+    return max(padded, F * (M + (M // 64 if M > 64 else 1)))
+
+
+def test_dynamic_lds_fits_a_cu_for_every_accepted_shape():
+    hpp = open(os.path.join(CSRC, "tdsa_chan.hpp")).read()
+    assert "(F + P * os - 1) * D" in hpp and "chan_stage_pad(int M) { return M < 64 ? M : 0; }" in hpp
+    assert "chan_row(int M) { return M + (M > 64 ? M / 64 : 1); }" in hpp
+    limit, static, worst = _const("kChanMaxLdsBytes"), _const("kChanStaticLdsBytes"), 0
+    assert limit == 160 * 1024
+    M = _const("kChanMinChannels")
+    while M <= _const("kChanMaxChannels"):
+        for os_ in (1, 2):
+            for P in range(1, _const("kChanMaxTapsPerBranch") + 1):
+                worst = max(worst, 8 * _lds_samples(M, os_, P) + static)
+        M *= 2
+    print("worst LDS per workgroup", worst)
+    assert worst <= limit
+    # at 32 taps per branch two workgroups share a CU even at 256 channels
+    assert 2 * (8 * _lds_samples(256, 1, 32) + static) <= limit

@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""Timing of the polyphase channelizer on one C3 second: 20e6 int8 IQ samples resident in HBM,
+the default prototype (zoom.design_decimator(M), 34 taps per branch).
+
+  copy     the box's device-to-device copy rate (1 GiB, torch), which the memory floor is stated against
+  bank     M in {8, 64, 256} x os in {1, 2}: one Channelizer.process_device call over the whole second, next to its
+           memory floor (2 bytes in and 8 os bytes out per input sample at the copy rate) and next to M passes of
+           zoom.DownConverter at the same decimation, one per channel, measured in the same process.  The down-converter
+           takes at most 64 D taps, so at os = 2 its passes run 32 taps per branch (64 per phase of D) and the line says so
+  spectra  ChannelSpectra end to end at M = 64, os = 2, nfft = 1024: the bank and all 64 x 610 frames in one launch
+  diff     the largest |difference| between channel 5 and the DownConverter tuned to 5 fs / M, on the same block
+
+Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per figure: warm-up
+calls, then the median of `--reps` (at least 20) single calls, each between device events on the engine's stream the
+work is launched on.
+
+    python tools/chanbench.py [--out profiles/chanbench.txt] [--reps 20]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+FS = 20e6
+N_SEC = 20_000_000
+SHAPES = [(M, os_) for M in (8, 64, 256) for os_ in (1, 2)]
+STEPS = ["copy"] + [f"bank_{M}_{os_}" for M, os_ in SHAPES] + ["spectra", "diff"]
+LIMIT_S = 240
+
+
+def median_us(eng, f, warm, reps):
+    for _ in range(warm):
+        f()
+    t = []
+    for _ in range(reps):
+        eng.timer_begin()
+        f()
+        t.append(eng.timer_end() * 1e3)
+    return float(np.median(t)), float(np.min(t)), float(np.max(t))
+
+
+def capture(nat, n):
+    rng = np.random.default_rng(4)
+    iq = rng.integers(-128, 128, 2 * n).astype(np.int8)
+    d = nat._dev_alloc(0, iq.nbytes)
+    nat.check(nat.lib.tdsa_memcpy_h2d(0, d, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
+    return iq, d
+
+
+def step_copy(args):
+    import torch
+    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    y = torch.empty_like(x)
+    x.fill_(1.0)
+    for _ in range(3):
+        y.copy_(x)
+    t = []
+    for _ in range(args.reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        y.copy_(x)
+        b.record()
+        b.synchronize()
+        t.append(a.elapsed_time(b) * 1e-3)
+    moved = 2 * x.numel() * 4
+    return dict(copy_bps=moved / float(np.median(t)), text=[
+        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
+
+
+def step_bank(args, M, os_):
+    from topdogspectrumanalyser_amd import Channelizer, DownConverter, SpectrumEngine, _native as nat
+    from topdogspectrumanalyser_amd.zoom import design_decimator
+    D = M // os_
+    n = N_SEC // D * D
+    n_out = n // D
+    _, d_in = capture(nat, n)
+    d_out = nat._dev_alloc(0, 8 * M * n_out)
+    with SpectrumEngine(64) as eng, Channelizer(M, FS, os_) as bank:
+        us, lo, hi = median_us(eng, lambda: bank.process_device(eng, nat.IN_I8, d_in.value, n, d_out.value, n_out),
+                               args.warm, args.reps)
+        floor = n * (2 + 8 * os_) / args.copy_bps * 1e6
+        taps = bank.taps if bank.taps.size <= 64 * D else design_decimator(M, 32)
+        with DownConverter(D, FS, 0.0, taps=taps) as ddc:
+            def passes():
+                for c in range(M):
+                    nat.check(nat.lib.tdsa_ddc_set_nco(ddc._h, (c << 32) // M))
+                    ddc.process_device(eng, nat.IN_I8, d_in.value, n, d_out.value + 8 * c * n_out)
+            us_d = median_us(eng, passes, 1, args.reps)
+    for p in (d_in, d_out):
+        nat.lib.tdsa_dev_free(0, p)
+    return dict(text=[
+        f"bank M={M:3d} os={os_}: {n} samples, {bank.taps.size // M} taps per branch: {us:9.1f} us (min {lo:.1f}, max {hi:.1f}); "
+        f"memory floor {floor:8.1f} us ({2 + 8 * os_} bytes per sample at the copy rate) = {100 * floor / us:5.1f}% of the time; "
+        f"{M} DownConverter passes at D={D}, {taps.size // M} taps per branch: {us_d[0]:10.1f} us "
+        f"({us_d[0] / M:7.1f} us per pass) = {us_d[0] / us:6.1f} x the bank"])
+
+
+def step_spectra(args):
+    from topdogspectrumanalyser_amd import ChannelSpectra, _native as nat
+    M, os_, nfft = 64, 2, 1024
+    F = N_SEC // (M // os_ * nfft)
+    n = F * (M // os_) * nfft
+    _, d_in = capture(nat, n)
+    d_rows = nat._dev_alloc(0, 4 * M * F * nfft)
+    with ChannelSpectra(FS, M, nfft, oversample=os_, max_frames=F) as cs:
+        us, lo, hi = median_us(cs.engine, lambda: cs.process_device(nat.IN_I8, d_in.value, n, d_rows.value),
+                               args.warm, args.reps)
+        rbw = cs.rbw
+    for p in (d_in, d_rows):
+        nat.lib.tdsa_dev_free(0, p)
+    return dict(text=[
+        f"spectra M={M} os={os_} nfft={nfft}: {n} samples -> {M} x {F} frames ({M * F} in one frame-kernel launch), dB rows "
+        f"in HBM, RBW {rbw:.1f} Hz: {us:9.1f} us (min {lo:.1f}, max {hi:.1f})"])
+
+
+def step_diff(args):
+    from topdogspectrumanalyser_amd import Channelizer, DownConverter
+    M, c, n = 64, 5, 1 << 20
+    rng = np.random.default_rng(5)
+    iq = rng.integers(-128, 128, 2 * n).astype(np.int8)
+    with Channelizer(M, FS, 1) as bank, DownConverter(M, FS, c * FS / M, taps=bank.taps) as ddc:
+        assert ddc.phase_step == (c << 32) // M
+        y = bank.process(iq)[c]
+        z = ddc.process(iq)
+    scale = float(np.abs(z).max())
+    return dict(text=[
+        f"diff M={M} os=1: channel {c} against the DownConverter tuned to {c} fs / M over {n} samples ({y.size} outputs): "
+        f"largest |difference| {float(np.abs(y - z).max()):.3e}, largest |output| {scale:.3e}"])
+
+
+def run_step(args):
+    if args.step == "copy":
+        return step_copy(args)
+    if args.step == "spectra":
+        return step_spectra(args)
+    if args.step == "diff":
+        return step_diff(args)
+    _, M, os_ = args.step.split("_")
+    return step_bank(args, int(M), int(os_))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warm", type=int, default=3)
+    ap.add_argument("--step", choices=STEPS, default=None)
+    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
+    args = ap.parse_args()
+    args.reps = max(args.reps, 20)
+    if args.step:
+        print("RESULT " + json.dumps(run_step(args)), flush=True)
+        return
+    lines = [f"polyphase channelizer on one C3 second ({N_SEC} int8 IQ samples in HBM, default prototype); every figure is "
+             f"the median of {args.reps} single calls after warm-up calls, between device events on the stream the work runs on"]
+    print(lines[0], flush=True)
+    copy_bps = 0.0
+    for step in STEPS:
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
+               "--copy-bps", repr(copy_bps)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
+        except subprocess.TimeoutExpired:
+            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
+            print(lines[-1], flush=True)
+            break
+        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+        if r.returncode != 0 or not res:
+            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
+            print(lines[-1], flush=True)
+            break
+        res = json.loads(res[-1][7:])
+        copy_bps = res.get("copy_bps", copy_bps)
+        for ln in res["text"]:
+            print(ln, flush=True)
+            lines.append(ln)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -20,6 +20,7 @@ HOLD_MAX, HOLD_MIN = 1, 2
 CH_MONO, CH_LEFT, CH_RIGHT, CH_STEREO = 0, 1, 2, 3
 SWEEP_DET_SAMPLE, SWEEP_DET_MAX, SWEEP_DET_MIN, SWEEP_DET_AVG = 0, 1, 2, 3
 SWEEP_INTERP, SWEEP_PEAK = 0, 1
+CHAN_BRANCHES = 1
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
 ZS_FREE_RUN, ZS_RISE, ZS_FALL = 0, 1, 2
 ZS_COL_MINMAX, ZS_COL_SAMPLE, ZS_COL_MEAN = 0, 1, 2
@@ -127,6 +128,13 @@ _SIGNATURES = {
     "tdsa_ddc_reset": (C.c_int, [_P]),
     "tdsa_ddc_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
     "tdsa_ddc_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
+    "tdsa_chan_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_chan_destroy": (C.c_int, [_P]),
+    "tdsa_chan_set_taps": (C.c_int, [_P, _P, C.c_int]),
+    "tdsa_chan_reset": (C.c_int, [_P]),
+    "tdsa_chan_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_uint, C.POINTER(C.c_size_t)]),
+    "tdsa_chan_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_uint,
+                                        C.POINTER(C.c_size_t)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),
