@@ -426,6 +426,45 @@ int tdsa_chan_process(tdsa_chan c, int in_format, const void* iq_host, size_t n_
 int tdsa_chan_process_dev(tdsa_chan c, tdsa_plan p, int in_format, const void* iq_dev, size_t n_in, void* out_dev,
                           size_t out_stride, unsigned flags, size_t* n_out);
 
+/* -------- analog demodulation: AM / FM audio, deviation, depth ----------------------------
+ * C channels (1 .. 256) of complex64, channel c's samples of a call at in + c * in_stride (complex64 units), counted
+ * from the last reset across calls, x[-1] = 0.  Per channel:
+ *   d[n] = arg(x[n] conj x[n-1]) / pi in (-1, 1] (TDSA_DEMOD_FM; one unit is f_i / 2 Hz; 0 where the product is 0, +1
+ *          where it is negative real) or |x[n]| (TDSA_DEMOD_AM)
+ *   a[m] = sum_{k < T} g[k] d[mR - k], d = 0 before sample 0; decimation R = 1 .. 64, T float32 taps, 1 <= T <= 64 R
+ *   y[m] = c y[m-1] + (1 - c) a[m], y[-1] = 0, 0 <= c < 1
+ *   out[m] = s a[m] (TDSA_DEMOD_POLE_OFF), s y[m] (_LOWPASS: de-emphasis) or s (a[m] - y[m]) (_HIGHPASS: carrier removal)
+ * Output m comes out of the call that delivers input mR; any split of the input into calls gives the same bits.  The
+ * outputs of a call are contiguous float32 at out + c * out_stride (float32 units), n_out <= out_stride per channel.
+ * Measurements per channel over a[m] since _reset_meas: count, max, min (exact), sum and sum of squares (float64).
+ * _set_taps and _set_pole also reset the handle; _reset zeroes the history, the pole state, the sample count and the
+ * measurements and returns when every earlier call has finished.  _process: host memory through pinned staging (one
+ * copy in, one copy out, one host wait), at most max_host_samples / channels samples per channel and call.
+ * _process_dev: device memory, on plan p's stream (ordered after its work, and its later work after this) or on the
+ * handle's own for p = NULL; no host wait.  _read_meas: five arrays of `channels` entries.  Argument errors are reported
+ * before any HIP call. */
+#define TDSA_DEMOD_FM 0
+#define TDSA_DEMOD_AM 1
+#define TDSA_DEMOD_POLE_OFF 0
+#define TDSA_DEMOD_POLE_LOWPASS 1
+#define TDSA_DEMOD_POLE_HIGHPASS 2
+typedef struct tdsa_demod_s* tdsa_demod;
+int tdsa_demod_create(int device_id, int mode, int channels, int decimation, int max_taps, size_t max_host_samples,
+                      tdsa_demod* out);
+int tdsa_demod_destroy(tdsa_demod d);
+int tdsa_demod_set_taps(tdsa_demod d, const float* taps_host, int n_taps);
+int tdsa_demod_set_pole(tdsa_demod d, int pole_mode, double c, float scale);
+int tdsa_demod_reset(tdsa_demod d);
+int tdsa_demod_process(tdsa_demod d, const void* in_host, size_t n_in, size_t in_stride, float* out_host,
+                       size_t out_stride, size_t* n_out);
+int tdsa_demod_process_dev(tdsa_demod d, tdsa_plan p, const void* in_dev, size_t n_in, size_t in_stride, void* out_dev,
+                           size_t out_stride, size_t* n_out);
+int tdsa_demod_read_meas(tdsa_demod d, int64_t* count, float* max_f32, float* min_f32, double* sum_f64,
+                         double* sumsq_f64);
+int tdsa_demod_reset_meas(tdsa_demod d);
+int tdsa_demod_timer_begin(tdsa_demod d);
+int tdsa_demod_timer_end(tdsa_demod d, float* elapsed_ms);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

@@ -1,0 +1,88 @@
+"""tdsa_demod.hip cross-compiled for gfx950 (no GPU), read through the compiler's resource remarks only: the expected
+kernel instantiations exist, none uses scratch or spills a register, VGPRs stay within 128, the static LDS is what the
+header budgets for, and the dynamic LDS the launcher asks for stays within a CU's 160 KiB for every (R, T) the library
+accepts."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+CSRC = os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+KERNELS = {"demod_audio_kernel": 2, "demod_history_kernel": 2, "demod_post_kernel": 1}     # name -> instantiations (FM, AM)
+
+
+def _const(name):
+    m = re.search(r"constexpr int %s = ([^;]+);" % name, open(os.path.join(CSRC, "tdsa_demod.hpp")).read())
+    return int(eval(m.group(1)))
+
+
+def _flags():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "$(B)/tdsa_demod.o" in mk and re.search(r"^CAPI\s*=.*\bdemod\b", mk, re.M)
+    assert re.search(r"^HDRS\s*=.*\btdsa_demod\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_demod_math\.hpp\b", mk, re.M)
+    extra = re.search(r"^EXTRA\s*\?=\s*(.*)$", mk, re.M).group(1).split()
+    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["--cuda-device-only"]
+
+
+@pytest.fixture(scope="module")
+def remarks(tmp_path_factory):
+    if not shutil.which(HIPCC):
+        pytest.skip("hipcc not available")
+    out = str(tmp_path_factory.mktemp("demod") / "tdsa_demod.o")
+    r = subprocess.run(_flags() + ["-Rpass-analysis=kernel-resource-usage", "-c", "tdsa_demod.hip", "-o", out],
+                       capture_output=True, text=True, cwd=CSRC)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stderr
+
+
+def test_demod_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(remarks):
+    kernels, cur = {}, None
+    for ln in remarks.splitlines():
+        m = re.search(r"Function Name: (\S+)", ln)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = m.group(2)
+    assert sorted(k for k in kernels if "demod_" in k) == sorted(k for k in kernels), sorted(kernels)
+    for name, count in KERNELS.items():
+        found = [k for k in kernels if name in k]
+        assert len(found) == count, (name, sorted(kernels))
+        for k in found:
+            print(k, kernels[k])
+            assert kernels[k]["ScratchSize [bytes/lane]"] == "0", (k, kernels[k])
+            assert kernels[k].get("VGPRs Spill", "0") == "0", (k, kernels[k])
+            assert kernels[k].get("SGPRs Spill", "0") == "0", (k, kernels[k])
+            assert int(kernels[k]["LDS Size [bytes/block]"]) <= _const("kDemodStaticLdsBytes"), (k, kernels[k])
+            assert int(kernels[k]["VGPRs"]) <= 128, (k, kernels[k])      # 256 threads: four workgroups fit a CU's registers
+
+
+def _lds_floats(R, Q):
+    """demod_lds_floats of tdsa_demod.hpp."""
+    blk, tile = _const("kDemodBlock"), _const("kDemodTile")
+    last = tile + Q - 2
+    rows = (last + last // blk + 1) | 1
+    return -(-R // blk) * rows * blk
+
+
+def test_dynamic_lds_fits_a_cu_for_every_accepted_shape():
+    hpp = open(os.path.join(CSRC, "tdsa_demod.hpp")).read()
+    assert "demod_prow(int j) { return j + j / kDemodBlock; }" in hpp
+    assert "demod_stage_rows(int Q) { return (demod_prow(kDemodTile + Q - 2) + 1) | 1; }" in hpp
+    assert "return (R + kDemodBlock - 1) / kDemodBlock * demod_stage_rows(Q) * kDemodBlock;" in hpp
+    assert (_const("kDemodMaxChannels"), _const("kDemodMaxDecimation"), _const("kDemodMaxTapsPerPhase")) == (256, 64, 64)
+    assert _const("kDemodTile") % (256 // _const("kDemodBlock") * _const("kDemodBlock")) == 0 and _const("kDemodPoleBlock") == 64
+    limit, worst = _const("kDemodMaxLdsBytes"), 0
+    assert limit == 160 * 1024
+    for R in range(1, _const("kDemodMaxDecimation") + 1):
+        for Q in range(1, _const("kDemodMaxTapsPerPhase") + 1):      # every T with ceil(T / R) = Q
+            worst = max(worst, 4 * _lds_floats(R, Q))
+    print("worst dynamic LDS per workgroup", worst)
+    assert worst + _const("kDemodStaticLdsBytes") <= limit
+    # the default filter (34 phases) at the bench's R = 6 leaves room for eight workgroups per CU
+    assert 8 * 4 * _lds_floats(6, 34) <= limit

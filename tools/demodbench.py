@@ -1,0 +1,211 @@
+#!/usr/bin/env python3
+"""Timing of the analog demodulator on one C3 second: 20e6 int8 IQ samples through
+Channelizer(128, os=2), which leaves 128 channels of 312 500 complex64 samples (312.5 kHz) in HBM; then FM at R = 6 with
+the default audio filter (34 taps per phase) and 75 us de-emphasis, and AM at the same shape with carrier removal.
+
+  copy     the box's device-to-device copy rate (1 GiB, torch), which the memory floor is stated against
+  fm, am   one Demodulator.process_device call over all 128 channels of the second, next to its memory floor: 8 bytes in
+           and 4 / R bytes out per channel sample at the copy rate
+  split    the FM step again under `rocprofv3 --kernel-trace --stats`: the audio, post and history kernels separately
+  numpy    for scale: the same three stages in float32 numpy on one host core, on 8 of the 128 channels, times 16
+
+Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per figure: warm-up
+calls, then the median of `--reps` (at least 20) single calls, each between device events on the engine's stream the
+work is launched on.
+
+    python tools/demodbench.py [--out profiles/demodbench.txt] [--reps 20]
+"""
+import argparse
+import csv
+import ctypes as C
+import glob
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+FS = 20e6
+N_SEC = 20_000_000
+M, OS, R = 128, 2, 6
+TAU = 75e-6
+STEPS = ["copy", "fm", "am", "split", "numpy"]
+LIMIT_S = 240
+
+
+def median_us(eng, f, warm, reps):
+    for _ in range(warm):
+        f()
+    t = []
+    for _ in range(reps):
+        eng.timer_begin()
+        f()
+        t.append(eng.timer_end() * 1e3)
+    return float(np.median(t)), float(np.min(t)), float(np.max(t))
+
+
+def capture(n):
+    """Noise: an FM carrier per channel would cost minutes of host time, and the kernels' work does not depend on the data."""
+    rng = np.random.default_rng(4)
+    return rng.integers(-128, 128, 2 * n).astype(np.int8)
+
+
+def step_copy(args):
+    import torch
+    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    y = torch.empty_like(x)
+    x.fill_(1.0)
+    for _ in range(3):
+        y.copy_(x)
+    t = []
+    for _ in range(args.reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        y.copy_(x)
+        b.record()
+        b.synchronize()
+        t.append(a.elapsed_time(b) * 1e-3)
+    moved = 2 * x.numel() * 4
+    return dict(copy_bps=moved / float(np.median(t)), text=[
+        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
+
+
+def step_demod(args, mode):
+    from topdogspectrumanalyser_amd import Channelizer, Demodulator, SpectrumEngine, _native as nat
+    D = M // OS
+    n = N_SEC // D * D
+    ny = n // D
+    iq = capture(n)
+    d_in = nat._dev_alloc(0, iq.nbytes)
+    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
+    d_y = nat._dev_alloc(0, 8 * M * ny)
+    kw = dict(deemphasis=TAU) if mode == "fm" else dict(remove_carrier=True)
+    with SpectrumEngine(64) as eng, Channelizer(M, FS, OS) as bank, \
+            Demodulator(mode, FS / D, R, M, max_host_samples=M, **kw) as dm:
+        bank.process_device(eng, nat.IN_I8, d_in.value, n, d_y.value, ny)
+        na = ny // R                             # a whole number of outputs per call: every call does the same work
+        d_a = nat._dev_alloc(0, 4 * M * na)
+
+        def call():
+            dm.process_device(eng, d_y.value, na * R, ny, d_a.value, na)
+
+        us, lo, hi = median_us(eng, call, args.warm, args.reps)
+        eng.synchronize()
+        taps = dm.taps.size
+    ny = na * R
+    floor = M * ny * (8 + 4.0 / R) / args.copy_bps * 1e6 if args.copy_bps else float("nan")
+    for p in (d_in, d_y, d_a):
+        nat.lib.tdsa_dev_free(0, p)
+    return dict(text=[
+        f"{mode} R={R}: {M} channels x {ny} samples at {FS / D / 1e3:.1f} kHz, {taps // R} taps per phase, one-pole section on: "
+        f"{us:9.1f} us (min {lo:.1f}, max {hi:.1f}); memory floor {floor:8.1f} us (8 bytes in, 4 / {R} out per channel sample at "
+        f"the copy rate) = {100 * floor / us:5.1f}% of the time"])
+
+
+def step_split(args):
+    prof = shutil.which("rocprofv3")
+    if not prof:
+        return dict(text=["split: rocprofv3 not found; the kernels were not timed separately"])
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
+               os.path.abspath(__file__), "--step", "fm", "--reps", str(args.reps), "--warm", str(args.warm)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        rows = []
+        for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
+            with open(path, newline="") as f:
+                rows += [row for row in csv.DictReader(f) if "demod_" in row.get("Name", "")]
+        if r.returncode != 0 or not rows:
+            return dict(text=[f"split: no kernel statistics (exit status {r.returncode}); the kernels were not timed separately"])
+    text = []
+    for row in sorted(rows, key=lambda q: q["Name"].split("demod_")[-1]):
+        name = re.search(r"demod_\w+(<\d+>)?", row["Name"]).group(0)
+        text.append(f"split fm R={R}: {name}: {int(row['Calls'])} calls, average {float(row['AverageNs']) / 1e3:9.1f} us "
+                    f"(min {float(row['MinNs']) / 1e3:.1f}, max {float(row['MaxNs']) / 1e3:.1f}), under the profiler")
+    return dict(text=text)
+
+
+def step_numpy(args):
+    from topdogspectrumanalyser_amd.demod import deemphasis_pole, design_audio_filter
+    D, part = M // OS, 8
+    ny = N_SEC // D
+    rng = np.random.default_rng(5)
+    y = (rng.standard_normal((part, ny)) + 1j * rng.standard_normal((part, ny))).astype(np.complex64)
+    g = design_audio_filter(R)
+    c = np.float32(deemphasis_pole(TAU, FS / D / R))
+    t0 = time.perf_counter()
+    for row in y:
+        p = row[1:] * np.conj(row[:-1])
+        d = np.arctan2(p.imag, p.real) * np.float32(1 / np.pi)
+        a = np.convolve(d, g)[:d.size:R].astype(np.float32)
+        out = np.empty_like(a)
+        acc = np.float32(0)
+        for m in range(a.size):                  # the recursion, as a host program would write it without scipy
+            acc = c * acc + (np.float32(1) - c) * a[m]
+            out[m] = acc
+    dt = time.perf_counter() - t0
+    return dict(text=[f"numpy fm R={R}: {part} of the {M} channels on one host core {dt:.2f} s; times {M // part} = "
+                      f"{dt * M / part:.1f} s for the second"])
+
+
+def run_step(args):
+    if args.step == "copy":
+        return step_copy(args)
+    if args.step == "split":
+        return step_split(args)
+    if args.step == "numpy":
+        return step_numpy(args)
+    return step_demod(args, args.step)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warm", type=int, default=3)
+    ap.add_argument("--step", choices=STEPS, default=None)
+    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
+    args = ap.parse_args()
+    args.reps = max(args.reps, 20)
+    if args.step:
+        print("RESULT " + json.dumps(run_step(args)), flush=True)
+        return
+    lines = [f"analog demodulator on one C3 second through Channelizer({M}, os={OS}): {M} channels at {FS * OS / M / 1e3:.1f} kHz "
+             f"in HBM; every device figure is the median of {args.reps} single calls after warm-up calls, between device events on "
+             f"the stream the work runs on"]
+    print(lines[0], flush=True)
+    copy_bps = 0.0
+    for step in STEPS:
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
+               "--copy-bps", repr(copy_bps)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
+        except subprocess.TimeoutExpired:
+            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
+            print(lines[-1], flush=True)
+            break
+        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+        if r.returncode != 0 or not res:
+            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
+            print(lines[-1], flush=True)
+            break
+        res = json.loads(res[-1][7:])
+        copy_bps = res.get("copy_bps", copy_bps)
+        for ln in res["text"]:
+            print(ln, flush=True)
+            lines.append(ln)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -13,6 +13,7 @@ from .core.tare_state import TareState  # noqa: F401
 from .analytics import Constellation, ConstellationView  # noqa: F401
 from .zoom import DownConverter, ZoomSpectrum, design_decimator  # noqa: F401
 from .channelizer import Channelizer, ChannelSpectra  # noqa: F401
+from .demod import Demodulator, deemphasis_pole, design_audio_filter  # noqa: F401
 from .zerospan import ZeroSpan, view_plan  # noqa: F401
 from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401
@@ -21,4 +22,5 @@ __all__ = ["SpectrumEngine", "HostPipe", "TraceState", "TraceAverager", "SampleD
            "HackrfSamplesDataSource", "RtlSamplesDataSource", "MicrophoneSamplesDataSource",
            "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView",
            "DownConverter", "ZoomSpectrum", "design_decimator", "ZeroSpan", "view_plan", "IqSweepDataSource", "SweepAssembler", "plan_steps",
-           "TraceHistory", "RibbonView", "ThreeDView", "SurfaceView", "Channelizer", "ChannelSpectra"]
+           "TraceHistory", "RibbonView", "ThreeDView", "SurfaceView", "Channelizer", "ChannelSpectra",
+           "Demodulator", "design_audio_filter", "deemphasis_pole"]

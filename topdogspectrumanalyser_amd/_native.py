@@ -21,6 +21,8 @@ CH_MONO, CH_LEFT, CH_RIGHT, CH_STEREO = 0, 1, 2, 3
 SWEEP_DET_SAMPLE, SWEEP_DET_MAX, SWEEP_DET_MIN, SWEEP_DET_AVG = 0, 1, 2, 3
 SWEEP_INTERP, SWEEP_PEAK = 0, 1
 CHAN_BRANCHES = 1
+DEMOD_FM, DEMOD_AM = 0, 1
+DEMOD_POLE_OFF, DEMOD_POLE_LOWPASS, DEMOD_POLE_HIGHPASS = 0, 1, 2
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
 ZS_FREE_RUN, ZS_RISE, ZS_FALL = 0, 1, 2
 ZS_COL_MINMAX, ZS_COL_SAMPLE, ZS_COL_MEAN = 0, 1, 2
@@ -135,6 +137,17 @@ _SIGNATURES = {
     "tdsa_chan_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_uint, C.POINTER(C.c_size_t)]),
     "tdsa_chan_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_uint,
                                         C.POINTER(C.c_size_t)]),
+    "tdsa_demod_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_demod_destroy": (C.c_int, [_P]),
+    "tdsa_demod_set_taps": (C.c_int, [_P, _P, C.c_int]),
+    "tdsa_demod_set_pole": (C.c_int, [_P, C.c_int, C.c_double, C.c_float]),
+    "tdsa_demod_reset": (C.c_int, [_P]),
+    "tdsa_demod_process": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tdsa_demod_process_dev": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tdsa_demod_read_meas": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "tdsa_demod_reset_meas": (C.c_int, [_P]),
+    "tdsa_demod_timer_begin": (C.c_int, [_P]),
+    "tdsa_demod_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),
