@@ -1,5 +1,5 @@
 """A handle's launches are totally ordered whichever stream each goes on (the ordering rule of Lane in
-csrc/tdsa_capi_internal.hpp).  Each of the four handle types that can launch on a producer plan's stream is fed the same
+csrc/tdsa_capi_internal.hpp).  Each of the six handle types that can launch on a producer plan's stream is fed the same
 input in six pieces, hopping engine A's stream -> its own -> engine B's stream -> ..., and has to return exactly what a
 second handle returns that was fed the same pieces on its own stream throughout.  Every piece depends on the state the
 piece before it left (filter history, ring position, hold row, a step written twice), so a launch that overtakes its
@@ -10,8 +10,8 @@ import math
 import numpy as np
 import pytest
 
-from topdogspectrumanalyser_amd import (DownConverter, SpectrumEngine, SweepAssembler, TraceHistory, ZeroSpan,
-                                        _native as nat)
+from topdogspectrumanalyser_amd import (Channelizer, Demodulator, DownConverter, SpectrumEngine, SweepAssembler,
+                                        TraceHistory, ZeroSpan, _native as nat)
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +84,55 @@ def test_down_converter_hopping_streams(engines):
     n1, y1 = _ddc_run(SINGLE)
     assert n == n1 == 10 * PIECES // 3
     assert _same(y, y1)
+
+
+# ---- channelizer: M = 4, oversample 2 (D = 2), 9 taps (3 per branch), pieces of 7 complex64 samples -------------------
+def _chan_run(streams):
+    rng = np.random.default_rng(15)
+    x = (rng.normal(size=7 * PIECES) + 1j * rng.normal(size=7 * PIECES)).astype(np.complex64)
+    taps = np.array([0.02, 0.06, 0.12, 0.19, 0.22, 0.19, 0.12, 0.06, 0.02], dtype=np.float32)
+    total = 7 * PIECES // 2                                    # 21 outputs per channel: the row stride
+    with Channelizer(4, 48000.0, oversample=2, taps=taps, max_host_samples=64) as bank, _Dev(x) as d_in, \
+            _Dev(nbytes=8 * 4 * total) as d_out:
+        counts = []
+        for i, eng in enumerate(streams):
+            counts.append(bank.process_device(eng, nat.IN_C64, d_in.p.value + 8 * 7 * i, 7,
+                                              d_out.p.value + 8 * sum(counts), total))
+        bank.reset()             # waits on the handle's own stream, which it first puts behind the last launch
+        return counts, d_out.get(4 * total, np.complex64).view(np.uint64)
+
+
+def test_channelizer_hopping_streams(engines):
+    n, y = _chan_run(_hopping(engines))
+    n1, y1 = _chan_run(SINGLE)
+    assert n == n1 == [4, 3] * (PIECES // 2)
+    assert _same(y, y1)
+
+
+# ---- demodulator: FM, 2 channels, R = 3, 7 taps, low-pass pole c = 0.5, pieces of 10 samples per channel --------------
+def _demod_run(streams):
+    rng = np.random.default_rng(16)
+    x = (rng.normal(size=(2, 10 * PIECES)) + 1j * rng.normal(size=(2, 10 * PIECES))).astype(np.complex64)
+    taps = np.array([0.05, 0.12, 0.2, 0.26, 0.2, 0.12, 0.05], dtype=np.float32)
+    total = 10 * PIECES // 3                                   # 20 outputs per channel: the row stride
+    with Demodulator("fm", 48000.0, decimation=3, channels=2, taps=taps, max_host_samples=64) as dem, _Dev(x) as d_in, \
+            _Dev(nbytes=4 * 2 * total) as d_out:
+        dem.set_pole(nat.DEMOD_POLE_LOWPASS, 0.5)              # its block of 64 outputs is never completed
+        counts = []
+        for i, eng in enumerate(streams):
+            counts.append(dem.process_device(eng, d_in.p.value + 8 * 10 * i, 10, 10 * PIECES,
+                                             d_out.p.value + 4 * sum(counts), total))
+        m = dem.measure()        # waits on the handle's own stream, which it first puts behind the last launch
+        return counts, d_out.get(2 * total, np.float32).view(np.uint32), (m.count, m.max, m.min, m.sum, m.sumsq)
+
+
+def test_demodulator_hopping_streams(engines):
+    n, y, m = _demod_run(_hopping(engines))
+    n1, y1, m1 = _demod_run(SINGLE)
+    assert n == n1 == [4, 3, 3] * (PIECES // 3)
+    assert list(m[0]) == [10 * PIECES // 3] * 2
+    assert _same(y, y1)
+    assert _same(m, m1)
 
 
 # ---- sweep assembler: 4 steps of nfft 64, one step per piece (steps 0 and 1 are written twice) -----------------------

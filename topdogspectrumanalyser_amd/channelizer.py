@@ -26,7 +26,7 @@ from ._native import _dev_alloc
 from .analytics import _iq_input
 from .engine import SpectrumEngine
 from .utils.constants import DSPConstants
-from .zoom import design_decimator, zoom_window
+from .zoom import as_taps, check_same_device, design_decimator, outputs_completed, zoom_window
 
 MIN_CHANNELS, MAX_CHANNELS = 4, 256
 MAX_TAPS_PER_BRANCH = 40
@@ -43,24 +43,12 @@ def check_parameters(channels: int, oversample: int, n_taps: int) -> None:
         raise ValueError(f"{n_taps} taps: 1 .. {MAX_TAPS_PER_BRANCH * M} ({MAX_TAPS_PER_BRANCH} per branch at {M} channels)")
 
 
-def outputs_completed(n_total: int, n_in: int, decimation: int) -> int:
-    """Outputs per channel a call delivering n_in inputs completes after n_total earlier ones: output m comes out of the
-    call that delivers input m D."""
-    D = int(decimation)
-    return -(-(int(n_total) + int(n_in)) // D) - (-(-int(n_total) // D))
-
-
 def check_output(n_out: int, out_stride: int, out_ptr: int) -> None:
     """A call's output placement: channel c's run starts at out_ptr + 8 c out_stride."""
     if int(out_stride) < int(n_out):
         raise ValueError(f"out_stride={out_stride}: the call completes {n_out} outputs per channel")
     if int(out_ptr) % 8:
         raise ValueError("output pointer must be aligned to one complex64 sample")
-
-
-def check_same_device(engine_device: int, device: int) -> None:
-    if int(engine_device) != int(device):
-        raise ValueError(f"engine on device {engine_device}, channelizer on device {device}")
 
 
 def _complex_input(iq):
@@ -77,7 +65,7 @@ class Channelizer(nat._Handle):
 
     def __init__(self, channels: int, sample_rate: float, oversample: int = 1, taps=None, device: int = 0,
                  max_host_samples: int = 1 << 22):
-        self.taps = (None if taps is None else np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1)))
+        self.taps = None if taps is None else as_taps(taps)
         check_parameters(channels, oversample, self.taps.size if self.taps is not None else int(channels))
         self.channels = int(channels)
         self.oversample = int(oversample)
@@ -89,8 +77,6 @@ class Channelizer(nat._Handle):
         self.max_host_samples = int(max_host_samples)
         if self.taps is None:
             self.taps = design_decimator(self.channels)
-        if not np.all(np.isfinite(self.taps)):
-            raise ValueError("taps must be finite")
         self._inputs = 0
         self._h = C.c_void_p()
         nat.check(nat.lib.tdsa_chan_create(self.device, self.channels, self.oversample, int(self.taps.size),

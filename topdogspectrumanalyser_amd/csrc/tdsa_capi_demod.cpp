@@ -8,27 +8,18 @@
 using namespace tdsa;
 
 // ---- analog demodulator (tdsa_demod.hip) -------------------------------------------------------------------------
-struct tdsa_demod_s : Lane {
-  int mode = kDemodFM, C = 1, R = 1, max_taps = 1, max_rows = kDemodBlock;
-  size_t max_host = 0;
+struct tdsa_demod_s : Feed {
+  int mode = kDemodFM, C = 1, max_rows = kDemodBlock;
+  // the base's D = R; d_taps: [max_rows][R], tap q R + r at q * R + r; d_hist: [C][hist_stride] discriminator values
+  // (float) each; the host staging is [C][n_in] complex64 in, [C][n_out] float out
   long long hist_stride = 0;          // floats of history per channel: max phases * R
-  float* d_taps = nullptr;            // [max_rows][R], zero beyond n_taps
-  float* d_hist[2] = {nullptr, nullptr};    // [C][hist_stride] discriminator values, ping-pong
-  float2* d_last[2] = {nullptr, nullptr};   // [C] the last raw sample, ping-pong
-  int cur = 0;
-  int n_taps = 0;
-  long long n_total = 0;              // inputs per channel since the last reset
+  float2* d_last[2] = {nullptr, nullptr};   // [C] the last raw sample, ping-pong with d_hist (the same `cur`)
   int pole_mode = kDemodPoleOff;
   float scale = 1.0f;
   float* d_pole = nullptr;            // [2][kDemodPoleBlock]: (1 - c) c^i, then c^(i + 1)
   float* d_pole_y = nullptr;          // [C]
   float* d_pend = nullptr;            // [C][kDemodPoleBlock]
   void* d_meas = nullptr;             // [C] count, [C] sum, [C] sumsq, [C] max, [C] min
-  float2* h_in = nullptr;             // pinned staging of a host block, [C][n_in] ...
-  float2* d_in = nullptr;
-  float* d_out = nullptr;             // ... and of its outputs, [C][n_out]
-  float* h_out = nullptr;
-  size_t out_cap = 0;                 // floats of output staging
 
   long long* m_count() const { return static_cast<long long*>(d_meas); }
   double* m_sum() const { return reinterpret_cast<double*>(m_count() + C); }
@@ -55,87 +46,74 @@ int demod_clear_meas(tdsa_demod d) {
   return TDSA_OK;
 }
 
-// zero history, pole state, input count and measurements
-int demod_clear(tdsa_demod d) {
+const FeedNames kDemod = {"demodulator", "demodulator", "demod"};
+
+// what the base's clear() leaves: last samples, pole state and measurements.  Waits for the stream.
+int demod_clear_own(tdsa_demod d) {
   TRY(d->own_stream());
-  const size_t hb = size_t(d->C) * size_t(d->hist_stride) * sizeof(float);
-  for (int i = 0; i < 2; ++i) {
-    HIPCHK(hipMemsetAsync(d->d_hist[i], 0, hb, d->stream));
-    HIPCHK(hipMemsetAsync(d->d_last[i], 0, size_t(d->C) * sizeof(float2), d->stream));
-  }
+  for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(d->d_last[i], 0, size_t(d->C) * sizeof(float2), d->stream));
   HIPCHK(hipMemsetAsync(d->d_pole_y, 0, size_t(d->C) * sizeof(float), d->stream));
   HIPCHK(hipMemsetAsync(d->d_pend, 0, size_t(d->C) * kDemodPoleBlock * sizeof(float), d->stream));
   TRY(d->done(d->stream));
-  d->n_total = 0;
   return demod_clear_meas(d);
 }
 
-size_t demod_outputs(tdsa_demod d, size_t n_in) {
-  const long long R = d->R;
-  return size_t((d->n_total + (long long)n_in + R - 1) / R - (d->n_total + R - 1) / R);
+// zero history, pole state, input count and measurements
+int demod_clear(tdsa_demod d) {
+  TRY(d->clear());
+  return demod_clear_own(d);
 }
 
-// common checks of both process entry points (before any HIP call)
-int demod_check_call(tdsa_demod d, const void* in, size_t n_in, size_t in_stride, const void* out, size_t out_stride,
-                     size_t* n_out) {
-  if (in && (reinterpret_cast<uintptr_t>(in) % 8) != 0)
-    return fail(TDSA_ERR_ARG, "input pointer must be aligned to one complex64 sample (8 bytes)");
-  if (out && (reinterpret_cast<uintptr_t>(out) % 4) != 0)
-    return fail(TDSA_ERR_ARG, "output pointer must be aligned to one float32 (4 bytes)");
-  if (in_stride < n_in) return fail(TDSA_ERR_ARG, "in_stride=%zu: below the call's %zu samples per channel", in_stride, n_in);
-  if (!d) return fail(TDSA_ERR_ARG, "null demodulator");
-  if (!n_out) return fail(TDSA_ERR_ARG, "null n_out");
-  if (n_in > 0 && !in) return fail(TDSA_ERR_ARG, "null samples");
-  const size_t n = demod_outputs(d, n_in);
-  if (n > 0 && !out) return fail(TDSA_ERR_ARG, "null output");
-  if (out_stride < n)
-    return fail(TDSA_ERR_ARG, "out_stride=%zu: the call completes %zu outputs per channel", out_stride, n);
-  if (d->n_taps < 1) return fail(TDSA_ERR_STATE, "no taps: call tdsa_demod_set_taps first");
-  return TDSA_OK;
-}
-
-// enqueue one call on stream s: audio and post kernel over the outputs it completes, then the history
-int demod_run(tdsa_demod d, hipStream_t s, const float2* in, size_t n_in, size_t in_stride, float* out,
-              size_t out_stride, size_t* n_out) {
-  const long long R = d->R;
-  *n_out = demod_outputs(d, n_in);
-  if (n_in == 0) return TDSA_OK;
-  TRY(d->order(s));
-  DemodLaunch a;
-  a.mode = d->mode;
-  a.C = d->C;
-  a.R = d->R;
-  a.n_taps = d->n_taps;
-  a.in = in;
-  a.in_stride = (long long)in_stride;
-  a.n_in = (long long)n_in;
-  a.n0 = d->n_total;
-  a.taps = d->d_taps;
-  a.hist = d->d_hist[d->cur];
-  a.hist_out = d->d_hist[d->cur ^ 1];
-  a.last = d->d_last[d->cur];
-  a.last_out = d->d_last[d->cur ^ 1];
-  a.hist_stride = d->hist_stride;
-  a.out = out;
-  a.out_stride = (long long)out_stride;
-  a.m_first = (d->n_total + R - 1) / R;
-  a.n_out = (long long)*n_out;
-  a.pole_mode = d->pole_mode;
-  a.scale = d->scale;
-  a.pole_w = d->d_pole;
-  a.pole_cp = d->d_pole + kDemodPoleBlock;
-  a.pole_y = d->d_pole_y;
-  a.pole_pend = d->d_pend;
-  a.m_count = d->m_count();
-  a.m_max = d->m_max();
-  a.m_min = d->m_min();
-  a.m_sum = d->m_sum();
-  a.m_sumsq = d->m_sumsq();
-  HIPCHK(launch_demod(a, s));
-  TRY(d->done(s));
-  d->cur ^= 1;
-  d->n_total += (long long)n_in;
-  return TDSA_OK;
+// both process entry points: audio and post kernel over the outputs the call completes, then the history
+int demod_process(tdsa_demod d, tdsa_plan p, bool host, const void* in, size_t n_in, size_t in_stride, void* out,
+                  size_t out_stride, size_t* n_out) {
+  FeedCall c;
+  c.in = in;
+  c.n_in = n_in;
+  c.in_stride = in_stride;
+  c.in_align = 8;
+  c.out = out;
+  c.out_stride = out_stride;
+  c.out_unit = sizeof(float);
+  c.out_align = 4;
+  c.in_rows = c.out_rows = d ? size_t(d->C) : 1;
+  c.n_out = n_out;
+  const auto run = [&](hipStream_t s, const void* src, size_t src_stride, void* dst, size_t dst_stride, size_t* n) {
+    return d->enqueue(s, n_in, n, [&](long long m_first, long long n_new) {
+      DemodLaunch a;
+      a.mode = d->mode;
+      a.C = d->C;
+      a.R = d->D;
+      a.n_taps = d->n_taps;
+      a.in = static_cast<const float2*>(src);
+      a.in_stride = (long long)src_stride;
+      a.n_in = (long long)n_in;
+      a.n0 = d->n_total;
+      a.taps = d->d_taps;
+      a.hist = static_cast<float*>(d->d_hist[d->cur]);
+      a.hist_out = static_cast<float*>(d->d_hist[d->cur ^ 1]);
+      a.last = d->d_last[d->cur];
+      a.last_out = d->d_last[d->cur ^ 1];
+      a.hist_stride = d->hist_stride;
+      a.out = static_cast<float*>(dst);
+      a.out_stride = (long long)dst_stride;
+      a.m_first = m_first;
+      a.n_out = n_new;
+      a.pole_mode = d->pole_mode;
+      a.scale = d->scale;
+      a.pole_w = d->d_pole;
+      a.pole_cp = d->d_pole + kDemodPoleBlock;
+      a.pole_y = d->d_pole_y;
+      a.pole_pend = d->d_pend;
+      a.m_count = d->m_count();
+      a.m_max = d->m_max();
+      a.m_min = d->m_min();
+      a.m_sum = d->m_sum();
+      a.m_sumsq = d->m_sumsq();
+      return launch_demod(a, s);
+    });
+  };
+  return host ? Feed::host(d, kDemod, c, run) : Feed::dev(d, kDemod, p, c, run);
 }
 
 int demod_upload_pole(tdsa_demod d, double c) {
@@ -175,29 +153,21 @@ int tdsa_demod_create(int device_id, int mode, int channels, int decimation, int
   d->device = device_id;
   d->mode = mode;
   d->C = channels;
-  d->R = decimation;
+  d->D = decimation;
   d->max_taps = max_taps;
   d->max_rows = demod_tap_rows(max_taps, decimation);
   d->hist_stride = (long long)demod_phases(max_taps, decimation) * decimation;
   d->max_host = max_host_samples;
-  d->out_cap = max_host_samples / size_t(decimation) + size_t(channels);
-  const size_t tb = size_t(d->max_rows) * decimation * sizeof(float);
-  const size_t hb = size_t(channels) * size_t(d->hist_stride) * sizeof(float);
+  d->taps_len = size_t(d->max_rows) * decimation;
+  d->hist_bytes = size_t(channels) * size_t(d->hist_stride) * sizeof(float);
   hipError_t e = d->open(true);
-  if (e == hipSuccess) e = hipMalloc(&d->d_taps, tb);
-  for (int i = 0; i < 2; ++i) {
-    if (e == hipSuccess) e = hipMalloc(&d->d_hist[i], hb);
+  if (e == hipSuccess) e = d->alloc(size_t(channels), size_t(channels), sizeof(float));
+  for (int i = 0; i < 2; ++i)
     if (e == hipSuccess) e = hipMalloc(&d->d_last[i], size_t(channels) * sizeof(float2));
-  }
   if (e == hipSuccess) e = hipMalloc(&d->d_pole, 2 * kDemodPoleBlock * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&d->d_pole_y, size_t(channels) * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&d->d_pend, size_t(channels) * kDemodPoleBlock * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&d->d_meas, d->meas_bytes());
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&d->h_in), max_host_samples * sizeof(float2), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&d->d_in, max_host_samples * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(&d->d_out, d->out_cap * sizeof(float));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&d->h_out), d->out_cap * sizeof(float), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMemsetAsync(d->d_taps, 0, tb, d->stream);
   if (e != hipSuccess) {
     (void)tdsa_demod_destroy(d);
     return fail(TDSA_ERR_HIP, "demod create: %s", hipGetErrorString(e));
@@ -215,10 +185,8 @@ int tdsa_demod_create(int device_id, int mode, int channels, int decimation, int
 int tdsa_demod_destroy(tdsa_demod d) {
   if (!d) return TDSA_OK;
   d->drain();
-  free_all({d->d_taps, d->d_hist[0], d->d_hist[1], d->d_last[0], d->d_last[1], d->d_pole, d->d_pole_y, d->d_pend,
-            d->d_meas, d->d_in, d->d_out});
-  if (d->h_in) (void)hipHostFree(d->h_in);
-  if (d->h_out) (void)hipHostFree(d->h_out);
+  free_all({d->d_last[0], d->d_last[1], d->d_pole, d->d_pole_y, d->d_pend, d->d_meas});
+  d->release();
   d->close();
   delete d;
   return TDSA_OK;
@@ -226,17 +194,8 @@ int tdsa_demod_destroy(tdsa_demod d) {
 
 int tdsa_demod_set_taps(tdsa_demod d, const float* taps_host, int n_taps) {
   if (!d) return fail(TDSA_ERR_ARG, "null demodulator");
-  if (!taps_host) return fail(TDSA_ERR_ARG, "null taps");
-  if (n_taps < 1 || n_taps > d->max_taps)
-    return fail(TDSA_ERR_ARG, "n_taps=%d: 1 .. %d (the handle's max_taps)", n_taps, d->max_taps);
-  for (int k = 0; k < n_taps; ++k)
-    if (!std::isfinite(taps_host[k])) return fail(TDSA_ERR_ARG, "tap %d is not finite", k);
-  std::vector<float> pad(size_t(d->max_rows) * d->R, 0.0f);   // [q][r]: tap q R + r at q * R + r
-  std::memcpy(pad.data(), taps_host, size_t(n_taps) * sizeof(float));
-  TRY(d->own_stream());
-  HIPCHK(hipMemcpyAsync(d->d_taps, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
-  d->n_taps = n_taps;
-  return demod_clear(d);   // waits for the stream: the host copy of the taps is released
+  TRY(d->set_taps(taps_host, n_taps));
+  return demod_clear_own(d);
 }
 
 int tdsa_demod_set_pole(tdsa_demod d, int pole_mode, double c, float scale) {
@@ -258,37 +217,12 @@ int tdsa_demod_reset(tdsa_demod d) {
 
 int tdsa_demod_process(tdsa_demod d, const void* in_host, size_t n_in, size_t in_stride, float* out_host,
                        size_t out_stride, size_t* n_out) {
-  TRY(demod_check_call(d, in_host, n_in, in_stride, out_host, out_stride, n_out));
-  if (n_in > d->max_host / size_t(d->C))
-    return fail(TDSA_ERR_ARG, "block of %zu samples per channel, the handle stages at most %zu (max_host_samples / channels)",
-                n_in, d->max_host / size_t(d->C));
-  *n_out = 0;
-  if (n_in == 0) return TDSA_OK;
-  HIPCHK(hipSetDevice(d->device));
-  const float2* src = static_cast<const float2*>(in_host);
-  for (int c = 0; c < d->C; ++c)          // the previous host call has waited: the staging is free
-    std::memcpy(d->h_in + size_t(c) * n_in, src + size_t(c) * in_stride, n_in * sizeof(float2));
-  HIPCHK(hipMemcpyAsync(d->d_in, d->h_in, size_t(d->C) * n_in * sizeof(float2), hipMemcpyHostToDevice, d->stream));
-  size_t n = 0;
-  TRY(demod_run(d, d->stream, d->d_in, n_in, n_in, d->d_out, demod_outputs(d, n_in), &n));
-  if (n) HIPCHK(hipMemcpyAsync(d->h_out, d->d_out, size_t(d->C) * n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  for (int c = 0; n && c < d->C; ++c)
-    std::memcpy(out_host + size_t(c) * out_stride, d->h_out + size_t(c) * n, n * sizeof(float));
-  *n_out = n;
-  return TDSA_OK;
+  return demod_process(d, nullptr, true, in_host, n_in, in_stride, out_host, out_stride, n_out);
 }
 
 int tdsa_demod_process_dev(tdsa_demod d, tdsa_plan p, const void* in_dev, size_t n_in, size_t in_stride, void* out_dev,
                            size_t out_stride, size_t* n_out) {
-  TRY(demod_check_call(d, in_dev, n_in, in_stride, out_dev, out_stride, n_out));
-  if (p && p->device != d->device) return fail(TDSA_ERR_ARG, "plan and demodulator live on different devices");
-  *n_out = 0;
-  if (n_in == 0) return TDSA_OK;
-  hipStream_t s;
-  TRY(d->producer_stream(p, &s));
-  return demod_run(d, s, static_cast<const float2*>(in_dev), n_in, in_stride, static_cast<float*>(out_dev), out_stride,
-                   n_out);
+  return demod_process(d, p, false, in_dev, n_in, in_stride, out_dev, out_stride, n_out);
 }
 
 int tdsa_demod_read_meas(tdsa_demod d, int64_t* count, float* max_f32, float* min_f32, double* sum_f64,

@@ -1,12 +1,15 @@
 // tdsa_capi_internal.hpp - what the translation units of the C-ABI layer (tdsa_capi_*.cpp, one per handle type or
 // concern) share: error reporting, the status macros, the host idioms they all use, the few functions that cross files,
-// the plan itself, and - at the end, because it needs the plan - Lane, the base of the handle types: their stream,
-// their lifetime, and the one rule that orders a handle's launches whichever stream each goes on.  The public face of
-// the library is include/tdsa_hip.h.
+// the plan itself, and - at the end, because they need the plan - Lane, the base of the handle types: their stream,
+// their lifetime, and the one rule that orders a handle's launches whichever stream each goes on; and over it Feed, the
+// base of the streaming filters (down-converter, channelizer, demodulator): taps, history, input count, the bracket and
+// the checks of a call, and both entry points with the host one's staging.  The public face of the library is
+// include/tdsa_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -353,6 +356,182 @@ struct Lane {
     HIPCHK(hipEventSynchronize(ev_t1));
     HIPCHK(hipEventElapsedTime(elapsed_ms, ev_t0, ev_t1));
     return TDSA_OK;
+  }
+};
+
+// What the messages of a streaming filter call it: "null <handle>", "the <noun> takes ...", "tdsa_<prefix>_set_taps".
+struct FeedNames {
+  const char *handle, *noun, *prefix;
+};
+
+// One process call of a streaming filter, as both entry points see it: `in_rows` rows of n_in samples of in_unit bytes
+// each, row r at in + r * in_stride samples, and out_rows rows of out_unit-byte outputs at out + r * out_stride.
+// in_align / out_align: what the pointer must be a multiple of, in bytes; 0 for a host pointer that is only memcpy'd.
+struct FeedCall {
+  int fmt = TDSA_IN_C64;      // of the input; a filter that takes complex64 rows only leaves it
+  const void* in = nullptr;
+  size_t n_in = 0, in_stride = 0, in_rows = 1, in_unit = 8;
+  unsigned in_align = 0;
+  void* out = nullptr;
+  size_t out_stride = 0, out_rows = 1, out_unit = 8;
+  unsigned out_align = 0;
+  size_t* n_out = nullptr;
+};
+
+// The base of the streaming filters (down-converter, channelizer, demodulator) over Lane: a decimating FIR fed in
+// pieces, one output per D inputs, output m from the call that delivers input m D.  It owns the zero-padded tap table,
+// the ping-pong pair of history buffers and which half is current, the count of inputs since the last reset, and the
+// pinned and device staging of the synchronous host entry point.  A filter supplies its kernel's launch struct (the
+// callable of enqueue), its FeedCall, whatever set_taps makes it recompute, and state of its own, which it clears next
+// to clear() and flips with `cur`.
+//
+// The checks of a call come in ONE order, for both entry points of every filter (check): what needs no handle - format,
+// pointer alignment, in_stride - then null handle, null n_out, null samples, null output when outputs complete,
+// out_stride, "no taps"; host() adds the block size after them, dev() the plan's device.
+//
+// clear() only enqueues; reset and set_taps wait for the stream after it, so both return with the stream idle.
+struct Feed : Lane {
+  int D = 1;                          // inputs per output
+  int max_taps = 1, n_taps = 0;
+  size_t taps_len = 0;                // floats of d_taps: the filter's padded [rows][row length]
+  float* d_taps = nullptr;            // zero beyond n_taps
+  void* d_hist[2] = {nullptr, nullptr};   // hist_bytes each, ping-pong
+  size_t hist_bytes = 0;
+  int cur = 0;
+  long long n_total = 0;              // inputs (per row) since the last reset
+  size_t max_host = 0;                // samples, all rows together, one host call stages
+  void* h_in = nullptr;               // pinned staging of a host block, rows back to back ...
+  void* d_in = nullptr;
+  void* d_out = nullptr;              // ... and of its outputs
+  void* h_out = nullptr;
+
+  long long m_first() const { return (n_total + D - 1) / D; }   // the next output
+  size_t outputs(size_t n_in) const { return size_t((n_total + (long long)n_in + D - 1) / D - m_first()); }
+
+  // create, in the chain that began with open(); D, max_taps, taps_len, hist_bytes and max_host are set.  A host call
+  // brings at most max_host / in_rows samples per row, which complete at most that / D + 1 outputs per row.
+  hipError_t alloc(size_t in_rows, size_t out_rows, size_t out_unit) {
+    const size_t ob = ((max_host / in_rows) / size_t(D) + 1) * out_rows * out_unit;
+    hipError_t e = hipMalloc(&d_taps, taps_len * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&d_hist[0], hist_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_hist[1], hist_bytes);
+    if (e == hipSuccess) e = hipHostMalloc(&h_in, max_host * 8, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc(&d_in, max_host * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_out, ob);
+    if (e == hipSuccess) e = hipHostMalloc(&h_out, ob, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemsetAsync(d_taps, 0, taps_len * sizeof(float), stream);
+    return e;
+  }
+  // destroy, between drain() and close(): whichever of them exist
+  void release() {
+    free_all({d_taps, d_hist[0], d_hist[1], d_in, d_out});
+    if (h_in) (void)hipHostFree(h_in);
+    if (h_out) (void)hipHostFree(h_out);
+  }
+
+  // zero history and input count, enqueued on the handle's own stream
+  int clear() {
+    TRY(own_stream());
+    HIPCHK(hipMemsetAsync(d_hist[0], 0, hist_bytes, stream));
+    HIPCHK(hipMemsetAsync(d_hist[1], 0, hist_bytes, stream));
+    TRY(done(stream));
+    n_total = 0;
+    return TDSA_OK;
+  }
+
+  // new taps (tap k at float k of the padded table) and a clear(); on return the stream is idle and taps_host released
+  int set_taps(const float* taps_host, int n) {
+    if (!taps_host) return fail(TDSA_ERR_ARG, "null taps");
+    if (n < 1 || n > max_taps) return fail(TDSA_ERR_ARG, "n_taps=%d: 1 .. %d (the handle's max_taps)", n, max_taps);
+    for (int k = 0; k < n; ++k)
+      if (!std::isfinite(taps_host[k])) return fail(TDSA_ERR_ARG, "tap %d is not finite", k);
+    std::vector<float> pad(taps_len, 0.0f);
+    std::memcpy(pad.data(), taps_host, size_t(n) * sizeof(float));
+    TRY(own_stream());
+    HIPCHK(hipMemcpyAsync(d_taps, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    n_taps = n;
+    TRY(clear());
+    HIPCHK(hipStreamSynchronize(stream));
+    return TDSA_OK;
+  }
+
+  // One call on stream s: launch(m_first, n_out) enqueues the kernels over the n_out outputs the call completes, from
+  // d_hist[cur] into d_hist[cur ^ 1], and returns a hipError_t.
+  template <class Launch>
+  int enqueue(hipStream_t s, size_t n_in, size_t* n_out, Launch&& launch) {
+    *n_out = outputs(n_in);
+    if (n_in == 0) return TDSA_OK;
+    TRY(order(s));
+    HIPCHK(launch(m_first(), (long long)*n_out));
+    TRY(done(s));
+    cur ^= 1;
+    n_total += (long long)n_in;
+    return TDSA_OK;
+  }
+
+  // the shared checks of a call, before any HIP call (f may be null: that is one of them)
+  static int check(const Feed* f, const FeedNames& who, const FeedCall& c) {
+    if (c.fmt != TDSA_IN_I8 && c.fmt != TDSA_IN_U8 && c.fmt != TDSA_IN_C64)
+      return fail(TDSA_ERR_ARG, "in_format=%d: the %s takes complex IQ (TDSA_IN_I8 / _U8 / _C64)", c.fmt, who.noun);
+    const auto unit = [](unsigned align) { return align == 8 ? "complex64 sample" : "float32"; };
+    if (c.in_align && reinterpret_cast<uintptr_t>(c.in) % c.in_align != 0)
+      return fail(TDSA_ERR_ARG, "input pointer must be aligned to one %s (%u bytes)", unit(c.in_align), c.in_align);
+    if (c.out_align && reinterpret_cast<uintptr_t>(c.out) % c.out_align != 0)
+      return fail(TDSA_ERR_ARG, "output pointer must be aligned to one %s (%u bytes)", unit(c.out_align), c.out_align);
+    if (c.in_stride < c.n_in)
+      return fail(TDSA_ERR_ARG, "in_stride=%zu: below the call's %zu samples per channel", c.in_stride, c.n_in);
+    if (!f) return fail(TDSA_ERR_ARG, "null %s", who.handle);
+    if (!c.n_out) return fail(TDSA_ERR_ARG, "null n_out");
+    if (c.n_in > 0 && !c.in) return fail(TDSA_ERR_ARG, "null samples");
+    const size_t n = f->outputs(c.n_in);
+    if (n > 0 && !c.out) return fail(TDSA_ERR_ARG, "null output");
+    if (c.out_stride < n)
+      return fail(TDSA_ERR_ARG, "out_stride=%zu: the call completes %zu outputs per channel", c.out_stride, n);
+    if (f->n_taps < 1) return fail(TDSA_ERR_STATE, "no taps: call tdsa_%s_set_taps first", who.prefix);
+    return TDSA_OK;
+  }
+
+  // The two entry points.  run(s, in, in_stride, out, out_stride, n_out) is the filter's call on stream s over device
+  // memory; it ends in enqueue.
+  //
+  // host: through the staging, rows back to back both ways, on the handle's own stream; returns when the outputs are
+  // in the caller's memory
+  template <class Run>
+  static int host(Feed* f, const FeedNames& who, const FeedCall& c, Run&& run) {
+    TRY(check(f, who, c));
+    const size_t most = f->max_host / c.in_rows;
+    if (c.n_in > most)
+      return c.in_rows == 1
+                 ? fail(TDSA_ERR_ARG, "block of %zu samples, the handle stages at most %zu (max_host_samples)", c.n_in, most)
+                 : fail(TDSA_ERR_ARG, "block of %zu samples per channel, the handle stages at most %zu (max_host_samples / "
+                        "channels)", c.n_in, most);
+    *c.n_out = 0;
+    if (c.n_in == 0) return TDSA_OK;
+    HIPCHK(hipSetDevice(f->device));
+    const size_t irow = c.n_in * c.in_unit;
+    for (size_t r = 0; r < c.in_rows; ++r)   // the previous host call has waited: the staging is free
+      std::memcpy(static_cast<char*>(f->h_in) + r * irow, static_cast<const char*>(c.in) + r * c.in_stride * c.in_unit, irow);
+    HIPCHK(hipMemcpyAsync(f->d_in, f->h_in, c.in_rows * irow, hipMemcpyHostToDevice, f->stream));
+    size_t n = 0;
+    TRY(run(f->stream, static_cast<const void*>(f->d_in), c.n_in, f->d_out, f->outputs(c.n_in), &n));
+    const size_t orow = n * c.out_unit;
+    if (n) HIPCHK(hipMemcpyAsync(f->h_out, f->d_out, c.out_rows * orow, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    for (size_t r = 0; n && r < c.out_rows; ++r)
+      std::memcpy(static_cast<char*>(c.out) + r * c.out_stride * c.out_unit, static_cast<const char*>(f->h_out) + r * orow, orow);
+    *c.n_out = n;
+    return TDSA_OK;
+  }
+  // dev: in place, on plan p's stream (null: the handle's own), no host wait
+  template <class Run>
+  static int dev(Feed* f, const FeedNames& who, tdsa_plan p, const FeedCall& c, Run&& run) {
+    TRY(check(f, who, c));
+    if (p && p->device != f->device) return fail(TDSA_ERR_ARG, "plan and %s live on different devices", who.noun);
+    *c.n_out = 0;
+    if (c.n_in == 0) return TDSA_OK;
+    hipStream_t s;
+    TRY(f->producer_stream(p, &s));
+    return run(s, c.in, c.in_stride, c.out, c.out_stride, c.n_out);
   }
 };
 

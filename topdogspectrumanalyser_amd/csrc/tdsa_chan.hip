@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tdsa_chan.hpp"
+#include "tdsa_unpack.hpp"
 
 // every rounding below is written out
 #pragma clang fp contract(off)
@@ -34,21 +35,9 @@ constexpr int kB = kChanBlock;
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-__device__ inline void fill_lut(int fmt, float* lut) {
-  if (fmt == 1) lut[threadIdx.x] = float(double(threadIdx.x) / 127.5 - 1.0);   // pyrtlsdr's float64, then float32
-}
-
-// x[n0 + k], the unpack of section 4.8
+// x[n0 + k]: fmt and in are read from the launch here, behind the callers' branches, not ahead of them
 __device__ inline float2 chan_unpack(const ChanLaunch& a, long long k, const float* lut) {
-  if (a.fmt == 0) {
-    const char2 v = static_cast<const char2*>(a.in)[k];
-    return make_float2(float(v.x) * 0.0078125f, float(v.y) * 0.0078125f);   // (I + jQ) / 128: exact
-  }
-  if (a.fmt == 1) {
-    const uchar2 v = static_cast<const uchar2*>(a.in)[k];
-    return make_float2(lut[v.x], lut[v.y]);
-  }
-  return static_cast<const float2*>(a.in)[k];
+  return unpack_iq(a.fmt, a.in, k, lut);
 }
 
 // input n (absolute): this call's input, the history before it, zero after it

@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "tdsa_constellation.hpp"
+#include "tdsa_unpack.hpp"
 
 #pragma clang fp contract(off)
 
@@ -40,22 +41,6 @@ struct Walk {                     // LDS of the partial-block path
   int st_n[kStack], st_start[kStack], st_state[kStack];
   int n_leaves;
 };
-
-__device__ inline void load_iq(int fmt, const void* in, long long idx, const float* lut, float& re, float& im) {
-  if (fmt == 0) {
-    const char2 v = static_cast<const char2*>(in)[idx];
-    re = float(v.x) * 0.0078125f;   // (I + jQ) / 128: exact
-    im = float(v.y) * 0.0078125f;
-  } else if (fmt == 1) {
-    const uchar2 v = static_cast<const uchar2*>(in)[idx];
-    re = lut[v.x];
-    im = lut[v.y];
-  } else {
-    const float2 v = static_cast<const float2*>(in)[idx];
-    re = v.x;
-    im = v.y;
-  }
-}
 
 // numpy 2.x complex64 absolute (loops_unary_complex): an infinite part wins, then NaN, then L * sqrt(fma(r, r, 1))
 __device__ inline float np_cabs(float re, float im) {
@@ -166,10 +151,6 @@ __device__ T block_sum_full(const T* chains) {
   return x;
 }
 
-__device__ inline void fill_lut(int fmt, float* lut) {
-  if (fmt == 1) lut[threadIdx.x] = float(double(threadIdx.x) / 127.5 - 1.0);   // pyrtlsdr's complex128, then astype
-}
-
 __global__ __launch_bounds__(kThreads) void cst_power_kernel(CstLaunch a, int nblk) {
   __shared__ float lut[256];
   __shared__ float chains[2 * kThreads];
@@ -184,8 +165,8 @@ __global__ __launch_bounds__(kThreads) void cst_power_kernel(CstLaunch a, int nb
   const long long rest = a.seg_len - (long long)b * kCstBlock;
   const int nb = rest < kCstBlock ? int(rest) : kCstBlock;
   auto val = [&](int j) -> float {
-    float re, im;
-    load_iq(a.fmt, a.in, base + j, lut, re, im);
+    const float2 x = unpack_iq(a.fmt, a.in, base + j, lut);
+    const float re = x.x, im = x.y;
     const float m = np_cabs(re, im);
     return m * m;
   };
@@ -288,8 +269,8 @@ __global__ __launch_bounds__(kThreads) void cst_symbol_kernel(CstLaunch a, int n
   const bool do_tail = a.tail != nullptr && seg == 0 && (long long)b * kCstBlock + nb > tail0;
 
   auto sample = [&](int j, float& i, float& q) {
-    float re, im;
-    load_iq(a.fmt, a.in, base + j, lut, re, im);
+    const float2 x = unpack_iq(a.fmt, a.in, base + j, lut);
+    const float re = x.x, im = x.y;
     if (norm) {                      // numpy complex division by (rms + 0j): (re + im * 0) * (1 / rms)
       i = (re + im * 0.0f) * scl;
       q = (im - re * 0.0f) * scl;

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tdsa_ddc.hpp"
+#include "tdsa_unpack.hpp"
 
 // every rounding below is written out: the FIR's staging and the history kernel must mix a sample to the same bits
 #pragma clang fp contract(off)
@@ -30,27 +31,11 @@ constexpr int kMB = kDdcBlock;
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-__device__ inline void fill_lut(int fmt, float* lut) {
-  if (fmt == 1) lut[threadIdx.x] = float(double(threadIdx.x) / 127.5 - 1.0);   // pyrtlsdr's float64, then float32
-}
-
 // x[n0 + k] exp(-2 pi j p / 2^32): the top 12 phase bits from the table, the low 20 (an angle below 1.6e-3) by their
 // series, the product formed so that the table value takes only the final rounding
 __device__ inline float2 ddc_mix(const DdcLaunch& a, long long k, const float* lut) {
-  float xr, xi;
-  if (a.fmt == 0) {
-    const char2 v = static_cast<const char2*>(a.in)[k];
-    xr = float(v.x) * 0.0078125f;   // (I + jQ) / 128: exact
-    xi = float(v.y) * 0.0078125f;
-  } else if (a.fmt == 1) {
-    const uchar2 v = static_cast<const uchar2*>(a.in)[k];
-    xr = lut[v.x];
-    xi = lut[v.y];
-  } else {
-    const float2 v = static_cast<const float2*>(a.in)[k];
-    xr = v.x;
-    xi = v.y;
-  }
+  const float2 x = unpack_iq(a.fmt, a.in, k, lut);
+  const float xr = x.x, xi = x.y;
   const unsigned p = a.p0 + unsigned(k) * a.step;
   const float2 h = a.nco[p >> 20];
   const float t = float(p & 0xFFFFFu) * 1.46291807926715968e-9f;   // 2 pi / 2^32

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _native as nat
 from .engine import SpectrumEngine
-from .zoom import design_decimator
+from .zoom import as_taps, check_same_device, design_decimator, outputs_completed
 
 MAX_CHANNELS = 256
 MAX_DECIMATION = 64
@@ -61,13 +61,6 @@ def check_parameters(mode, channels: int, decimation: int, n_taps: int, pole: fl
     return int(key)
 
 
-def outputs_completed(n_total: int, n_in: int, decimation: int) -> int:
-    """Outputs per channel a call delivering n_in inputs completes after n_total earlier ones: output m comes out of the
-    call that delivers input m R."""
-    R = int(decimation)
-    return -(-(int(n_total) + int(n_in)) // R) - (-(-int(n_total) // R))
-
-
 def check_call(n_in: int, in_stride: int, ptr: int, n_out: int, out_stride: int, out_ptr: int) -> None:
     """A call's placement: channel c's input at ptr + 8 c in_stride, its outputs at out_ptr + 4 c out_stride."""
     if int(n_in) < 0:
@@ -84,11 +77,6 @@ def check_call(n_in: int, in_stride: int, ptr: int, n_out: int, out_stride: int,
         raise ValueError("null input pointer")
     if int(n_out) > 0 and not out_ptr:
         raise ValueError("null output pointer")
-
-
-def check_same_device(engine_device: int, device: int) -> None:
-    if int(engine_device) != int(device):
-        raise ValueError(f"engine on device {engine_device}, demodulator on device {device}")
 
 
 @dataclass
@@ -148,7 +136,7 @@ class Demodulator(nat._Handle, nat._Timer):
     def __init__(self, mode, input_rate: float, decimation: int = 1, channels: int = 1, taps=None,
                  deemphasis: Optional[float] = None, remove_carrier: bool = False, scale: float = 1.0, device: int = 0,
                  max_host_samples: int = 1 << 20):
-        self.taps = (None if taps is None else np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1)))
+        self.taps = None if taps is None else as_taps(taps)
         self._mode = check_parameters(mode, channels, decimation,
                                       self.taps.size if self.taps is not None else int(decimation))
         self.mode = "am" if self._mode == nat.DEMOD_AM else "fm"
@@ -159,8 +147,6 @@ class Demodulator(nat._Handle, nat._Timer):
             raise ValueError(f"input_rate={input_rate}")
         if self.taps is None:
             self.taps = design_audio_filter(self.decimation)
-        if not np.all(np.isfinite(self.taps)):
-            raise ValueError("taps must be finite")
         if not np.isfinite(float(scale)):
             raise ValueError(f"scale={scale}")
         self.scale = float(scale)

@@ -72,6 +72,27 @@ def alias_free_bins(nfft: int, decimation: int, sample_rate: float) -> slice:
     return slice(int(idx[0]), int(idx[-1]) + 1)
 
 
+def as_taps(taps) -> np.ndarray:
+    """A filter as the library takes it: contiguous float32 [T], every tap finite."""
+    h = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
+    if not np.all(np.isfinite(h)):
+        raise ValueError("taps must be finite")
+    return h
+
+
+def outputs_completed(n_total: int, n_in: int, decimation: int) -> int:
+    """Outputs (per channel) a call delivering n_in inputs completes after n_total earlier ones, one output per D inputs:
+    output m comes out of the call that delivers input m D."""
+    D = int(decimation)
+    return -(-(int(n_total) + int(n_in)) // D) - (-(-int(n_total) // D))
+
+
+def check_same_device(engine_device: int, device: int) -> None:
+    """A handle launches on the stream of an engine of its own device only."""
+    if int(engine_device) != int(device):
+        raise ValueError(f"engine on device {engine_device}, handle on device {device}")
+
+
 class DownConverter(nat._Handle):
     """Mixes `offset_hz` to 0 Hz and decimates by `decimation` (complex64 out, one output per D inputs)."""
     _destroy = "tdsa_ddc_destroy"
@@ -82,8 +103,7 @@ class DownConverter(nat._Handle):
         self.sample_rate = float(sample_rate)
         self.device = int(device)
         self.max_host_samples = int(max_host_samples)
-        self.taps = (design_decimator(self.decimation) if taps is None
-                     else np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1)))
+        self.taps = design_decimator(self.decimation) if taps is None else as_taps(taps)
         self._h = C.c_void_p()
         nat.check(nat.lib.tdsa_ddc_create(self.device, self.decimation, int(self.taps.size), self.max_host_samples,
                                           C.byref(self._h)))
@@ -266,7 +286,7 @@ class ZoomSpectrum(nat._Handle):
         """DDC onto the pending outputs, frames of everything complete, the unframed tail to the other buffer."""
         D = self.decimation
         total = self._inputs + int(n_in)
-        n_new = -(-total // D) + (self._inputs // -D)        # ceil(total / D) - ceil(inputs / D)
+        n_new = outputs_completed(self._inputs, n_in, D)
         self._grow(self._pending + n_new)
         y = self._y[self._cur]
         n_out = self.ddc.process_device(self.engine, fmt, ptr, n_in, y.value + 8 * self._pending)
