@@ -10,10 +10,14 @@ and as the device evaluates it, with P = ceil(T / M):
   w_m[r]  sum_{q < P} h[qM + r] x[mD - qM - r]
   W_m[p]  w_m[r] at p = (r - mD) mod M
   y_c[m]  sum_p W_m[p] exp(+2 pi j c p / M)
-Every array of outputs here is channel-major, [M][n_out], as the device stores it."""
+Every array of outputs here is channel-major, [M][n_out], as the device stores it.
+
+Non-finite samples: zoom_contract's rule with the padded window H = P M.  x[n*] reaches instant m through one branch,
+and the transform spreads it over every channel of that instant: where h[mD - n*] != 0 all M channels are non-finite,
+outside (mD - P M, mD] no channel of instant m changes a bit."""
 import numpy as np
 
-from zoom_contract import FMT_C64, FMT_I8, FMT_U8, n_outputs, unpack  # noqa: F401
+from zoom_contract import FMT_C64, FMT_I8, FMT_U8, hit_outputs, n_outputs, padded_window_outputs, unpack  # noqa: F401
 
 
 def branch_taps(T: int, M: int) -> int:

@@ -5,6 +5,14 @@ without reference to how the kernels compute it.
     a[m] = sum_{k < T} g[k] d[mR - k], d = 0 before sample 0
     y[m] = c y[m-1] + (1 - c) a[m], y[-1] = 0
     out  = s a | s y | s (a - y)
+
+Non-finite samples.  An output depends on the samples of its padded window only: a[m] on d[n] for n in (mR - QR, mR],
+Q = ceil(T / R), and d[n] on x[n] (FM: and x[n-1]).  FM gives d[n] = NaN when any part of x[n] or x[n-1] is not finite;
+AM gives a non-finite |x[n]|: NaN with a NaN part, inf with an infinite one (with both, np.abs says inf and the device's
+sqrt(fma(xr, xr, xi xi)) NaN: either).  Such a d[n] makes a[m] non-finite wherever g[mR - n] != 0; an output
+that meets it only under the zero padding T <= k < QR is unspecified, every other output does not see it.  The one-pole
+section and sum / sumsq keep a non-finite value as their recurrences do, until reset() / reset_measure(); count counts
+it; max and min skip NaN (np.fmax / np.fmin).  Other channels never see it.
 """
 import numpy as np
 
@@ -32,18 +40,32 @@ def n_outputs(n_in, R):
     return -(-int(n_in) // int(R))
 
 
+def phase_step(x, prev):
+    """arg(x conj prev) / pi elementwise (float64): 0 where the product is 0, +1 where it is negative real, NaN where
+    any part of x or prev is not finite."""
+    x, prev = np.asarray(x, dtype=np.complex128), np.asarray(prev, dtype=np.complex128)
+    with np.errstate(invalid="ignore"):
+        re = x.real * prev.real + x.imag * prev.imag
+        im = x.imag * prev.real - x.real * prev.imag
+        d = np.arctan2(im, re) / np.pi
+    d[(re == 0) & (im == 0)] = 0.0
+    d[(im == 0) & (re < 0)] = 1.0
+    bad = ~(np.isfinite(x.real) & np.isfinite(x.imag) & np.isfinite(prev.real) & np.isfinite(prev.imag))
+    d[bad] = np.nan                        # arctan2 alone gives a number for (finite, inf) and (inf, inf)
+    return d
+
+
 def discriminator(x, mode, as_stored=True):
     """d[n], float64, of one channel x, taken as the complex64 the device stores (as_stored=False: as it is given)."""
     x = np.asarray(x, dtype=np.complex64 if as_stored else np.complex128).astype(np.complex128)
     if mode == AM:
         return np.abs(x)
-    prev = np.concatenate([[0.0 + 0.0j], x[:-1]])
-    re = x.real * prev.real + x.imag * prev.imag
-    im = x.imag * prev.real - x.real * prev.imag
-    d = np.arctan2(im, re) / np.pi
-    d[(re == 0) & (im == 0)] = 0.0
-    d[(im == 0) & (re < 0)] = 1.0
-    return d
+    return phase_step(x, np.concatenate([[0.0 + 0.0j], x[:-1]]))
+
+
+def bad_discriminator_values(n_star, mode):
+    """The indices n at which a non-finite x[n_star] makes d[n] non-finite."""
+    return (n_star,) if mode == AM else (n_star, n_star + 1)
 
 
 def fir(d, g, R):
@@ -87,10 +109,12 @@ def reference(x, mode, g, R, pole_mode=POLE_OFF, c=0.0, scale=1.0):
 
 
 def measurements(a):
-    """(count, max, min, sum, sumsq) per channel over a [C][n_out]."""
+    """(count, max, min, sum, sumsq) per channel over a [C][n_out]; max and min skip NaN, the sums keep it."""
     a = np.atleast_2d(np.asarray(a, dtype=np.float64))
     n = a.shape[1]
-    return (np.full(a.shape[0], n, dtype=np.int64), a.max(axis=1), a.min(axis=1), a.sum(axis=1), (a * a).sum(axis=1))
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (np.full(a.shape[0], n, dtype=np.int64), np.fmax.reduce(a, axis=1, initial=-np.inf),
+                np.fmin.reduce(a, axis=1, initial=np.inf), a.sum(axis=1), (a * a).sum(axis=1))
 
 
 def pole_allowance(a, c):

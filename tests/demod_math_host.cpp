@@ -2,7 +2,9 @@
 // host against double: the header's arithmetic is +, -, x, fmaf and the correctly rounded / and sqrt only, so what this
 // program measures is what the device computes.  Prints the worst |error| in u = 2^-24: "fm <A>" in half turns, the
 // difference taken on the circle (a step next to +-pi may come out on the other side of the cut), "am <A>" in units
-// of |x|; then the pinned special cases, "special ok" or the first one that fails.
+// of |x|; then the pinned special cases, "special ok" or the first one that fails; then the non-finite rule over every
+// (x[n], x[n-1]) with parts from {NaN, +-inf, +-0, a few finite values}, "nonfinite ok <combinations>" or the first
+// combination that breaks it: FM is NaN exactly when a part is not finite, AM is |x| as IEEE has it (inf, else NaN).
 //
 //   clang++ -O2 -std=c++17 -I topdogspectrumanalyser_amd/csrc tests/demod_math_host.cpp -o demod_math_host
 #include <cmath>
@@ -88,5 +90,26 @@ int main() {
     return 1;
   }
   std::printf("special ok\n");
+
+  const float v[] = {NAN, INFINITY, -INFINITY, 0.0f, -0.0f, 1.0f, -0.5f, 0x1p-100f, -0x1p60f};
+  const int nv = int(sizeof(v) / sizeof(v[0]));
+  int bad_inputs = 0;
+  for (int i = 0; i < nv * nv * nv * nv; ++i) {
+    const float xr = v[i % nv], xi = v[i / nv % nv], yr = v[i / (nv * nv) % nv], yi = v[i / (nv * nv * nv)];
+    const bool finite = std::isfinite(xr) && std::isfinite(xi) && std::isfinite(yr) && std::isfinite(yi);
+    const float d = tdsa::demod_fm(xr, xi, yr, yi);
+    if (finite ? !(d > -1.0f && d <= 1.0f) : !std::isnan(d)) {
+      std::printf("nonfinite: fm(%g, %g | %g, %g) gave %.9g\n", xr, xi, yr, yi, d);
+      return 1;
+    }
+    const float e = tdsa::demod_am(xr, xi);
+    const bool inf = std::isinf(xr) || std::isinf(xi), nan = std::isnan(xr) || std::isnan(xi);
+    if (inf && nan ? std::isfinite(e) : inf ? !(std::isinf(e) && e > 0.0f) : nan ? !std::isnan(e) : !std::isfinite(e)) {
+      std::printf("nonfinite: am(%g, %g) gave %.9g\n", xr, xi, e);
+      return 1;
+    }
+    bad_inputs += !finite;
+  }
+  std::printf("nonfinite ok %d\n", bad_inputs);
   return 0;
 }

@@ -126,6 +126,42 @@ def test_discriminator_accuracy_stays_within_the_recorded_constant(sweep):
     assert "special ok" in sweep.stdout
 
 
+def test_discriminator_gives_nan_for_every_non_finite_sample(sweep):
+    """The enumeration of demod_math_host.cpp: FM is NaN for every (x[n], x[n-1]) with a part that is not finite and a
+    number in (-1, 1] otherwise, AM is IEEE's |x|; and the finite path is untouched - the accuracy sweep of the same run
+    still prints the figures the constants were rounded up from."""
+    assert sweep.returncode == 0, sweep.stdout
+    m = re.search(r"^nonfinite ok ([0-9]+)$", sweep.stdout, re.M)
+    assert m, sweep.stdout
+    assert int(m.group(1)) == 9 ** 4 - 6 ** 4                       # every combination with a non-finite part was looked at
+    assert re.search(r"^fm 1\.29$", sweep.stdout, re.M) and re.search(r"^am 1\.88$", sweep.stdout, re.M), sweep.stdout
+    assert (dc.A_D_FM, dc.A_D_AM) == (1.30, 1.90)
+
+
+def test_contract_discriminator_follows_the_non_finite_rule():
+    nan, inf = np.nan, np.inf
+    x = np.array([1, 1j, complex(nan, 0.1), 1, complex(inf, 0), -1, 2, complex(0, -inf), complex(nan, nan), 1, 1],
+                 dtype=np.complex64)
+    d = dc.discriminator(x, dc.FM)
+    assert list(np.isnan(d)) == [False, False, True, True, True, True, False, True, True, True, False]
+    assert list(d[[0, 1, 6, 10]]) == [0.0, 0.5, 1.0, 0.0]
+    e = dc.discriminator(x, dc.AM)
+    assert list(np.isfinite(e)) == [True, True, False, True, False, True, True, False, False, True, True]
+    assert e[4] == inf and e[7] == inf and np.isnan(e[2]) and np.isnan(e[8])
+    # the filter: an output is non-finite exactly where a non-zero tap meets the sample
+    g = np.array([0.5, 0.0, 0.25, 0.0], dtype=np.float32)             # the last phase's padding and an inner zero
+    dd = np.ones(12)
+    dd[5] = nan
+    with np.errstate(invalid="ignore"):
+        a = dc.fir(dd, g, 1)
+    assert list(np.nonzero(~np.isfinite(a))[0]) == [5, 6, 7, 8]         # np.convolve multiplies the zero taps too ...
+    hit = [m for m in range(12) if 0 <= m - 5 < g.size and g[m - 5] != 0]
+    assert hit == [5, 7]                                                # ... the rule names only these
+    cnt, mx, mn, s, ss = dc.measurements(np.array([[1.0, nan, 3.0], [inf, 2.0, -1.0]]))
+    assert list(cnt) == [3, 3] and list(mx) == [3.0, inf] and list(mn) == [1.0, -1.0]
+    assert np.isnan(s[0]) and np.isnan(ss[0]) and s[1] == inf and ss[1] == inf
+
+
 def test_design_document_states_the_measured_accuracy():
     txt = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "4.13" in txt and f"{dc.A_D_FM:.2f}" in txt and f"{dc.A_D_AM:.2f}" in txt

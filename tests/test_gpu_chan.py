@@ -1,11 +1,15 @@
 """The polyphase channelizer on the MI355X, pinned against something other than the kernel:
 exact integer branch sums and exact channels bit for bit, the float64 contract under a derived rounding allowance,
-split invariance, the channel-major layout, ChannelSpectra against the engine run channel by channel, and the handle's
+split invariance, streams past 2^31 and 2^32 inputs, tdsa_chan_set_taps on a handle that has streamed, host blocks above
+max_host_samples, the channel-major layout, ChannelSpectra against the engine run channel by channel, and the handle's
 launch order across streams.
 
 Shapes: M in {4, 16, 64, 256} x os in {1, 2} x P in {1, 3, 32} taps per branch, plus one T = 3M - 5: less than a wave,
-one wave and several waves per output instant, and a partly filled last phase.  A workgroup owns 2048 / M output instants;
-every case is three such tiles plus a ragged remainder.
+one wave and several waves per output instant, and a partly filled last phase; M in {8, 32, 128} x os in {1, 2} x
+P in {1, 9} - the other thread-group counts, both staging pads and the row skew of 2, one tap and a full register block
+followed by a partial one - P = 8, exactly one block, 17 branch taps with a partly filled last phase, and the tap limit
+P = 40 at M = 4, 128 and 256 (the last is the largest LDS request the launcher makes).  A workgroup owns 2048 / M output
+instants; every case is three such tiles plus a ragged remainder.
 
 The allowance of test 3, per output instant in the 2-norm over channels, with u = 2^-24:
     ||y^_m - y_m||_2 <= u ((P + 1) sqrt(M) ||a_m||_2 + 7 log2(M) ||y_m||_2),  a_m[r] = sum_q |h[qM + r]| |x[mD - qM - r]|
@@ -29,6 +33,8 @@ FS = 20e6
 U = 2.0 ** -24
 TILE = 2048
 SHAPES = [(M, os_, P * M) for M in (4, 16, 64, 256) for os_ in (1, 2) for P in (1, 3, 32)] + [(16, 2, 3 * 16 - 5)]
+SHAPES += [(M, os_, P * M) for M in (8, 32, 128) for os_ in (1, 2) for P in (1, 9)]
+SHAPES += [(8, 1, 8 * 8), (32, 2, 17 * 32 - 3), (4, 2, 40 * 4), (128, 2, 40 * 128), (256, 1, 40 * 256)]
 IDS = [f"M{M}-os{o}-T{T}" for M, o, T in SHAPES]
 
 
@@ -133,9 +139,13 @@ def _float_taps(M, T):
 
 
 def _check_allowance(got, x, h, M, os_, what):
-    P = cc.branch_taps(len(h), M)
-    ref = cc.restated(x, h, M, os_)
-    a = cc.abs_branches(x, h, M, os_)                                   # [n_out][M]
+    return _check_against(got, cc.restated(x, h, M, os_), cc.abs_branches(x, h, M, os_), len(h), what)
+
+
+def _check_against(got, ref, a, T, what):
+    """got and ref [M][n_out], a [n_out][M] the absolute branch sums: the allowance of the module's docstring."""
+    M = ref.shape[0]
+    P = cc.branch_taps(T, M)
     assert got.shape == ref.shape
     err = np.linalg.norm(got.astype(np.complex128) - ref, axis=0)
     bound = U * ((P + 1) * np.sqrt(M) * np.linalg.norm(a, axis=1) + 7 * np.log2(M) * np.linalg.norm(ref, axis=0))
@@ -179,8 +189,9 @@ def _pieces(n, size):
     return [size] * (n // size) + ([n % size] if n % size else [])
 
 
-@pytest.mark.parametrize("M,os_,T", [(4, 2, 11), (16, 1, 3 * 16), (64, 2, 32 * 64), (256, 1, 3 * 256 - 5)],
-                         ids=["M4-os2", "M16-os1", "M64-os2", "M256-os1"])
+@pytest.mark.parametrize("M,os_,T", [(4, 2, 11), (16, 1, 3 * 16), (64, 2, 32 * 64), (256, 1, 3 * 256 - 5),
+                                     (32, 2, 9 * 32), (128, 1, 3 * 128 - 5)],
+                         ids=["M4-os2", "M16-os1", "M64-os2", "M256-os1", "M32-os2", "M128-os1"])
 def test_split_invariance(M, os_, T):
     rng = np.random.default_rng(31 * M + os_)
     D = M // os_
@@ -214,6 +225,124 @@ def test_split_invariance(M, os_, T):
         assert np.array_equal(_bits(got), _bits(one))
 
 
+# ---- 4b: past 2^31 and 2^32 inputs -----------------------------------------------------------------------------------
+LONG_BLOCK = 1 << 24
+
+
+@functools.lru_cache(maxsize=None)
+def _long_block():
+    raw = np.random.default_rng(2 ** 32 + 12).integers(-128, 128, 2 * LONG_BLOCK).astype(np.int8)
+    raw.setflags(write=False)
+    return raw
+
+
+@pytest.mark.parametrize("M,os_", [(4, 2), (256, 1)], ids=["M4-os2", "M256-os1"])
+def test_streams_past_2_32_inputs(M, os_):
+    """A block of 2^24 int8 samples replayed 257 times with the default prototype: x[n] = block[n mod 2^24].  Checked
+    against the float64 defining sum, regrouped by branch (exp(-2 pi j c n / M) has period M in n) with every index in
+    int64, under the allowance of test 3: all M channels of the first and last 160 instants of the calls that end at
+    2^31 and 2^32 inputs and of the calls that begin there (the first ones read the history); the call that begins at
+    2^32 is the last.  At M = 4, os = 2 the output index itself passes 2^31, with the half-turn shift of odd
+    instants."""
+    reps, nb, keep = 257, LONG_BLOCK, 160
+    D = M // os_
+    raw = _long_block()
+    checked = (127, 128, 255, 256)
+    cap = nb // D + 2
+    with Channelizer(M, FS, os_, max_host_samples=64) as bank, _Dev(raw) as d_in, \
+            _Dev(nbytes=8 * M * cap * (1 + len(checked))) as d_y:
+        h = bank.taps
+        total, spans = 0, []
+        for i in range(reps):                               # every other call overwrites slot 0
+            slot = 1 + checked.index(i) if i in checked else 0
+            k = bank.process_device(None, cc.FMT_I8, d_in.p.value, nb, d_y.p.value + 8 * M * cap * slot, cap)
+            assert k <= cap
+            if slot:
+                spans.append((total, k, slot))
+            total += k
+        bank.reset()                                        # waits for the handle's stream
+        assert total == -(-(reps * nb) // D)
+        got, ms = [], []
+        for m0, k, slot in spans:
+            for a in (0, k - keep):
+                got.append(np.stack([d_y.get(keep, np.complex64, 8 * ((M * slot + c) * cap + a)) for c in range(M)]))
+                ms.append(m0 + a + np.arange(keep, dtype=np.int64))
+    got, ms = np.concatenate(got, axis=1), np.concatenate(ms)
+    assert ms.min() * D < 1 << 31 < ms.max() * D and np.any(ms * D > 1 << 32)
+    assert os_ == 1 or (ms.max() > 1 << 31 and np.any(ms & 1) and not np.all(ms & 1))
+    T, PM = h.size, cc.branch_taps(h.size, M) * M
+    hp = np.zeros(PM)
+    hp[:T] = h
+    idx = ms[:, None] * D - np.arange(PM, dtype=np.int64)[None, :]
+    assert idx.min() > 0 and idx.max() > 1 << 32
+    j = idx % nb
+    x = (raw[2 * j].astype(np.float64) + 1j * raw[2 * j + 1].astype(np.float64)) / 128.0
+    w = (x * hp).reshape(ms.size, -1, M).sum(axis=1)                   # w_m[r], [n][M]
+    a = (np.abs(x) * np.abs(hp)).reshape(ms.size, -1, M).sum(axis=1)
+    p = (np.arange(M, dtype=np.int64)[None, :] - ms[:, None] * D) % M  # W_m[p] at p = (r - mD) mod M
+    W = np.empty_like(w)
+    np.put_along_axis(W, p, w, axis=1)
+    _check_against(got, cc.transform(W.T), a, T, f"past 2^32 M={M} os={os_}: {ms.size} instants")
+
+
+# ---- 4c: entry points: taps on a live handle, host blocks above max_host_samples ---------------------------------------
+def _set_taps(bank, h):
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    nat.check(nat.lib.tdsa_chan_set_taps(bank._h, h.ctypes.data_as(C.c_void_p), int(h.size)))
+    bank.taps, bank._inputs = h, 0
+
+
+def test_set_taps_on_a_handle_that_has_streamed():
+    """A shorter prototype shortens P inside tap and history buffers sized for the handle's max_taps (40 rows, 3 in
+    use); afterwards the handle must behave as a fresh one with those taps: history cleared, inputs counted from 0."""
+    M, os_ = 32, 2
+    D = M // os_
+    rng = np.random.default_rng(78)
+    long_h = (rng.standard_normal(40 * M) / M).astype(np.float32)
+    short_h = (rng.standard_normal(3 * M - 5) / M).astype(np.float32)
+    n, n_out = _n_in(M, os_)
+    first = _raw(rng, n + 5 * D + 3, cc.FMT_I8)
+    later = _raw(rng, n, cc.FMT_I8)
+    cut = (n // 2) | 1                                    # the second call starts between two outputs
+
+    def run(bank):
+        return np.concatenate([bank.process(later[:2 * cut]), bank.process(later[2 * cut:])], axis=1)
+
+    def fresh(h):
+        with Channelizer(M, FS, os_, taps=h, max_host_samples=first.size // 2) as bank:
+            return run(bank)
+
+    with Channelizer(M, FS, os_, taps=long_h, max_host_samples=first.size // 2) as bank:
+        bank.process(first)
+        _set_taps(bank, short_h)
+        y_short = run(bank)
+        _set_taps(bank, long_h)
+        y_long = run(bank)
+    assert y_short.shape == y_long.shape == (M, n_out)
+    assert np.array_equal(_bits(y_short), _bits(fresh(short_h)))
+    assert np.array_equal(_bits(y_long), _bits(fresh(long_h)))
+
+
+@pytest.mark.parametrize("fmt", [cc.FMT_I8, cc.FMT_C64], ids=["int8", "complex64"])
+def test_host_block_larger_than_max_host_samples(fmt):
+    """process() cuts a block above max_host_samples into several library calls: the bits of the single call."""
+    M, os_ = 16, 2
+    rng = np.random.default_rng(79)
+    n, n_out = _n_in(M, os_)
+    raw = _raw(rng, n, fmt)
+    h = _float_taps(M, 3 * M - 5)
+    with Channelizer(M, FS, os_, taps=h, max_host_samples=n) as bank:
+        one = bank.process(raw)
+    with Channelizer(M, FS, os_, taps=h, max_host_samples=n // 3 + 1) as bank:
+        assert bank.max_host_samples < n < 3 * bank.max_host_samples
+        got = bank.process(raw)
+        assert got.shape == one.shape == (M, n_out) and np.array_equal(_bits(got), _bits(one))
+        bank.reset()
+        W = bank.process(raw, branches=True)
+    with Channelizer(M, FS, os_, taps=h, max_host_samples=n) as bank:
+        assert np.array_equal(_bits(W), _bits(bank.process(raw, branches=True)))
+
+
 # ---- 5: layout -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("branches", [False, True])
 def test_stride_leaves_the_gaps_alone(branches):
@@ -242,8 +371,8 @@ def test_stride_leaves_the_gaps_alone(branches):
 
 
 # ---- 6: ChannelSpectra -----------------------------------------------------------------------------------------------
-def test_channel_spectra_rows_are_the_engine_on_every_channel():
-    M, os_, nfft = 16, 2, 256
+def _spectra_rows_are_the_engine(M, os_):
+    nfft = 256
     D = M // os_
     rng = np.random.default_rng(66)
     blocks = [_raw(rng, F * D * nfft, cc.FMT_I8) for F in (2, 3)]
@@ -268,6 +397,14 @@ def test_channel_spectra_rows_are_the_engine_on_every_channel():
                         eng.synchronize()
                         want = d_rows.get(F * nfft, np.float32).reshape(F, nfft)
                         assert np.array_equal(got[c].view(np.uint32), want.view(np.uint32)), c
+
+
+def test_channel_spectra_rows_are_the_engine_on_every_channel():
+    _spectra_rows_are_the_engine(16, 2)
+
+
+def test_channel_spectra_rows_without_oversampling_at_8_channels():
+    _spectra_rows_are_the_engine(8, 1)
 
 
 def test_channel_spectra_finds_a_tone_in_the_stitched_row():

@@ -1,10 +1,13 @@
 """The analog demodulator on the MI355X, pinned against something other than the kernels:
-exact integer data bit for bit, the float64 contract under derived rounding allowances, split invariance, the layout,
+exact integer data bit for bit, the float64 contract under derived rounding allowances, split invariance, streams past
+2^31 and 2^32 inputs, tdsa_demod_set_taps on a handle that has streamed, host blocks above max_host_samples, the layout,
 the measurements, and the chain channelizer -> demodulator on one stream.
 
 Shapes (R, T): (1, 1), (1, 7), (3, 8), (8, 272), (64, 64), (64, 4096) - no filter, fewer residues than lanes, a residue
-group that is partly filled, 34 phases, one phase of 8 residue groups, and the largest filter; both modes, 1 and 3
-channels.  A workgroup owns kDemodTile = 256 outputs: every case is three tiles plus a ragged remainder of 85, ends
+group that is partly filled, 34 phases, one phase of 8 residue groups, and the largest filter - and (2, 18), (5, 37),
+(12, 96), (16, 16), (20, 53), (63, 4032): 9 phases (a register block and one tap), a ragged T, two residue groups with
+the second half filled at exactly 8 phases, two and three groups, and eight groups with the last one lane short at the
+largest Q; both modes, 1 and 3 channels.  A workgroup owns kDemodTile = 256 outputs: every case is three tiles plus a ragged remainder of 85, ends
 between two outputs (R > 1) and inside a pole block (853 = 13 * 64 + 21).
 
 Allowances of test 2, u = 2^-24, A_d the measured worst discriminator error of demod_contract (in u):
@@ -30,7 +33,8 @@ pytestmark = pytest.mark.gpu
 
 U = dc.U
 FI = 312.5e3
-SHAPES = [(1, 1), (1, 7), (3, 8), (8, 272), (64, 64), (64, 4096)]
+SHAPES = [(1, 1), (1, 7), (3, 8), (8, 272), (64, 64), (64, 4096),
+          (2, 18), (5, 37), (12, 96), (16, 16), (20, 53), (63, 63 * 64)]
 IDS = [f"R{R}-T{T}" for R, T in SHAPES]
 MODES = [("fm", dc.FM), ("am", dc.AM)]
 N_OUT = 3 * dc.TILE + 85
@@ -125,6 +129,12 @@ def _float_taps(R, T):
     return np.ascontiguousarray(design_decimator(max(R, 2), taps_per_phase=Q)[:T])
 
 
+def _allow_a(mode, g, absd):
+    """u ((T + 1) sum |g||d| + 2 A_d sum |g|) (AM: 2 A_d sum |g||d|) of absd = sum |g||d| per output."""
+    disc = 2 * dc.a_d(mode) * (absd if mode == dc.AM else np.abs(g.astype(np.float64)).sum())
+    return U * ((g.size + 1) * absd + disc)
+
+
 @functools.lru_cache(maxsize=None)
 def _float_case(mode, R, T):
     """Three channels: an FM tone with |d| <= 0.9, amplitude 0.1 .. 0.3 (AM: modulated around it), noise 3e-3."""
@@ -143,11 +153,7 @@ def _float_case(mode, R, T):
     d, a, _ = dc.reference(x, mode, g, R)
     if mode == dc.FM:
         assert np.abs(d).max() <= 0.9, np.abs(d).max()           # the +-pi wrap is not in play
-    ad = dc.a_d(mode)
-    g64 = np.abs(g.astype(np.float64))
-    absd = np.stack([dc.abs_fir(row, g, R) for row in d])
-    disc = 2 * ad * (absd if mode == dc.AM else g64.sum())
-    allow_a = U * ((T + 1) * absd + disc)
+    allow_a = _allow_a(mode, g, np.stack([dc.abs_fir(row, g, R) for row in d]))
     for arr in (x, g, d, a, allow_a):
         arr.setflags(write=False)
     return x, g, d, a, allow_a
@@ -201,8 +207,10 @@ def _pieces(n, size):
 
 
 @pytest.mark.parametrize("name,R,T,pole_mode,c", [("fm", 1, 7, 1, 0.757), ("am", 3, 8, 2, 0.999), ("fm", 8, 272, 2, 0.9),
-                                                  ("am", 64, 64, 1, 0.757), ("fm", 64, 4096, 1, 0.999)],
-                         ids=["fm-R1-low", "am-R3-high", "fm-R8-high", "am-R64-low", "fm-R64-T4096-low"])
+                                                  ("am", 64, 64, 1, 0.757), ("fm", 64, 4096, 1, 0.999),
+                                                  ("am", 12, 96, 1, 0.9), ("fm", 63, 4032, 2, 0.757)],
+                         ids=["fm-R1-low", "am-R3-high", "fm-R8-high", "am-R64-low", "fm-R64-T4096-low", "am-R12-low",
+                              "fm-R63-T4032-high"])
 def test_split_invariance(name, R, T, pole_mode, c):
     rng = np.random.default_rng(31 * R + T)
     n_out = dc.TILE + 45                                         # past a tile and four pole blocks, ending inside one
@@ -232,6 +240,156 @@ def test_split_invariance(name, R, T, pole_mode, c):
                 left -= k
         got = _device_run(dm, x, mixed + ([left] if left else []), n_out)
         assert np.array_equal(_bits(got), _bits(one))
+
+
+# ---- 3b: past 2^31 and 2^32 inputs -----------------------------------------------------------------------------------
+LONG_BLOCK = 1 << 22
+
+
+@functools.lru_cache(maxsize=None)
+def _long_block():
+    """One period of x[n] = block[n mod 2^22]: the phase steps 0.6 sin(2 pi 5 n / nb) half turns sum to nothing over a
+    period, so the step across the seam is as small as the others (|d| <= 0.61, the +-pi wrap is not in play); the
+    envelope 0.2 (1 + 0.5 sin(2 pi 3 n / nb)) has the same period; noise 1e-3."""
+    nb = LONG_BLOCK
+    rng = np.random.default_rng(2 ** 32 + 13)
+    t = np.arange(nb) / nb
+    phase = np.pi * np.cumsum(0.6 * np.sin(2 * np.pi * 5 * t))
+    amp = 0.2 * (1.0 + 0.5 * np.sin(2 * np.pi * 3 * t))
+    noise = 1e-3 * (rng.standard_normal(nb) + 1j * rng.standard_normal(nb))
+    x = (amp * np.exp(1j * phase) + noise).astype(np.complex64)
+    x.setflags(write=False)
+    return x
+
+
+@pytest.mark.parametrize("name,mode,R,pole_mode,c", [("fm", dc.FM, 64, dc.POLE_OFF, 0.0), ("am", dc.AM, 8, dc.POLE_LOW, 0.757)],
+                         ids=["fm-R64", "am-R8-low"])
+def test_streams_past_2_32_inputs(name, mode, R, pole_mode, c):
+    """A block of 2^22 complex64 samples of one channel replayed 1025 times with the default audio filter: x[n] =
+    block[n mod 2^22].  Checked against the float64 defining sum with every index in int64, under test 2's allowances:
+    the first and last 160 outputs of the calls that end at 2^31 and 2^32 inputs and of the calls that begin there (the
+    first ones read the history and the last raw sample); the call that begins at 2^32 is the last.  The pole's
+    memory is c^256 < 2^-100 at c = 0.757, so its reference starts from y = 0 256 outputs before the first checked one.
+    The output index stays below 2^31 here (2^32 / R outputs): only the input indices n_total, n_lo and the staged
+    (jlo + j) R pass 2^31 and 2^32; m_first, jlo and m_first % 64 are long long by reading and stay untested beyond.
+    Measured on the MI355X: 0.5 s at R = 64 and 3.2 s at R = 8, where demod_post_kernel walks a channel's 2^29 outputs
+    with one workgroup (the time halves with every doubling of R); the down-converter's test takes 0.3 s."""
+    nb, keep, lead = LONG_BLOCK, 160, 256
+    reps = (1 << 32) // nb + 1
+    checked = (reps // 2 - 1, reps // 2, reps - 2, reps - 1)
+    x = _long_block()
+    cap = nb // R + 2
+    with Demodulator(name, FI, R, 1, max_host_samples=64) as dm, _Dev(x) as d_in, \
+            _Dev(nbytes=4 * cap * (1 + len(checked))) as d_a:
+        g = dm.taps
+        dm.set_pole(pole_mode, c)
+        total, spans = 0, []
+        for i in range(reps):                               # every other call overwrites slot 0
+            slot = 1 + checked.index(i) if i in checked else 0
+            k = dm.process_device(None, d_in.p.value, nb, nb, d_a.p.value + 4 * cap * slot, cap)
+            assert k <= cap
+            if slot:
+                spans.append((total, k, slot))
+            total += k
+        dm.reset()                                          # waits for the handle's stream
+        assert total == -(-(reps * nb) // R)
+        audio = d_a.get(cap * (1 + len(checked)), np.float32)
+    T = g.size
+    g64 = g.astype(np.float64)
+    worst, n_lo, n_hi = 0.0, 1 << 62, 0
+    for m0, k, slot in spans:
+        for at in (0, k - keep):
+            ms = m0 + at - (lead if pole_mode else 0) + np.arange(keep + (lead if pole_mode else 0), dtype=np.int64)
+            idx = ms[:, None] * R - np.arange(T, dtype=np.int64)[None, :]
+            assert idx.min() > 0
+            n_lo, n_hi = min(n_lo, int(idx.min())), max(n_hi, int(idx.max()))
+            xs = x[idx % nb]
+            d = np.abs(xs.astype(np.complex128)) if mode == dc.AM else dc.phase_step(xs, x[(idx - 1) % nb])
+            assert mode == dc.AM or np.abs(d).max() <= 0.9
+            a = d @ g64
+            allow = _allow_a(mode, g, np.abs(d) @ np.abs(g64))
+            ref = dc.output(a, pole_mode, c, 1.0)
+            if pole_mode:
+                allow = allow + dc.pole_allowance(a, c)
+                ref, allow = ref[lead:], allow[lead:]
+            got = audio[cap * slot + at:cap * slot + at + keep]
+            worst = max(worst, _ratio(got, ref, allow, f"past 2^32 {name} R={R}: outputs {m0 + at} .."))
+    assert n_lo < 1 << 31 < 1 << 32 < n_hi
+    assert worst <= 1.0
+
+
+# ---- 3c: entry points: taps on a live handle, host blocks above max_host_samples ---------------------------------------
+def _set_taps(dm, g):
+    g = np.ascontiguousarray(g, dtype=np.float32)
+    nat.check(nat.lib.tdsa_demod_set_taps(dm._h, g.ctypes.data_as(C.c_void_p), int(g.size)))
+    dm.taps, dm._inputs = g, 0
+
+
+def _meas_equal(m, want):
+    return all(np.array_equal(getattr(m, f), getattr(want, f)) for f in ("count", "max", "min", "sum", "sumsq"))
+
+
+@pytest.mark.parametrize("name", ["fm", "am"])
+def test_set_taps_on_a_handle_that_has_streamed(name):
+    """A shorter filter shortens Q inside tap and history buffers sized for the handle's max_taps (64 phases, 3 in
+    use, the history's channel stride still 64 R); afterwards the handle must behave as a fresh one with those taps:
+    history, last sample and pole state cleared, inputs counted from 0, the pole kept, the measurements restarted."""
+    R, chans = 12, 2
+    rng = np.random.default_rng(78)
+    long_g = (rng.standard_normal(64 * R) / R).astype(np.float32)
+    short_g = (rng.standard_normal(3 * R - 5) / R).astype(np.float32)
+    n_out = dc.TILE + 45
+    n = _n_in(R, n_out)
+    first = (0.3 * (rng.standard_normal((chans, n + 5 * R + 3)) + 1j * rng.standard_normal((chans, n + 5 * R + 3)))).astype(np.complex64)
+    later = (0.3 * (rng.standard_normal((chans, n)) + 1j * rng.standard_normal((chans, n)))).astype(np.complex64)
+    cut = n // 2 + 1
+    assert cut % R and -(-cut // R) % dc.POLE_BLOCK      # the second call starts between two outputs, inside a pole block
+    kw = dict(deemphasis=75e-6, scale=0.5, max_host_samples=first.size)
+
+    def run(dm):
+        y = np.concatenate([dm.process(later[:, :cut]), dm.process(later[:, cut:])], axis=1)
+        return y, dm.measure()
+
+    def fresh(g):
+        with Demodulator(name, FI, R, chans, taps=g, **kw) as dm:
+            return run(dm)
+
+    with Demodulator(name, FI, R, chans, taps=long_g, **kw) as dm:
+        dm.process(first)
+        assert np.all(dm.measure().count == dc.n_outputs(first.shape[1], R))
+        _set_taps(dm, short_g)
+        none = dm.measure()
+        assert np.all(none.count == 0) and np.all(none.sum == 0) and np.all(none.sumsq == 0)
+        assert np.all(none.max == -np.inf) and np.all(none.min == np.inf)
+        y_short, m_short = run(dm)
+        _set_taps(dm, long_g)
+        assert np.all(dm.measure().count == 0)
+        y_long, m_long = run(dm)
+    for got, m, g in ((y_short, m_short, short_g), (y_long, m_long, long_g)):
+        want, m_want = fresh(g)
+        assert got.shape == (chans, n_out) and np.array_equal(_bits(got), _bits(want))
+        assert np.all(m.count == n_out) and _meas_equal(m, m_want)
+
+
+@pytest.mark.parametrize("name", ["fm", "am"])
+def test_host_block_larger_than_max_host_samples(name):
+    """process() cuts a block above max_host_samples / C per channel into several library calls, each an offset into
+    the rows of the whole block with in_stride = n: the bits of the single call, and its measurements' count and extremes."""
+    R, T, chans = 3, 8, 3
+    rng = np.random.default_rng(79)
+    n_out = dc.TILE + 45
+    n = _n_in(R, n_out)
+    x = (0.3 * (rng.standard_normal((chans, n)) + 1j * rng.standard_normal((chans, n)))).astype(np.complex64)
+    kw = dict(taps=_float_taps(R, T), deemphasis=75e-6)
+    with Demodulator(name, FI, R, chans, max_host_samples=chans * n, **kw) as dm:
+        one, m_one = dm.process(x), dm.measure()
+    with Demodulator(name, FI, R, chans, max_host_samples=chans * (n // 3 + 1), **kw) as dm:
+        assert dm.max_host_samples // chans < n < 3 * (dm.max_host_samples // chans)
+        got, m = dm.process(x), dm.measure()
+    assert got.shape == one.shape == (chans, n_out) and np.array_equal(_bits(got), _bits(one))
+    for f in ("count", "max", "min"):
+        assert np.array_equal(getattr(m, f), getattr(m_one, f)), f
+    assert np.allclose(m.sum, m_one.sum, rtol=1e-12, atol=1e-12) and np.allclose(m.sumsq, m_one.sumsq, rtol=1e-12, atol=1e-12)
 
 
 # ---- 4: layout -------------------------------------------------------------------------------------------------------

@@ -8,6 +8,12 @@ Inputs count from the last reset, across calls: n = 0, 1, ...
   v[n]  x[n] exp(-2 pi j p[n] / 2^32), and 0 for n < 0
   y[m]  sum_{k < T} h[k] v[mD - k]; output m is emitted by the call that delivers input mD, so n_total inputs give
         ceil(n_total / D) outputs
+
+Non-finite samples (the rule of all three streaming filters; H = phases D here with phases = ceil(T / D), P M for the
+channelizer, Q R for the demodulator).  Output m depends on the inputs of its padded window (mD - H, mD] only: outside
+it a non-finite x[n*] changes no bit of any output, whatever the split into calls: the device history carries it for
+that window (the down-converter's, rounded up to 8 phases, for longer, where no output reads it).  Inside, every output whose tap h[mD - n*] is not zero is non-finite (all channels of a
+channelizer instant); an output that meets x[n*] only under the zero padding T <= k < H is unspecified.
 """
 import numpy as np
 
@@ -60,6 +66,21 @@ def direct(v: np.ndarray, h: np.ndarray, D: int, ms) -> np.ndarray:
 def by_convolution(v: np.ndarray, h: np.ndarray, D: int) -> np.ndarray:
     """Every output at once: np.convolve(v, h)[::D], ceil(n / D) of them."""
     return np.convolve(v, np.asarray(h, dtype=np.float64))[::D][:n_outputs(len(v), D)]
+
+
+def padded_window_outputs(n_star: int, H: int, D: int, n_out: int) -> np.ndarray:
+    """The outputs m < n_out whose padded window (mD - H, mD] holds input n_star; H a multiple of D."""
+    lo, hi = -(-int(n_star) // D), (int(n_star) + H - 1) // D
+    return np.arange(lo, min(hi, n_out - 1) + 1)
+
+
+def hit_outputs(n_star: int, h, D: int, n_out: int) -> np.ndarray:
+    """The outputs m < n_out that meet input n_star under a non-zero tap: these a non-finite x[n_star] makes non-finite."""
+    h = np.asarray(h)
+    m = np.arange(-(-int(n_star) // D), n_out)
+    k = m * D - int(n_star)
+    ok = k < h.size
+    return m[ok][h[k[ok]] != 0]
 
 
 def lanes(D: int) -> int:

@@ -34,10 +34,12 @@ TDSA_HD inline float demod_atan_over_pi(float t) {
 
 // atan2(im, re) / pi in (-1, 1]: 0 at im = re = 0, +1 at im = +-0 and re < 0; the axes are exact (0, +-1/2, 1).
 // Octant reduction: the smaller of |re|, |im| over the larger, the polynomial, then the reflections, all in half turns.
+// NaN where either argument is NaN or both are infinite (what a non-finite sample makes of the product): a NaN among
+// ax, ay leaves one in mx or mn, so the early return is 0 + 0 or NaN, and inf / inf is NaN.
 TDSA_HD inline float demod_atan2_over_pi(float im, float re) {
   const float ax = fabsf(re), ay = fabsf(im);
   const float mx = ax > ay ? ax : ay, mn = ax > ay ? ay : ax;
-  if (!(mx > 0.0f)) return 0.0f;
+  if (!(mx > 0.0f)) return mx + mn;
   float r = demod_atan_over_pi(mn / mx);
   if (ay > ax) r = 0.5f - r;
   if (re < 0.0f) r = 1.0f - r;
