@@ -355,10 +355,12 @@ int tdsa_density_read_u8(tdsa_density d, uint8_t* img_host, float* levels2);
  * table's dtype, and np.histogram2d(i, q, bins, [[-range, range], [-range, range]]) laid out as the image
  * ([q_bin][i_bin], uint32 counts; the image is log1p of them).
  * _set_refs: n_points (<= 64) x {x, y} interleaved, float32 (is_f64 = 0) or float64; 0 points = no EVM (the
- * reference's None for an unknown modulation).  _set_density: 1 <= bins <= 128, range > 0 and finite.
+ * reference's None for an unknown modulation); a NaN or infinite point is refused.
+ * _set_density: 1 <= bins <= 128, range > 0 and finite.
  * _process: one host block of n <= max_host_samples samples (one host wait): rms, evm (has_evm = 0 <=> None), counts
  * [bins][bins], and the last n_tail normalised points as float32 i[n_tail] then q[n_tail] (n_tail is clamped to n);
- * any output may be NULL.  _process_dev: a capture already on the device, n_seg segments of seg_len samples every hop
+ * any output may be NULL.
+ * _process_dev: a capture already on the device (aligned to one sample), n_seg segments of seg_len samples every hop
  * samples, each exactly what _process gives for that slice alone: rms / EVM per segment to the host (either may be
  * NULL; EVM NaN without a table), counts [n_seg][bins][bins] to a device buffer (or NULL); p = the plan whose stream
  * produced the capture (ordered after it), or NULL. */

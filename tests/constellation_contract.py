@@ -142,6 +142,23 @@ def histogram(i_data, q_data, r, bins=128):
     return np.bincount(flat, minlength=bins * bins).astype(np.uint32).reshape(bins, bins)
 
 
+def histogram_rows(i_data, q_data, r, bins=128):
+    """histogram() of every row of two [rows, n] arrays: counts[row][q_bin][i_bin]."""
+    e = edges(r, bins)
+
+    def idx(v):
+        v = v.astype(np.float64)
+        k = np.searchsorted(e, v.reshape(-1), side="right").reshape(v.shape)
+        k[v == e[-1]] -= 1
+        return k
+
+    ki, kq = idx(i_data), idx(q_data)
+    keep = (ki >= 1) & (ki <= bins) & (kq >= 1) & (kq <= bins)
+    row = np.broadcast_to(np.arange(ki.shape[0])[:, None], ki.shape)
+    flat = (row[keep] * bins + (kq[keep] - 1)) * bins + (ki[keep] - 1)
+    return np.bincount(flat, minlength=ki.shape[0] * bins * bins).astype(np.uint32).reshape(ki.shape[0], bins, bins)
+
+
 def min_dist_sq(i_data, q_data, pts):
     """Brute-force nearest-point squared distance in the table's dtype, NaN propagating."""
     dt = pts.dtype
@@ -156,11 +173,30 @@ def min_dist_sq(i_data, q_data, pts):
     return best
 
 
-def evaluate(iq, modulation="qpsk", r=1.5, bins=128):
-    """dict(rms float32, evm float or None, counts [bins][bins] uint32, i, q float32) of update_iq_data."""
+def split_leaves(n, depth=0):
+    """(leaf sizes in order, depth of the deepest leaf) of numpy's pairwise_sum over n elements; the root is at 0."""
+    if n <= 128:
+        return [n], depth
+    n2 = n // 2
+    n2 -= n2 % 8
+    left, dl = split_leaves(n2, depth + 1)
+    right, dr = split_leaves(n - n2, depth + 1)
+    return left + right, max(dl, dr)
+
+
+def sequential_sum(x):
+    """A plain left-to-right fold in x's dtype: what a summation that ignores numpy's tree would give."""
+    return np.cumsum(x, dtype=x.dtype)[-1] if len(x) else x.dtype.type(0)
+
+
+def evaluate(iq, modulation="qpsk", r=1.5, bins=128, pts=None):
+    """dict(rms float32, evm float or None, counts [bins][bins] uint32, i, q float32) of update_iq_data; pts (an
+    [n, 2] float32 / float64 table, possibly empty) overrides reference_points(modulation).  evaluate_rows() below is
+    its twin over many rows at once: a change here belongs there too."""
     iq = np.asarray(iq).astype(np.complex64)
     a = cabs(iq)
-    rms = np.sqrt(np_mean((a * a).astype(np.float32))).astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):        # |x|^2 may overflow: rms is inf then, as numpy's
+        rms = np.sqrt(np_mean((a * a).astype(np.float32))).astype(np.float32)
     re = iq.real.astype(np.float32)
     im = iq.imag.astype(np.float32)
     if rms > np.float32(1e-10):
@@ -171,13 +207,48 @@ def evaluate(iq, modulation="qpsk", r=1.5, bins=128):
             q_data = ((im - re * z) * scl).astype(np.float32)
     else:
         i_data, q_data = re, im
-    pts = reference_points(modulation)
+    if pts is None:
+        pts = reference_points(modulation)
     evm = None
-    if pts is not None:
+    if pts is not None and len(pts):
         d = min_dist_sq(i_data, q_data, pts)
         evm = float(np.sqrt(np_mean(d)))
     return {"rms": np.float32(rms), "evm": evm, "counts": histogram(i_data, q_data, r, bins), "i": i_data,
             "q": q_data}
+
+
+def _rows_mean(x):
+    """np_mean of every row of a [rows, n] float array."""
+    acc = np.zeros(x.shape[0], x.dtype)
+    for lo in range(0, x.shape[1], BLOCK):
+        acc = acc + _pairwise(x[:, lo:lo + BLOCK])
+    mean = acc.astype(np.float64) / np.float64(x.shape[1])
+    return mean.astype(x.dtype)
+
+
+def evaluate_rows(rows, modulation="qpsk", r=1.5, bins=128, pts=None):
+    """evaluate() of every row of a [rows, n] complex array at once (the segments of a capture), with the same
+    operations in the same order: dict(rms [rows] float32, evm [rows] float64 (NaN without a table), counts
+    [rows][bins][bins] uint32, i, q [rows, n] float32).  It restates evaluate(): keep the two in step
+    (tests/test_constellation_host.py compares them row by row)."""
+    rows = np.asarray(rows).astype(np.complex64)
+    a = cabs(rows)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        rms = np.sqrt(_rows_mean((a * a).astype(np.float32))).astype(np.float32)
+        re = rows.real.astype(np.float32)
+        im = rows.imag.astype(np.float32)
+        on = (rms > np.float32(1e-10))[:, None]
+        scl = (np.float32(1.0) / rms).astype(np.float32)[:, None]
+        z = np.float32(0.0)
+        i_data = np.where(on, (re + im * z) * scl, re).astype(np.float32)
+        q_data = np.where(on, (im - re * z) * scl, im).astype(np.float32)
+    if pts is None:
+        pts = reference_points(modulation)
+    evm = np.full(len(rows), np.nan)
+    if pts is not None and len(pts):
+        with np.errstate(over="ignore", invalid="ignore"):
+            evm = np.sqrt(_rows_mean(min_dist_sq(i_data, q_data, pts))).astype(np.float64)
+    return {"rms": rms, "evm": evm, "counts": histogram_rows(i_data, q_data, r, bins), "i": i_data, "q": q_data}
 
 
 def readout(evm, modulation):

@@ -122,14 +122,16 @@ int tdsa_constellation_set_refs(tdsa_constellation c, const void* xy, int n_poin
       if (y == x) return;
     v.push_back(x);
   };
-  bool distinct = true, finite = true;
+  bool distinct = true;
   for (int k = 0; k < n_points; ++k) {
+    // the kernel's fmin would drop a NaN point where np.min propagates it; the reference has no such table
+    if (!std::isfinite(px[k]) || !std::isfinite(py[k]))
+      return fail(TDSA_ERR_ARG, "point %d = (%g, %g): reference points must be finite", k, px[k], py[k]);
     add_level(xs, px[k]);
     add_level(ys, py[k]);
-    finite = finite && std::isfinite(px[k]) && std::isfinite(py[k]);
     for (int j = 0; j < k; ++j) distinct = distinct && !(px[j] == px[k] && py[j] == py[k]);
   }
-  const bool sep = n_points > 0 && finite && distinct && xs.size() * ys.size() == size_t(n_points);
+  const bool sep = n_points > 0 && distinct && xs.size() * ys.size() == size_t(n_points);
   const std::vector<double>& ax = sep ? xs : px;
   const std::vector<double>& ay = sep ? ys : py;
   double tab[2 * kCstMaxPoints] = {};
@@ -205,6 +207,8 @@ int tdsa_constellation_process_dev(tdsa_constellation c, tdsa_plan p, int in_for
   if (!c) return fail(TDSA_ERR_ARG, "null constellation");
   TRY(cst_check_format(in_format));
   if (!iq_dev) return fail(TDSA_ERR_ARG, "null samples");
+  if ((reinterpret_cast<uintptr_t>(iq_dev) % uintptr_t(bytes_per_sample(in_format))) != 0)
+    return fail(TDSA_ERR_ARG, "samples pointer must be aligned to one sample (%d bytes)", bytes_per_sample(in_format));
   if (seg_len == 0 || n_seg < 1) return fail(TDSA_ERR_ARG, "seg_len=%zu n_seg=%d: need non-empty segments", seg_len, n_seg);
   if (n_seg > 1 && hop == 0) return fail(TDSA_ERR_ARG, "hop=0 with %d segments", n_seg);
   if (p && p->device != c->device) return fail(TDSA_ERR_ARG, "plan and constellation live on different devices");

@@ -33,8 +33,10 @@ namespace tdsa {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxLeaves = 128;   // leaves of a block of <= 8192: every leaf of a split holds at least 64 elements
-constexpr int kStack = 16;        // recursion depth of a block of <= 8192 is at most 8
+// checked for every n <= 8192 by tests/test_constellation_host.py: at most 65 leaves (every leaf of a split holds at
+// least 64 elements), the deepest leaf 7 splits below the root
+constexpr int kMaxLeaves = 128;
+constexpr int kStack = 16;
 
 struct Walk {                     // LDS of the partial-block path
   int lstart[kMaxLeaves], lsize[kMaxLeaves];
