@@ -100,6 +100,80 @@ def test_uint8_unpack_is_the_frame_kernels():
     assert np.array_equal(re, want) and np.array_equal(im, want[::-1]) and re[0] == -1.0 and re[255] == 1.0
 
 
+def test_origin_is_the_identity_at_zero_and_a_shift_elsewhere_on_the_golden_ticks():
+    """view(origin=0) is view() on every recorded tick; the last `capacity` samples with origin = base see the same
+    window, and so does the same tail declared 2^32 samples later, shifted by exactly that."""
+    rate, ticks = zc.golden_ticks(GOLDEN)
+    capacity = int(2.0 * rate)
+    history = np.empty(0, dtype=np.float32)
+    triggered = 0
+    for t in ticks:
+        history = np.concatenate([history, zc.detect(*zc.unpack(t["raw"], "i8"), "real")])
+        n_display = max(int(t["window"] * rate), 4)
+        start, trig, chunk = zc.view(history, capacity, n_display, t["mode"], t["level"])
+        s0, t0, c0 = zc.view(history, capacity, n_display, t["mode"], t["level"], origin=0)
+        assert (s0, t0) == (start, trig) and np.array_equal(c0, chunk) and np.array_equal(chunk, t["shown"])
+        base = max(0, history.size - capacity)
+        for shift in (0, 1 << 32):
+            if history.size < capacity and shift:
+                continue                                  # a short history is not the tail of a longer one
+            s1, t1, c1 = zc.view(history[base:], capacity, n_display, t["mode"], t["level"], origin=base + shift)
+            assert (s1, t1) == (start + shift, trig) and np.array_equal(c1, chunk)
+        triggered += trig
+    assert triggered >= 50 and history.size > 10 * capacity
+    with pytest.raises(ValueError):
+        zc.view(history[-10:], capacity, 4, "rise", 0.0, origin=history.size - 10)   # does not reach back to base
+
+
+def test_inputs_of_the_shapes_suite_discriminate():
+    """The CPU half of tests/test_gpu_zero_span_shapes.py: exact sums, crossing trains that cross at every sample, DB
+    inputs whose neighbours are 0.1 dB apart, push streams that meet every head, tail and piece length."""
+    # exact sums: multiples of 2^-7 below 1 - up to 2^46 of them fit 53 bits
+    rng = np.random.default_rng(0)
+    e = zc.crossing_train(100_000, rng)
+    assert zc.sum_is_exact(e) and np.all(np.abs(e) < 1) and np.array_equal(e * 128, np.rint(e * 128))
+    assert zc.crossings(e) == (50_000, 49_999) and np.all((e[:-1] < 0) != (e[1:] < 0))
+    assert zc.crossings(zc.crossing_train(7, rng, first_above=True)) == (3, 3)
+    shuffled = rng.permutation(e).astype(np.float64)
+    assert np.sum(shuffled) == np.sum(e, dtype=np.float64) == float(np.sum(np.rint(e.astype(np.float64) * 128).astype(np.int64))) / 128
+    assert not zc.sum_is_exact([0.1]) and not zc.sum_is_exact([2.0 ** -8]) and not zc.sum_is_exact([np.nan])
+    assert not zc.sum_is_exact([2.0 ** 46, 2.0 ** 46 - 2.0 ** -7]) and zc.sum_is_exact([2.0 ** 45, -(2.0 ** 45) + 2.0 ** -7])
+    # the view cases: a window across the physical wrap, a crossing on either side of it, length - 1 crossings inside
+    for length, points in zc.VIEW_SHAPES:
+        e, cap, start = zc.train_case(length, length)        # asserts all of that
+        assert e.size * 127 < 2 ** 46 and cap == length + zc.PAD
+        nans = zc.nan_positions(length, points)
+        assert all(2 <= k < length for k in nans) and (length < 3 or nans)
+    # the push streams
+    for cap in zc.PUSH_CAPS:
+        for fmt in ("i8", "u8", "c64", "f32r"):
+            lengths, raw = zc.push_stream(fmt, cap)
+            assert sorted(lengths)[:41] == list(range(41)) and {cap - 1, cap, cap + 1, 3 * cap + 5} <= set(lengths)
+            re, im = zc.unpack(raw, fmt)
+            assert re.size == sum(lengths) and zc.db_spacing(re, im, zc.LOG_FLOOR) >= 0.1
+            assert np.all(re[1:] != re[:-1])
+            G = zc.GROUP[fmt]
+            pieces = zc.push_pieces(cap, lengths, G)
+            assert {p[0] for p in pieces} == {0, 1, 2, 3} and {p[2] for p in pieces} == set(range(G))
+            assert all(h + g * G + t == n and n <= cap for h, g, t, n in pieces)
+            assert set(range(1, G + 4)) <= {p[3] for p in pieces} and 0 in lengths
+            assert len(pieces) > len(lengths) - 1                 # pushes cut in two at the physical wrap
+            assert max(p[1] for p in pieces) > 256 // G or cap < 256   # a body of more than one workgroup
+            p = re.astype(np.float64) ** 2 + im.astype(np.float64) ** 2 + float(np.float32(zc.LOG_FLOOR))
+            assert p.min() >= 0.999e-12 and p.max() <= 32.0
+            for det in ("real", "mag", "db"):
+                e = zc.detect(re, im, det, zc.LOG_FLOOR, zc.OFFSET_DB)
+                assert np.all(np.isfinite(e)) and np.all(e[1:] != e[:-1]), (fmt, cap, det)
+    assert zc.db_spacing([1.0, 1.0], [0.0, 0.0], 0.0) == 0.0 and zc.db_spacing([1.0], [0.0], 0.0) == float("inf")
+    # the extreme samples hold what the suite says they hold
+    parts = zc.extreme_parts()
+    assert np.isnan(parts).sum() == 3 and np.isinf(parts).sum() == 2 and np.signbit(parts[1]) and parts[1] == 0
+    tiny = np.finfo(np.float32).tiny
+    with np.errstate(all="ignore"):
+        sq = parts * parts
+    assert ((np.abs(parts) > 0) & (np.abs(parts) < tiny)).sum() >= 4 and ((sq > 0) & (sq < tiny)).any() and np.isinf(sq[np.isfinite(parts)]).any()
+
+
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "core")), reason="the reference tree is not here")
 def test_live_differential_against_the_reference_class(tmp_path):
     """The generator run afresh against the reference's _process_zero_span_data: the same vectors as the committed ones."""

@@ -87,20 +87,25 @@ def view_plan(total, capacity, n_display, mode):
     return dict(held=held, base=base, length=n_display, free_start=total - n_display, search=search)
 
 
-def view(history, capacity, n_display, mode="free_run", level=0.0):
-    """(start, triggered, chunk) over the full detected history (absolute indices)."""
+def view(history, capacity, n_display, mode="free_run", level=0.0, origin=0):
+    """(start, triggered, chunk) over the detected history (absolute indices).  `origin` is the absolute index of
+    history[0]: a test that only knows the end of a long stream passes that end (at least everything the ring holds)
+    and where it begins; 0 means the full history."""
     e = np.asarray(history, dtype=F32)
-    plan = view_plan(e.size, capacity, n_display, mode)
+    origin = int(origin)
+    plan = view_plan(origin + e.size, capacity, n_display, mode)
+    if origin < 0 or plan["base"] < origin:
+        raise ValueError(f"origin={origin}: the history must reach back to base={plan['base']}")
     start, triggered = plan["free_start"], 0
     if plan["search"] is not None:
         ss, se = plan["search"]
-        seg = e[plan["base"] + ss: plan["base"] + se]
+        seg = e[plan["base"] - origin + ss: plan["base"] - origin + se]
         lv = F32(level)                          # numpy compares a float32 array with a Python float in float32
         hit = (seg[:-1] < lv) & (seg[1:] >= lv) if mode == "rise" else (seg[:-1] >= lv) & (seg[1:] < lv)
         where = np.flatnonzero(hit)
         if where.size:
             start, triggered = plan["base"] + ss + int(where[-1]) + 1, 1
-    return start, triggered, e[start:start + plan["length"]]
+    return start, triggered, e[start - origin:start - origin + plan["length"]]
 
 
 def cells(length, n_points):
@@ -135,3 +140,150 @@ def statistics(chunk, level):
     return dict(min=np.min(chunk), max=np.max(chunk), mean=float(np.sum(chunk, dtype=np.float64) / chunk.size),
                 n_at_or_above=int(np.count_nonzero(chunk >= lv)),
                 n_rise=int(np.count_nonzero((a < lv) & (b >= lv))), n_fall=int(np.count_nonzero((a >= lv) & (b < lv))))
+
+
+# ---------------------------------------------------------------------------------------------------- test inputs
+def sum_is_exact(values, unit=2.0 ** -7):
+    """True when every float64 sum over `values`, in any order and of any subset, is exact: all are integer multiples
+    of `unit` and the largest possible partial sum, in units, needs no more than 53 bits."""
+    v = np.asarray(values, dtype=np.float64) / unit
+    if v.size == 0:
+        return True
+    if not np.all(np.isfinite(v)) or not np.array_equal(v, np.rint(v)):
+        return False
+    return int(np.sum(np.abs(v).astype(np.int64))) < 2 ** 53      # int64: exact for any test-sized input
+
+
+def crossing_train(n, rng, first_above=False, unit=2.0 ** -7):
+    """n float32 values that alternate below / above the level 0.0 at every sample: multiples of `unit` with
+    magnitudes 1 .. 127 units drawn from rng, so that neighbours, cells and sums all tell samples apart."""
+    mag = rng.integers(1, 128, int(n)).astype(np.float64) * unit
+    sign = np.where((np.arange(int(n)) + (1 if first_above else 0)) % 2 == 1, 1.0, -1.0)
+    return (mag * sign).astype(F32)
+
+
+def crossings(values, level=0.0):
+    """(n_rise, n_fall) between neighbours, as `statistics` counts them."""
+    st = statistics(values, level)
+    return st["n_rise"], st["n_fall"]
+
+
+def db_spacing(re, im, log_floor):
+    """Smallest |difference| in dB between neighbouring samples of the float64 DB detector (inf for fewer than two)."""
+    d = detect64(re, im, "db", log_floor, 0.0)
+    return float(np.min(np.abs(np.diff(d)))) if d.size > 1 else float("inf")
+
+
+def spaced_samples(rng, n, fmt, log_floor=1e-12, min_db=0.1):
+    """n raw samples of one input format whose neighbours differ by at least `min_db` in the DB detector and are not
+    equal in Re x, with re^2 + im^2 + log_floor inside [1e-12, 32]: a sample stored one slot off cannot pass any of the
+    three detectors.  Returned in the layout `unpack` takes (interleaved bytes, complex64 or float32)."""
+    n = int(n)
+
+    def draw(k):
+        if fmt == "i8":
+            return rng.integers(-128, 128, (k, 2)).astype(np.int8)
+        if fmt == "u8":
+            return rng.integers(0, 256, (k, 2)).astype(np.uint8)
+        amp = (10.0 ** rng.uniform(-3.0, 0.3, k)) * rng.choice([-1.0, 1.0], k)
+        if fmt == "c64":
+            return (amp * np.exp(1j * rng.uniform(0, 2 * np.pi, k))).astype(np.complex64)
+        return amp.astype(F32)
+
+    a = draw(n)
+    for _ in range(200):
+        re, im = unpack(a, fmt)
+        d = detect64(re, im, "db", log_floor, 0.0)
+        bad = np.flatnonzero((np.abs(np.diff(d)) < min_db) | (re[1:] == re[:-1])) + 1
+        if bad.size == 0:
+            break
+        a[bad] = draw(bad.size)
+    else:
+        raise RuntimeError("no spaced sequence found")
+    return a.reshape(-1)
+
+
+# ---------------------------------------------------------------------------------------------------- the shapes suite
+# Inputs of tests/test_gpu_zero_span_shapes.py; tests/test_zero_span_host.py asserts without a GPU that they discriminate.
+GROUP = {"i8": 8, "u8": 8, "c64": 4, "f32r": 4}                  # samples per lane of the push kernel's body
+LOG_FLOOR, OFFSET_DB = 1e-12, -12.5
+PUSH_CAPS = (61, 1021)                                           # not multiples of 4: the ring position takes every residue
+
+
+def push_lengths(cap):
+    rng = np.random.default_rng(cap)
+    lengths = [int(v) for v in rng.permutation(41)]
+    for at, n in ((7, cap - 1), (16, cap), (25, cap + 1), (34, 3 * cap + 5)):
+        lengths.insert(at, n)
+    return lengths
+
+
+def push_pieces(cap, lengths, group):
+    """(head, groups, tail, n) of every launch the host makes for this stream of pushes (tdsa_capi_zspan.cpp)."""
+    out, total = [], 0
+    for n in lengths:
+        skip = max(0, n - cap)
+        t, left = total + skip, n - skip
+        while left > 0:
+            pos = t % cap
+            piece = min(left, cap - pos)
+            head = min((4 - pos % 4) & 3, piece)
+            groups = (piece - head) // group
+            out.append((head, groups, piece - head - groups * group, piece))
+            t, left = t + piece, left - piece
+        total += n
+    return out
+
+
+def push_stream(fmt, cap):
+    lengths = push_lengths(cap)
+    raw = spaced_samples(np.random.default_rng(cap + len(fmt)), sum(lengths), fmt, LOG_FLOOR)
+    return lengths, raw
+
+
+def extreme_parts():
+    bits = np.array([0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x000ABCDE, 0x007FFFFF, 0x00800000,   # zeros, denormals
+                     0x1E3CE508,                 # 1e-20: the square is a denormal
+                     0x0DA24260, 0x1A000000,     # 1e-30: the square underflows to 0; 2^-75: exactly the smallest denormal / 2
+                     0x5F000000, 0xDF000000,     # +-2^63: one square fits, the sum of two is 2^127
+                     0x5F800000, 0x60AD78EC,     # 2^64 and 1e20: the square overflows
+                     0x3F800000, 0xBFC00000, 0x7F7FFFFF, 0x7F800000, 0xFF800000,
+                     0x7FC00000, 0xFFC12345, 0x7FA00001], dtype=np.uint32)   # NaNs with payloads, one signalling
+    return bits.view(F32)
+
+
+PAD = 64                                                          # the ring is the window and this many samples
+
+
+def train_case(length, seed):
+    """(history, cap, start): an alternating train around level 0.0 in a ring just large enough; the rise-triggered
+    window of `length` starts a few samples before the physical end of the ring and ends before the history does."""
+    cap = length + PAD
+    total = cap + (length - 3) % cap
+    rng = np.random.default_rng(seed)
+    e = crossing_train(total, rng)
+    start, trig, chunk = view(e, cap, length, "rise", 0.0)
+    assert trig == 1 and chunk.size == length and 1 <= total - (start + length) <= 2
+    assert cap - 8 <= start % cap < cap and (length < 8 or start % cap + length > cap)   # laid across the physical wrap
+    assert sum_is_exact(e) and sum(crossings(chunk)) == length - 1
+    assert (e[start - 1] < 0) != (e[start] < 0) and (e[start + length - 1] < 0) != (e[start + length] < 0)
+    return e, cap, start
+
+
+def nan_positions(length, points):
+    """Chunk indices for NaNs: first and last sample of a cell and of a workgroup's share (never 0 or 1, which would
+    move the trigger)."""
+    if points:
+        P, b = cells(length, points)
+        pos = {b[c] for c in (1, P // 2, P - 1) if c < P} | {b[c + 1] - 1 for c in (0, P // 2, P - 2) if 0 <= c < P}
+        team = 256 if length // P >= 1024 else 64
+        pos |= {b[P // 2] + team - 1, b[P // 2] + team}          # a lane's second sample of a long cell
+    else:
+        stride = min(1024, -(-length // 1024)) * 256
+        pos = {255, 256, 1023, 1024, stride - 1, stride, length - 1}
+    return sorted(k for k in pos if 2 <= k < length)
+
+
+VIEW_SHAPES = [(1024 * 3 - 1, 3), (1024 * 3, 3), (1024 * 3 + 1, 3), (2 * 16384 + 5, 16384), (2 * 16384 + 5, 4097),
+               (1025 * 1024 + 7, 1025), (1024 * 1024 + 3, None), (4 * 256 * 3 + 1, None),
+               (1, 1), (2, 2), (3, 2), (64, 1), (65, 1), (255, 4), (257, 4), (5, 7), (100, 16384), (3, None)]

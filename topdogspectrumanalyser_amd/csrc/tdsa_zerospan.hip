@@ -48,7 +48,8 @@ template <int DET>
 __device__ inline float detect(float re, float im, float log_floor, float offset_db) {
   if (DET == TDSA_ZS_DET_REAL) return re;
   const float p = re * re + im * im;
-  if (DET == TDSA_ZS_DET_MAG) return __fsqrt_rn(p);
+  // correctly rounded while hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt holds; __fsqrt_rn is the 1 ulp root
+  if (DET == TDSA_ZS_DET_MAG) return __builtin_sqrtf(p);
   return log2f(p + log_floor) * kLog2ToDb + offset_db;
 }
 
