@@ -278,6 +278,15 @@ int tdsa_set_overlap(tdsa_plan p, int n_streams);
  *                      with -1 (dB padded with NaN).  n_bins <= 16384 (the row lives in LDS).  Equal-valued
  *                      candidates are visited larger index first (the reference's order for ties is that
  *                      of np.argsort's unstable sort).
+ *                      min_excursion_db IS a float32: the contract is the reference called with that float32 value
+ *                      (float(np.float32(x))), in its first, float32 comparison and in its second, float64 one - a
+ *                      caller's 6.3 means 6.30000019...; NaN is TDSA_ERR_ARG.  min_sep_bins < 1 means "no separation
+ *                      rule" (the reference's `abs(a - b) < min_sep_bins` then never holds), the same as 1; any value
+ *                      from n_bins up means the same as n_bins.  A NaN between two peaks never rejects (the
+ *                      reference's np.min of the valley is NaN and both of its comparisons are false); a NaN is no
+ *                      candidate and takes its two neighbours out of the candidates.  n_peaks outside [1, 8] and
+ *                      n_bins outside [1, 16384] are TDSA_ERR_ARG; peak_db_host may be NULL; n_rows = 0 returns
+ *                      TDSA_OK and writes nothing.
  * tdsa_rows_marker_peaks  MarkerManager.snap_to_peak / snap_to_next_peak (core/marker_manager.py:74-127): per row
  *                      scipy.signal.find_peaks(levels, height=, prominence=, distance=) - local maxima (a flat top
  *                      counts once, at its middle; never the first / last sample), height >= `height`, from the
@@ -291,7 +300,11 @@ int tdsa_set_overlap(tdsa_plan p, int n_streams);
  *                      first max_list peaks in bin order (padded with -1) and their prominences (NaN).  Any
  *                      output pointer may be NULL.  n_bins <= 16384.  Two EQUAL peaks closer than `distance`:
  *                      the larger bin is kept (scipy orders them by np.argsort, whose default sort is not stable:
- *                      the reference's choice between them depends on the CPU's sorting network). */
+ *                      the reference's choice between them depends on the CPU's sorting network).  `distance` from
+ *                      n_bins up means the same as n_bins.
+ *                      rows_dev of both calls must be aligned to a float (4 bytes; TDSA_ERR_ARG otherwise) and to no
+ *                      more: the marker search takes 16-byte loads only where n_bins % 4 == 0 AND rows_dev is 16-byte
+ *                      aligned, float loads otherwise, with the same results. */
 int tdsa_rows_stats(tdsa_plan p, const float* rows_dev, int n_rows, int n_bins, int band_lo, int band_hi,
                     double bin_width, float* peak_db_host, int32_t* peak_bin_host, double* band_db_host);
 int tdsa_rows_top_peaks(tdsa_plan p, const float* rows_dev, int n_rows, int n_bins, int n_peaks, int min_sep_bins,

@@ -38,16 +38,18 @@ def _accepts(power: np.ndarray, cand: int, chosen: List[int], min_sep_bins: int,
 
 
 def find_top_peaks(freq_bins: np.ndarray, power: np.ndarray, n: int = 5, min_sep_bins: int = 10,
-                   min_excursion_db: float = 10.0) -> List[Tuple[float, float]]:
+                   min_excursion_db: float = 10.0, kind: Optional[str] = None) -> List[Tuple[float, float]]:
     """display_data_processor.py:432-471: strict interior local maxima visited from the strongest down
-    (order = reversed np.argsort, as there), greedily accepted by `_accepts`, at most n of them."""
+    (order = reversed np.argsort, as there), greedily accepted by `_accepts`, at most n of them.
+    kind = "stable" makes the order between EQUAL candidates defined: the larger index first, the device's rule
+    (the reference's default sort leaves it to the sorting network)."""
     if len(power) < 3:
         return []
     mid = power[1:-1]
     cands = np.flatnonzero((mid > power[:-2]) & (mid > power[2:])) + 1
     if cands.size == 0:
         return []
-    order = cands[np.argsort(power[cands])[::-1]]
+    order = cands[np.argsort(power[cands], kind=kind)[::-1]]
     chosen: List[int] = []
     for c in order:
         if len(chosen) >= n:

@@ -65,7 +65,10 @@ def rows_stats(engine: SpectrumEngine, rows_dev: int, n_rows: int, n_bins: Optio
 def rows_top_peaks(engine: SpectrumEngine, rows_dev: int, n_rows: int, n_bins: Optional[int] = None, n: int = 5,
                    min_sep_bins: Optional[int] = None, min_excursion_db: float = 10.0):
     """(bins[n_rows, n] i32 padded with -1, db[n_rows, n] f32 padded with NaN); min_sep_bins defaults to the
-    reference's max(10, n_bins // 50) (display_data_processor.py:416)."""
+    reference's max(10, n_bins // 50) (display_data_processor.py:416); below 1 it means "no separation rule".
+    min_excursion_db is a float32 on the device: the result is the reference's for float(np.float32(min_excursion_db))
+    (6.3 means 6.30000019...); NaN is refused.  A NaN between two peaks never rejects, as in the reference.  Equal
+    candidates are visited larger bin first."""
     nb = int(n_bins or engine.nfft)
     sep = max(10, nb // 50) if min_sep_bins is None else int(min_sep_bins)
     bins = np.empty((n_rows, n), dtype=np.int32)

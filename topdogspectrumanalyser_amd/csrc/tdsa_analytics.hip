@@ -13,6 +13,7 @@
 //   waterfall_plan_kernel / waterfall_scatter_kernel
 #include "tdsa_fft.hpp"        // static_for
 #include "tdsa_kernels.hpp"
+#include "tdsa_rows_align.hpp"
 
 #include <math.h>
 
@@ -205,7 +206,7 @@ __global__ void __launch_bounds__(1 << LOG2T) __attribute__((amdgpu_waves_per_eu
     const int i = tid + T * k;
     if (T * k < n) {                       // (uniform)
       if (i < n) row[i] = vals[k];
-      float mn = row_min(vals[k]);
+      float mn = row_min(vals[k] != vals[k] ? -INFINITY : vals[k]);   // a NaN is the lowest floor there is (see the valley test)
       mn = fminf(mn, dpp_f<0x142, 0xa>(mn));          // row_bcast:15: lanes 31 and 63 hold the minimum of their 32 bins
       if ((lane & 31) == 31 && (i & ~31) < n) s_bmin[i >> 5] = mn;
     }
@@ -279,8 +280,8 @@ __global__ void __launch_bounds__(1 << LOG2T) __attribute__((amdgpu_waves_per_eu
       const float bm = s_bmin[b];
 #pragma unroll
       for (int k = 0; k < kMaxPeaks; ++k) {
-        if (k < nsel && b > lo[k] && b < hi[k]) vmin[k] = fminf(vmin[k], bm);   // (a NaN in the range would make np.min
-      }                                                                          //  NaN and never reject; rows here carry none)
+        if (k < nsel && b > lo[k] && b < hi[k]) vmin[k] = fminf(vmin[k], bm);
+      }
     }
 #pragma unroll
     for (int k = 0; k < kMaxPeaks; ++k) {
@@ -296,7 +297,11 @@ __global__ void __launch_bounds__(1 << LOG2T) __attribute__((amdgpu_waves_per_eu
       // from it on (the part of a valley that lies in this block, whichever side the accepted peak is on); an accepted peak
       // keeps the two minima it had as a candidate
       const int cidx = (cur & ~31) + (lane & 31);
-      const float cv = cidx < n ? row[cidx] : INFINITY;
+      // a NaN between the two peaks makes the reference's np.min NaN and both of its comparisons false: the valley never
+      // rejects.  A floor of -inf does the same (x - (-inf) = +inf is below no excursion), so a NaN counts as -inf in every
+      // minimum: here (the two end blocks, the same-block fold) and in s_bmin
+      const float craw = cidx < n ? row[cidx] : INFINITY;
+      const float cv = craw != craw ? -INFINITY : craw;
       float part = (lane < 32 ? cidx <= cur : cidx >= cur) ? cv : INFINITY;
       part = fminf(part, dpp_f<0xB1, 0xf>(part));
       part = fminf(part, dpp_f<0x4E, 0xf>(part));
@@ -442,12 +447,27 @@ __device__ __forceinline__ bool marker_prominent(const float* row, const MarkerL
   const double dxp = (double)xp;
   auto passes = [&](float v) { return dxp - (double)v >= prominence; };
   float thr = (float)(dxp - prominence);
+  if (thr != thr) thr = xp;                                  // inf - inf (a +inf peak, prominence +inf): every float below the peak passes
   if (!passes(thr)) thr = nextafterf(thr, -INFINITY);
   if (!passes(thr)) thr = nextafterf(thr, -INFINITY);
   if (!passes(thr)) return false;                            // (a NaN threshold, or none of the floats around it: nothing can pass)
   for (int k = 0; k < 2; ++k) {
     const float up = nextafterf(thr, INFINITY);
     if (up != thr && passes(up)) thr = up;
+  }
+  // Where peak and threshold cancel (a peak of 6.0, prominence 6.0: thr = 0) the floats around thr lie far closer than the
+  // float64 grid at the peak, and (double)xp - (double)v rounds back onto xp for every |v| below half a step of THAT grid:
+  // the largest float that passes is 2^-51 there, not the second float above zero.  Rare: bisect the floats in their order
+  // between thr (passes) and the peak (xp - xp = 0 fails, prominence > 0).
+  if (passes(nextafterf(thr, INFINITY))) {
+    auto key = [](float f) { const int u = __float_as_int(f); return (long long)(u >= 0 ? u : (int)0x80000000 - u); };
+    auto val = [](long long k) { return __int_as_float(k >= 0 ? (int)k : (int)(0x80000000u - (unsigned)k)); };
+    long long lo = key(thr), hi = key(xp);
+    while (hi - lo > 1) {
+      const long long mid = lo + (hi - lo) / 2;
+      if (passes(val(mid))) lo = mid; else hi = mid;
+    }
+    thr = val(lo);
   }
   // state of a side: 0 walking, 1 passed, 2 failed
   int st = 0, i = p - 1;
@@ -510,7 +530,7 @@ __device__ __forceinline__ bool marker_prominent(const float* row, const MarkerL
 
 __global__ void __launch_bounds__(kMarkThreads) marker_peaks_kernel(const float* __restrict__ rows, int n, double height,
                                                                     double prominence, int distance, int current_idx,
-                                                                    int max_list, int* out_count, int* out_snap,
+                                                                    int max_list, int vec, int* out_count, int* out_snap,
                                                                     int* out_next, int* out_bins, double* out_prom) {
   extern __shared__ __attribute__((aligned(16))) float mark_smem[];
   float* row = mark_smem;                                        // [n]
@@ -520,7 +540,7 @@ __global__ void __launch_bounds__(kMarkThreads) marker_peaks_kernel(const float*
   const int nw = (n + 31) >> 5, nw2 = (n + 1023) >> 10;
 
   // load + block extrema of 32: a half-wave holds one block
-  if ((n & 3) == 0) {
+  if (vec) {                                                      // (the launcher: n % 4 == 0 and a 16-byte aligned base)
     // four samples per lane, every load of the row in flight before the first is used; eight lanes hold a block of 32
     typedef float f4 __attribute__((ext_vector_type(4)));
     const f4* src4 = reinterpret_cast<const f4*>(src);
@@ -604,7 +624,8 @@ __global__ void __launch_bounds__(kMarkThreads) marker_peaks_kernel(const float*
     if (flat) {
       int a = i + 1;
       while (a < n - 1) {
-        if ((a & 31) == 0 && a + 32 < n - 1 && L.bmax1[a >> 5] == v && L.bmin1[a >> 5] == v) { a += 32; continue; }
+        // (bmin1 skips a NaN and bmax1 counts it as +inf: a block of +inf with a NaN in it looks flat, so +inf tops walk bin by bin)
+        if ((a & 31) == 0 && a + 32 < n - 1 && v != INFINITY && L.bmax1[a >> 5] == v && L.bmin1[a >> 5] == v) { a += 32; continue; }
         if (row[a] != v) break;
         ++a;
       }
@@ -1139,7 +1160,8 @@ hipError_t launch_marker_peaks(const float* rows, int n_rows, int n, double heig
   static std::atomic<unsigned long long> attr_done{0};
   const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(marker_peaks_kernel), 64 * 1024, attr_done);
   if (e != hipSuccess) return e;
-  marker_peaks_kernel<<<n_rows, kMarkThreads, lds, s>>>(rows, n, height, prominence, distance, current_idx, max_list,
+  const int vec = rows_take_vec16(rows, n) ? 1 : 0;           // 16-byte loads only where every row starts on 16 bytes
+  marker_peaks_kernel<<<n_rows, kMarkThreads, lds, s>>>(rows, n, height, prominence, distance, current_idx, max_list, vec,
                                                         out_count, out_snap, out_next, out_bins, out_prom);
   return hipGetLastError();
 }

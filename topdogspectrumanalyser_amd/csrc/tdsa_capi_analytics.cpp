@@ -143,6 +143,10 @@ int tdsa_rows_top_peaks(tdsa_plan p, const float* rows_dev, int n_rows, int n_bi
   if (!rows_dev || !peak_bins_host || n_rows < 0) return fail(TDSA_ERR_ARG, "null / negative argument");
   if (n_peaks < 1 || n_peaks > 8) return fail(TDSA_ERR_ARG, "n_peaks=%d outside [1, 8]", n_peaks);
   if (n_bins < 1 || n_bins > 16384) return fail(TDSA_ERR_ARG, "n_bins=%d outside [1, 16384] (row must fit the LDS)", n_bins);
+  if (reinterpret_cast<uintptr_t>(rows_dev) % sizeof(float)) return fail(TDSA_ERR_ARG, "rows_dev %p is not aligned to a float", (const void*)rows_dev);
+  if (min_excursion_db != min_excursion_db) return fail(TDSA_ERR_ARG, "NaN min_excursion_db");
+  // no two bins of a row are n_bins apart: every separation from n_bins up means the same, and below 1 there is no rule
+  min_sep_bins = min_sep_bins < 1 ? 1 : (min_sep_bins > n_bins ? n_bins : min_sep_bins);
   HIPCHK(hipSetDevice(p->device));
   JOIN(p);
   const size_t cnt = size_t(n_rows) * n_peaks;
@@ -168,6 +172,8 @@ int tdsa_rows_marker_peaks(tdsa_plan p, const float* rows_dev, int n_rows, int n
   if (distance < 1) return fail(TDSA_ERR_ARG, "distance=%d (scipy: `distance` must be greater or equal to 1)", distance);
   if (max_list < 0 || (max_list > 0 && !peak_bins_host)) return fail(TDSA_ERR_ARG, "max_list=%d without a list buffer", max_list);
   if (height != height || prominence != prominence) return fail(TDSA_ERR_ARG, "NaN height / prominence");
+  if (reinterpret_cast<uintptr_t>(rows_dev) % sizeof(float)) return fail(TDSA_ERR_ARG, "rows_dev %p is not aligned to a float", (const void*)rows_dev);
+  if (distance > n_bins) distance = n_bins;                  // (no two peaks are n_bins apart: the same rule, and no overflow in the reach)
   HIPCHK(hipSetDevice(p->device));
   JOIN(p);
   const size_t cnt = size_t(n_rows) * max_list, rb = size_t(n_rows) * sizeof(int);
