@@ -480,6 +480,53 @@ int tdsa_demod_reset_meas(tdsa_demod d);
 int tdsa_demod_timer_begin(tdsa_demod d);
 int tdsa_demod_timer_end(tdsa_demod d, float* elapsed_ms);
 
+/* -------- symbol recovery for EVM: timing, carrier, one sample per symbol ------------------
+ * Feed-forward and per segment: segment s is x[s * hop + j], j < seg_len, complex64, analysed on its own; the handle
+ * keeps no state between calls.  Positions are 32.32 fixed point: step = round(sps 2^32) (4 <= sps <= 64), nu =
+ * round(2^32 / sps) the symbol clock's phase step per sample.
+ *   1 timing    P = sum |x_j|^2, C = sum |x_j|^2 exp(-2 pi i (j nu mod 2^32) / 2^32); a = arg C / pi ((0, 0): 0),
+ *               t = -a / 2 (+ 1 if negative), delta_fx = floor(t step), + step if below 2^32.  TDSA_SYMSYNC_FIXED: the
+ *               caller's delta_fx instead, 2^32 <= delta_fx < step + 2^32.
+ *   2 resample  K = floor((seg_len - 4) 2^32 / step) - 1 symbols (2 .. 4096); pos = delta_fx + k step, i = pos >> 32,
+ *               mu = the top 24 bits of the fraction; y_k = the cubic Lagrange interpolation of x[i-1 .. i+2] at mu.
+ *   3 carrier   (order M = 2, 4, 8) z = y^M, Z = DFT_G of z zero padded, G = 2 * 2^ceil(log2 K); g = the lowest index of
+ *               the largest |Z|^2; f = g / G (less 1 from G / 2 up) + arg(S2 conj S1) / (2 pi H), S1, S2 the sums over
+ *               the first and second H = K / 2 of z_k exp(-2 pi i k g / G); step_f = round(f / M 2^32) mod 2^32;
+ *               theta_fx = round((arg sum z_k exp(-2 pi i k M step_f / 2^32) - ref_arg) / (2 pi M) 2^32) mod 2^32.
+ *   4 derotate  sym_k = y_k exp(-2 pi i ((theta_fx + k step_f) mod 2^32) / 2^32); order 0: sym = y.
+ * Symbols: complex64, segment s at sym + s * out_stride, the first K of each row are written.  raw (or NULL): the same
+ * shape, y.  One record per segment.  A segment whose P or C is not finite has TDSA_SYMSYNC_NONFINITE set, NaN symbols
+ * and an otherwise zero record; no other segment is touched.  TDSA_SYMSYNC_NO_CARRIER: the transform's power is not
+ * finite, step_f = theta_fx = 0.  A segment's results depend on its samples alone: not on n_seg, its place or the entry
+ * point.  _process: host memory through pinned staging, n_samples and n_seg * seg_len <= max_host_samples.
+ * _process_dev: device memory, on plan p's stream (ordered after its work, and its later work after this) or on the
+ * handle's own for p = NULL; returns when the records are in records_host.  _symbols_per_segment needs no device.
+ * Argument errors are reported before any HIP call. */
+#define TDSA_SYMSYNC_AUTO 0
+#define TDSA_SYMSYNC_FIXED 1
+#define TDSA_SYMSYNC_NONFINITE 1u
+#define TDSA_SYMSYNC_NO_CARRIER 2u
+typedef struct tdsa_symsync_record {
+  uint64_t delta_fx;           /* the first symbol's position in the segment, 32.32 samples */
+  float c_re, c_im, p;         /* the symbol-rate line of |x|^2 and the segment's energy */
+  int32_t g;                   /* the carrier transform's peak bin, 0 .. G - 1 */
+  uint32_t step_f, theta_fx;   /* carrier per symbol and phase, in turns / 2^32 */
+  float peak, mean;            /* |Z_g|^2 and the mean of |Z|^2: the carrier lock's quality */
+  uint32_t flags, reserved;
+} tdsa_symsync_record;
+typedef struct tdsa_symsync_s* tdsa_symsync;
+int tdsa_symsync_create(int device_id, size_t max_host_samples, tdsa_symsync* out);
+int tdsa_symsync_destroy(tdsa_symsync h);
+int tdsa_symsync_configure(tdsa_symsync h, uint64_t step, uint32_t nu, int order, double ref_arg, int timing_mode,
+                           uint64_t delta_fx);
+int tdsa_symsync_process(tdsa_symsync h, const void* in_host, size_t n_samples, size_t seg_len, size_t hop, int n_seg,
+                         void* sym_host, size_t out_stride, void* raw_host, tdsa_symsync_record* records_host);
+int tdsa_symsync_process_dev(tdsa_symsync h, tdsa_plan p, const void* in_dev, size_t seg_len, size_t hop, int n_seg,
+                             void* sym_dev, size_t out_stride, void* raw_dev, tdsa_symsync_record* records_host);
+int tdsa_symsync_symbols_per_segment(uint64_t step, size_t seg_len, int* K);
+int tdsa_symsync_timer_begin(tdsa_symsync h);
+int tdsa_symsync_timer_end(tdsa_symsync h, float* elapsed_ms);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

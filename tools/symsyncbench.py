@@ -1,0 +1,184 @@
+#!/usr/bin/env python3
+"""Timing of the symbol recovery.
+
+  copy     the box's device-to-device copy rate (1 GiB, torch), which the memory floor is stated against
+  tick     one GUI tick: 16 384 complex64 samples at 4 samples per symbol as one segment (K = 4094, a 8192-point carrier
+           transform), qpsk, SymbolSync.process_device with the samples and the symbols in HBM
+  second   a C3-shaped second: 20e6 complex64 samples through DownConverter(D = 2, root-raised-cosine taps) leave 10e6 in
+           HBM; analysed as 2441 segments of 4096 (K = 1022 each) in one call, next to its memory floor: 8 bytes read
+           per sample and 8 K bytes written per segment at the copy rate
+  numpy    for scale: the float64 contract (tests/symsync_contract.py) on the tick's segment on one host core
+
+Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per device figure:
+warm-up calls, then the median of `--reps` (at least 20) single calls, each between device events on the handle's
+stream; a call ends when the segments' records are in host memory, so the figure includes that copy and wait.
+
+    python tools/symsyncbench.py [--out profiles/symsyncbench.txt] [--reps 20]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+SPS = 4
+TICK = 16384
+N_SEC = 20_000_000
+D = 2
+SEG = 4096
+STEPS = ["copy", "tick", "second", "numpy"]
+LIMIT_S = 240
+
+
+def median_us(h, f, warm, reps):
+    for _ in range(warm):
+        f()
+    t = []
+    for _ in range(reps):
+        h.timer_begin()
+        f()
+        t.append(h.timer_end() * 1e3)
+    return float(np.median(t)), float(np.min(t)), float(np.max(t))
+
+
+def signal(n, sps):
+    """A qpsk stream through a rectangular pulse with a carrier, plus noise: cheap to make at 20e6 samples, and the
+    kernel's work does not depend on the data."""
+    rng = np.random.default_rng(4)
+    sym = ((2 * rng.integers(0, 2, n // sps + 1) - 1) + 1j * (2 * rng.integers(0, 2, n // sps + 1) - 1)) / np.sqrt(2.0)
+    x = np.repeat(sym, sps)[:n] * np.exp(1j * 0.002 * np.arange(n))
+    x += 0.01 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    return x.astype(np.complex64)
+
+
+def step_copy(args):
+    import torch
+    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    y = torch.empty_like(x)
+    x.fill_(1.0)
+    for _ in range(3):
+        y.copy_(x)
+    t = []
+    for _ in range(args.reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        y.copy_(x)
+        b.record()
+        b.synchronize()
+        t.append(a.elapsed_time(b) * 1e-3)
+    moved = 2 * x.numel() * 4
+    return dict(copy_bps=moved / float(np.median(t)), text=[
+        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
+
+
+def step_tick(args):
+    from topdogspectrumanalyser_amd import SymbolSync, _native as nat
+    x = signal(TICK, SPS)
+    with SymbolSync(SPS, "qpsk") as s:
+        K = s.symbols_per_segment(TICK)
+        d_x, d_s = nat._dev_alloc(0, x.nbytes), nat._dev_alloc(0, 8 * K)
+        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_x, x.ctypes.data_as(C.c_void_p), x.nbytes))
+        us, lo, hi = median_us(s, lambda: s.process_device(None, d_x.value, TICK, TICK, 1, d_s.value, K), args.warm, args.reps)
+        t0 = time.perf_counter()
+        for _ in range(args.reps):
+            s.process(x, TICK)
+        host_us = (time.perf_counter() - t0) / args.reps * 1e6
+        for p in (d_x, d_s):
+            nat.lib.tdsa_dev_free(0, p)
+    return dict(text=[
+        f"tick: {TICK} samples at {SPS} samples per symbol, one segment, K = {K}, qpsk: {us:8.1f} us (min {lo:.1f}, max {hi:.1f}) "
+        f"in device memory; from and to host memory (SymbolSync.process, wall clock, mean of {args.reps}) {host_us:8.1f} us"])
+
+
+def step_second(args):
+    from topdogspectrumanalyser_amd import DownConverter, SpectrumEngine, SymbolSync, _native as nat
+    from topdogspectrumanalyser_amd.symbols import rrc_taps
+    x = signal(N_SEC, SPS * D)
+    ny = N_SEC // D
+    n_seg = ny // SEG
+    d_x, d_y = nat._dev_alloc(0, x.nbytes), nat._dev_alloc(0, 8 * (ny + 8))
+    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_x, x.ctypes.data_as(C.c_void_p), x.nbytes))
+    with SpectrumEngine(64) as eng, DownConverter(D, 20e6, taps=rrc_taps(SPS * D, 0.35, 4)) as ddc, SymbolSync(SPS, "qpsk") as s:
+        K = s.symbols_per_segment(SEG)
+        d_s = nat._dev_alloc(0, 8 * K * n_seg)
+        assert ddc.process_device(eng, nat.IN_C64, d_x.value, N_SEC, d_y.value) == ny
+        eng.synchronize()
+        us, lo, hi = median_us(s, lambda: s.process_device(None, d_y.value, SEG, SEG, n_seg, d_s.value, K), args.warm, args.reps)
+        r = s.process_device(None, d_y.value, SEG, SEG, n_seg, d_s.value, K)
+    floor = (8.0 * n_seg * SEG + 8.0 * K * n_seg) / args.copy_bps * 1e6 if args.copy_bps else float("nan")
+    for p in (d_x, d_y, d_s):
+        nat.lib.tdsa_dev_free(0, p)
+    return dict(text=[
+        f"second: {N_SEC} samples through DownConverter(D = {D}, RRC) -> {ny} in HBM, {n_seg} segments of {SEG}, K = {K}: "
+        f"{us:9.1f} us (min {lo:.1f}, max {hi:.1f}); memory floor {floor:8.1f} us (8 bytes read per sample, 8 K written per "
+        f"segment at the copy rate) = {100 * floor / us:5.1f}% of the time; median timing quality {np.median(r.timing_quality):.3f}, "
+        f"median lock {np.median(r.lock):.0f}, {int(np.count_nonzero(r.flags))} segments flagged"])
+
+
+def step_numpy(args):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import symsync_contract as sc
+    x = signal(TICK, SPS).astype(np.complex128)
+    ref = sc.reference_phase(sc.points("qpsk"), 4)
+    sc.recover(x, SPS, 4, ref)
+    t0 = time.perf_counter()
+    for _ in range(5):
+        sc.recover(x, SPS, 4, ref)
+    dt = (time.perf_counter() - t0) / 5
+    return dict(text=[f"numpy: the float64 contract on the tick's segment on one host core: {dt * 1e3:.1f} ms"])
+
+
+def run_step(args):
+    return dict(copy=step_copy, tick=step_tick, second=step_second, numpy=step_numpy)[args.step](args)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warm", type=int, default=3)
+    ap.add_argument("--step", choices=STEPS, default=None)
+    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
+    args = ap.parse_args()
+    args.reps = max(args.reps, 20)
+    if args.step:
+        print("RESULT " + json.dumps(run_step(args)), flush=True)
+        return
+    lines = [f"symbol recovery (tdsa_symsync_*): every device figure is the median of {args.reps} single calls after warm-up "
+             f"calls, between device events on the handle's stream, records read back included"]
+    print(lines[0], flush=True)
+    copy_bps = 0.0
+    for step in STEPS:
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
+               "--copy-bps", repr(copy_bps)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
+        except subprocess.TimeoutExpired:
+            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
+            print(lines[-1], flush=True)
+            break
+        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+        if r.returncode != 0 or not res:
+            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
+            print(lines[-1], flush=True)
+            break
+        res = json.loads(res[-1][7:])
+        copy_bps = res.get("copy_bps", copy_bps)
+        for ln in res["text"]:
+            print(ln, flush=True)
+            lines.append(ln)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -14,6 +14,7 @@ from .analytics import Constellation, ConstellationView  # noqa: F401
 from .zoom import DownConverter, ZoomSpectrum, design_decimator  # noqa: F401
 from .channelizer import Channelizer, ChannelSpectra  # noqa: F401
 from .demod import Demodulator, deemphasis_pole, design_audio_filter  # noqa: F401
+from .symbols import SymbolSync, rrc_taps  # noqa: F401
 from .zerospan import ZeroSpan, view_plan  # noqa: F401
 from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401

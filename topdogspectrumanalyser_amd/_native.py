@@ -23,6 +23,8 @@ SWEEP_INTERP, SWEEP_PEAK = 0, 1
 CHAN_BRANCHES = 1
 DEMOD_FM, DEMOD_AM = 0, 1
 DEMOD_POLE_OFF, DEMOD_POLE_LOWPASS, DEMOD_POLE_HIGHPASS = 0, 1, 2
+SYMSYNC_AUTO, SYMSYNC_FIXED = 0, 1
+SYMSYNC_NONFINITE, SYMSYNC_NO_CARRIER = 1, 2
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
 ZS_FREE_RUN, ZS_RISE, ZS_FALL = 0, 1, 2
 ZS_COL_MINMAX, ZS_COL_SAMPLE, ZS_COL_MEAN = 0, 1, 2
@@ -148,6 +150,14 @@ _SIGNATURES = {
     "tdsa_demod_reset_meas": (C.c_int, [_P]),
     "tdsa_demod_timer_begin": (C.c_int, [_P]),
     "tdsa_demod_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_symsync_create": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_symsync_destroy": (C.c_int, [_P]),
+    "tdsa_symsync_configure": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_int, C.c_double, C.c_int, C.c_uint64]),
+    "tdsa_symsync_process": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, _P, _P]),
+    "tdsa_symsync_process_dev": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, _P, _P]),
+    "tdsa_symsync_symbols_per_segment": (C.c_int, [C.c_uint64, C.c_size_t, C.POINTER(C.c_int)]),
+    "tdsa_symsync_timer_begin": (C.c_int, [_P]),
+    "tdsa_symsync_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),
