@@ -527,6 +527,57 @@ int tdsa_symsync_symbols_per_segment(uint64_t step, size_t seg_len, int* K);
 int tdsa_symsync_timer_begin(tdsa_symsync h);
 int tdsa_symsync_timer_end(tdsa_symsync h, float* elapsed_ms);
 
+/* -------- signal detection: noise floor, emissions, occupancy ----------------------------
+ * Rows are [n_rows][n_bins] float32 dB rows, 1 <= n_bins <= 16384, the input of tdsa_rows_top_peaks.  Per row, with
+ * seg = row[bin_lo .. bin_hi] (inclusive) and n_eff its length:
+ *   floor      np.sort(seg)[rank]: NaNs sort last, -inf and +inf take their places; compared by value (+0 / -0).  A NaN
+ *              floor flags the row (TDSA_DETECT_NAN_FLOOR): thr is NaN, n_over = n_found = 0, no occupancy.
+ *   threshold  thr = floor + margin_db, one float32 addition; a bin is set when row[i] > thr (a NaN never is); n_over
+ *              counts the set bins.
+ *   runs       consecutive set bins more than max_gap + 1 apart end one run and begin the next (gaps of up to max_gap
+ *              bins are bridged); then runs with stop - start + 1 < min_width are dropped.  n_found counts the runs
+ *              kept and may exceed max_signals; the first max_signals in bin order get records, the rest of a row's
+ *              records are start = stop = peak_bin = x_lo = x_hi = -1, peak_db = NaN, power = moment = 0.
+ *   signal     peak_bin = the first bin holding the run's largest non-NaN value, peak_db that value; x_lo / x_hi = the
+ *              first / last bin of the run with row[i] >= peak_db - xdb (float32); power = sum p_i, moment =
+ *              sum (i - start) p_i over the run's non-NaN bins, p_i = 10^(row[i] / 10) in float32 (tdsa_rows_stats'
+ *              expression) summed in float64 - one fixed tree given (start, stop), so a row's records do not depend
+ *              on n_rows, its place, the entry point or its alignment.
+ *   occupancy  uint32 [n_bins] on the handle: every unflagged row adds its set bins; rows_seen and rows_flagged count
+ *              the rows of all calls since the last _reset (or create).
+ * _configure fixes the parameters: 0 <= bin_lo <= bin_hi < n_bins, 0 <= rank < n_eff, margin_db finite, 1 <= min_width
+ * <= n_bins, 0 <= max_gap <= n_bins, xdb finite and >= 0, 1 <= max_signals <= 64.  _process: host rows through pinned
+ * staging, n_rows <= max_host_rows.  _process_dev: rows in device memory (aligned to 4 bytes; 16-byte loads where
+ * n_bins % 4 == 0 and rows_dev is 16-byte aligned, float loads otherwise, with the same results), on plan p's stream
+ * (ordered after its work, and its later work after this) or on the handle's own for p = NULL.  Both write n_rows row
+ * records and n_rows * max_signals signal records and return when they are in host memory; n_rows = 0 returns TDSA_OK
+ * and writes nothing.  _read_occupancy: any of the three destinations may be NULL, not all.  Argument errors are
+ * reported before any HIP call. */
+#define TDSA_DETECT_NAN_FLOOR 1
+typedef struct tdsa_detect_row {
+  float floor, thr;
+  int32_t n_found, n_over, flags;
+  int32_t reserved[3];
+} tdsa_detect_row;
+typedef struct tdsa_detect_signal {
+  int32_t start, stop, peak_bin, x_lo, x_hi;   /* bins of the row, inclusive */
+  float peak_db;
+  double power, moment;                        /* linear; centroid = start + moment / power */
+} tdsa_detect_signal;
+typedef struct tdsa_detect_s* tdsa_detect;
+int tdsa_detect_create(int device_id, int n_bins, size_t max_host_rows, tdsa_detect* out);
+int tdsa_detect_destroy(tdsa_detect h);
+int tdsa_detect_configure(tdsa_detect h, int bin_lo, int bin_hi, int rank, float margin_db, int min_width, int max_gap,
+                          float xdb, int max_signals);
+int tdsa_detect_process(tdsa_detect h, const float* rows_host, size_t n_rows, tdsa_detect_row* row_records_host,
+                        tdsa_detect_signal* signal_records_host);
+int tdsa_detect_process_dev(tdsa_detect h, tdsa_plan p, const float* rows_dev, size_t n_rows,
+                            tdsa_detect_row* row_records_host, tdsa_detect_signal* signal_records_host);
+int tdsa_detect_read_occupancy(tdsa_detect h, uint32_t* counts_host, uint64_t* rows_seen, uint64_t* rows_flagged);
+int tdsa_detect_reset(tdsa_detect h);
+int tdsa_detect_timer_begin(tdsa_detect h);
+int tdsa_detect_timer_end(tdsa_detect h, float* elapsed_ms);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

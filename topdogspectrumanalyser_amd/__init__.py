@@ -15,6 +15,7 @@ from .zoom import DownConverter, ZoomSpectrum, design_decimator  # noqa: F401
 from .channelizer import Channelizer, ChannelSpectra  # noqa: F401
 from .demod import Demodulator, deemphasis_pole, design_audio_filter  # noqa: F401
 from .symbols import SymbolSync, rrc_taps  # noqa: F401
+from .detect import Detections, SignalDetector  # noqa: F401
 from .zerospan import ZeroSpan, view_plan  # noqa: F401
 from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401
@@ -24,4 +25,4 @@ __all__ = ["SpectrumEngine", "HostPipe", "TraceState", "TraceAverager", "SampleD
            "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView",
            "DownConverter", "ZoomSpectrum", "design_decimator", "ZeroSpan", "view_plan", "IqSweepDataSource", "SweepAssembler", "plan_steps",
            "TraceHistory", "RibbonView", "ThreeDView", "SurfaceView", "Channelizer", "ChannelSpectra",
-           "Demodulator", "design_audio_filter", "deemphasis_pole"]
+           "Demodulator", "design_audio_filter", "deemphasis_pole", "SignalDetector", "Detections"]

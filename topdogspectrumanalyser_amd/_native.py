@@ -25,6 +25,7 @@ DEMOD_FM, DEMOD_AM = 0, 1
 DEMOD_POLE_OFF, DEMOD_POLE_LOWPASS, DEMOD_POLE_HIGHPASS = 0, 1, 2
 SYMSYNC_AUTO, SYMSYNC_FIXED = 0, 1
 SYMSYNC_NONFINITE, SYMSYNC_NO_CARRIER = 1, 2
+DETECT_NAN_FLOOR = 1
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
 ZS_FREE_RUN, ZS_RISE, ZS_FALL = 0, 1, 2
 ZS_COL_MINMAX, ZS_COL_SAMPLE, ZS_COL_MEAN = 0, 1, 2
@@ -158,6 +159,15 @@ _SIGNATURES = {
     "tdsa_symsync_symbols_per_segment": (C.c_int, [C.c_uint64, C.c_size_t, C.POINTER(C.c_int)]),
     "tdsa_symsync_timer_begin": (C.c_int, [_P]),
     "tdsa_symsync_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_detect_create": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_detect_destroy": (C.c_int, [_P]),
+    "tdsa_detect_configure": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int]),
+    "tdsa_detect_process": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "tdsa_detect_process_dev": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
+    "tdsa_detect_read_occupancy": (C.c_int, [_P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "tdsa_detect_reset": (C.c_int, [_P]),
+    "tdsa_detect_timer_begin": (C.c_int, [_P]),
+    "tdsa_detect_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),

@@ -1,0 +1,199 @@
+// tdsa_capi_detect.cpp - tdsa_detect_*.
+#include "tdsa_capi_internal.hpp"
+#include "tdsa_detect.hpp"
+
+using namespace tdsa;
+
+static_assert(sizeof(tdsa_detect_row) == sizeof(DetRow), "the public row record is the kernel's");
+static_assert(sizeof(tdsa_detect_signal) == sizeof(DetSignal), "the public signal record is the kernel's");
+
+// ---- signal detection (tdsa_detect.hip) --------------------------------------------------------------------------
+struct tdsa_detect_s : Lane {
+  int n_bins = 0;
+  size_t max_host = 0;             // rows one host call stages
+  void* h_in = nullptr;            // pinned staging of a host block ...
+  float* d_in = nullptr;
+  DetRow* d_row = nullptr;         // ... and the records of either entry point, grown on demand
+  DetSignal* d_sig = nullptr;
+  size_t row_cap = 0, sig_cap = 0;
+  unsigned* d_occ = nullptr;       // [n_bins] rows in which the bin was above the threshold
+  uint64_t rows_seen = 0, rows_flagged = 0;
+  bool configured = false;
+  int lo = 0, hi = 0, rank = 0, min_width = 1, max_gap = 0, S = 1;
+  float margin = 0.0f, xdb = 0.0f;
+};
+
+namespace {
+
+// the checks both entry points share, before any HIP call
+int det_check(const tdsa_detect_s* h, const void* rows, const void* row_rec, const void* sig_rec) {
+  if (!h) return fail(TDSA_ERR_ARG, "null detector");
+  if (!h->configured) return fail(TDSA_ERR_ARG, "not configured: call tdsa_detect_configure first");
+  if (!rows) return fail(TDSA_ERR_ARG, "null rows");
+  if (!row_rec) return fail(TDSA_ERR_ARG, "null row records");
+  if (!sig_rec) return fail(TDSA_ERR_ARG, "null signal records");
+  return TDSA_OK;
+}
+
+// one call on stream s over device rows; returns when the records are in the caller's memory
+int det_run(tdsa_detect_s* h, hipStream_t s, const float* rows, size_t n_rows, tdsa_detect_row* row_host,
+            tdsa_detect_signal* sig_host) {
+  TRY(grow_device(&h->d_row, &h->row_cap, n_rows, h->last, sizeof(DetRow)));
+  TRY(grow_device(&h->d_sig, &h->sig_cap, n_rows * size_t(h->S), h->last, sizeof(DetSignal)));
+  DetLaunch a;
+  a.rows = rows;
+  a.n_rows = n_rows;
+  a.n = h->n_bins;
+  a.lo = h->lo;
+  a.hi = h->hi;
+  a.rank = h->rank;
+  a.margin = h->margin;
+  a.xdb = h->xdb;
+  a.min_width = h->min_width;
+  a.max_gap = h->max_gap;
+  a.S = h->S;
+  a.row_rec = h->d_row;
+  a.sig_rec = h->d_sig;
+  a.occ = h->d_occ;
+  HIPCHK(launch_detect(a, s));
+  HIPCHK(hipMemcpyAsync(row_host, h->d_row, n_rows * sizeof(DetRow), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(sig_host, h->d_sig, n_rows * size_t(h->S) * sizeof(DetSignal), hipMemcpyDeviceToHost, s));
+  TRY(h->done(s));
+  HIPCHK(hipStreamSynchronize(s));   // the records are the call's result: they are in the caller's memory on return
+  h->rows_seen += n_rows;
+  for (size_t r = 0; r < n_rows; ++r) h->rows_flagged += row_host[r].flags != 0;
+  return TDSA_OK;
+}
+
+}  // namespace
+
+int tdsa_detect_create(int device_id, int n_bins, size_t max_host_rows, tdsa_detect* out) {
+  if (!out) return fail(TDSA_ERR_ARG, "null out");
+  *out = nullptr;
+  if (n_bins < 1 || n_bins > kDetMaxBins) return fail(TDSA_ERR_ARG, "n_bins=%d: 1 .. %d", n_bins, kDetMaxBins);
+  if (max_host_rows < 1) return fail(TDSA_ERR_ARG, "max_host_rows=%zu: at least 1", max_host_rows);
+  HIPCHK(hipSetDevice(device_id));
+  {
+    const hipError_t e = detect_prepare();
+    if (e != hipSuccess)
+      return fail(TDSA_ERR_HIP, "detect create: the device refuses %d bytes of LDS per workgroup: %s",
+                  kDetMaxLdsBytes - kDetStaticLdsBytes, hipGetErrorString(e));
+  }
+  tdsa_detect h = new (std::nothrow) tdsa_detect_s();
+  if (!h) return fail(TDSA_ERR_NOMEM, "out of host memory");
+  h->device = device_id;
+  h->n_bins = n_bins;
+  h->max_host = max_host_rows;
+  const size_t in_bytes = max_host_rows * size_t(n_bins) * sizeof(float);
+  hipError_t e = h->open(true);
+  if (e == hipSuccess) e = hipHostMalloc(&h->h_in, in_bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_in), in_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_occ), size_t(n_bins) * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMemsetAsync(h->d_occ, 0, size_t(n_bins) * sizeof(unsigned), h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    (void)tdsa_detect_destroy(h);
+    return fail(TDSA_ERR_HIP, "detect create: %s", hipGetErrorString(e));
+  }
+  *out = h;
+  return TDSA_OK;
+}
+
+int tdsa_detect_destroy(tdsa_detect h) {
+  if (!h) return TDSA_OK;
+  h->drain();
+  free_all({h->d_in, h->d_row, h->d_sig, h->d_occ});
+  if (h->h_in) (void)hipHostFree(h->h_in);
+  h->close();
+  delete h;
+  return TDSA_OK;
+}
+
+int tdsa_detect_configure(tdsa_detect h, int bin_lo, int bin_hi, int rank, float margin_db, int min_width, int max_gap,
+                          float xdb, int max_signals) {
+  // what needs no handle first, then the handle, then what depends on its n_bins
+  if (bin_lo < 0 || bin_hi < bin_lo || bin_hi >= kDetMaxBins)
+    return fail(TDSA_ERR_ARG, "bins %d .. %d: 0 <= bin_lo <= bin_hi < n_bins", bin_lo, bin_hi);
+  if (rank < 0 || rank > bin_hi - bin_lo)
+    return fail(TDSA_ERR_ARG, "rank=%d: 0 .. %d, the range's bins less one", rank, bin_hi - bin_lo);
+  if (!std::isfinite(margin_db)) return fail(TDSA_ERR_ARG, "margin_db is not finite");
+  if (min_width < 1 || min_width > kDetMaxBins) return fail(TDSA_ERR_ARG, "min_width=%d: 1 .. n_bins", min_width);
+  if (max_gap < 0 || max_gap > kDetMaxBins) return fail(TDSA_ERR_ARG, "max_gap=%d: 0 .. n_bins", max_gap);
+  if (!std::isfinite(xdb) || xdb < 0.0f) return fail(TDSA_ERR_ARG, "xdb=%g: finite and not negative", double(xdb));
+  if (max_signals < 1 || max_signals > kDetMaxSignals)
+    return fail(TDSA_ERR_ARG, "max_signals=%d: 1 .. %d", max_signals, kDetMaxSignals);
+  if (!h) return fail(TDSA_ERR_ARG, "null detector");
+  if (bin_hi >= h->n_bins) return fail(TDSA_ERR_ARG, "bin_hi=%d: below the handle's %d bins", bin_hi, h->n_bins);
+  if (min_width > h->n_bins) return fail(TDSA_ERR_ARG, "min_width=%d: 1 .. %d", min_width, h->n_bins);
+  if (max_gap > h->n_bins) return fail(TDSA_ERR_ARG, "max_gap=%d: 0 .. %d", max_gap, h->n_bins);
+  h->lo = bin_lo;
+  h->hi = bin_hi;
+  h->rank = rank;
+  h->margin = margin_db;
+  h->min_width = min_width;
+  h->max_gap = max_gap;
+  h->xdb = xdb;
+  h->S = max_signals;
+  h->configured = true;
+  return TDSA_OK;
+}
+
+int tdsa_detect_process(tdsa_detect h, const float* rows_host, size_t n_rows, tdsa_detect_row* row_records_host,
+                        tdsa_detect_signal* signal_records_host) {
+  TRY(det_check(h, rows_host, row_records_host, signal_records_host));
+  if (n_rows > h->max_host)
+    return fail(TDSA_ERR_ARG, "block of %zu rows, the handle stages at most %zu (max_host_rows)", n_rows, h->max_host);
+  if (n_rows == 0) return TDSA_OK;
+  TRY(h->own_stream());
+  const size_t bytes = n_rows * size_t(h->n_bins) * sizeof(float);
+  std::memcpy(h->h_in, rows_host, bytes);   // the previous host call has waited: the staging is free
+  HIPCHK(hipMemcpyAsync(h->d_in, h->h_in, bytes, hipMemcpyHostToDevice, h->stream));
+  return det_run(h, h->stream, h->d_in, n_rows, row_records_host, signal_records_host);
+}
+
+int tdsa_detect_process_dev(tdsa_detect h, tdsa_plan p, const float* rows_dev, size_t n_rows,
+                            tdsa_detect_row* row_records_host, tdsa_detect_signal* signal_records_host) {
+  TRY(det_check(h, rows_dev, row_records_host, signal_records_host));
+  if (reinterpret_cast<uintptr_t>(rows_dev) % 4 != 0)
+    return fail(TDSA_ERR_ARG, "rows_dev must be aligned to one float32 (4 bytes)");
+  if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and detector live on different devices");
+  if (n_rows == 0) return TDSA_OK;
+  hipStream_t s;
+  TRY(h->producer_stream(p, &s));
+  TRY(h->order(s));
+  return det_run(h, s, rows_dev, n_rows, row_records_host, signal_records_host);
+}
+
+int tdsa_detect_read_occupancy(tdsa_detect h, uint32_t* counts_host, uint64_t* rows_seen, uint64_t* rows_flagged) {
+  if (!h) return fail(TDSA_ERR_ARG, "null detector");
+  if (!counts_host && !rows_seen && !rows_flagged) return fail(TDSA_ERR_ARG, "nothing to read into");
+  if (counts_host) {
+    TRY(h->own_stream());
+    HIPCHK(hipMemcpyAsync(counts_host, h->d_occ, size_t(h->n_bins) * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    TRY(h->done(h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  if (rows_seen) *rows_seen = h->rows_seen;
+  if (rows_flagged) *rows_flagged = h->rows_flagged;
+  return TDSA_OK;
+}
+
+int tdsa_detect_reset(tdsa_detect h) {
+  if (!h) return fail(TDSA_ERR_ARG, "null detector");
+  TRY(h->own_stream());
+  HIPCHK(hipMemsetAsync(h->d_occ, 0, size_t(h->n_bins) * sizeof(unsigned), h->stream));
+  TRY(h->done(h->stream));
+  h->rows_seen = h->rows_flagged = 0;
+  return TDSA_OK;
+}
+
+int tdsa_detect_timer_begin(tdsa_detect h) {
+  if (!h) return fail(TDSA_ERR_ARG, "null detector");
+  return h->timer_begin();
+}
+
+int tdsa_detect_timer_end(tdsa_detect h, float* elapsed_ms) {
+  if (!h) return fail(TDSA_ERR_ARG, "null detector");
+  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
+  return h->timer_end(elapsed_ms);
+}
