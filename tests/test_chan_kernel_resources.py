@@ -4,13 +4,11 @@ CU's 160 KiB for every shape the library accepts."""
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-CSRC = os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_build import CSRC, HIPCC, compile_kernels, makefile
+
 KERNELS = {"chan_bank_kernel": 2, "chan_history_kernel": 1}      # name -> instantiations (oversampling 1 and 2)
 
 
@@ -19,36 +17,19 @@ def _const(name):
     return int(eval(m.group(1)))
 
 
-def _flags():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "$(B)/tdsa_chan.o" in mk and re.search(r"^CAPI\s*=.*\bchan\b", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_chan\.hpp\b", mk, re.M)
-    extra = re.search(r"^EXTRA\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["--cuda-device-only"]
-
-
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
     if not shutil.which(HIPCC):
         pytest.skip("hipcc not available")
+    mk = makefile()
+    assert "$(B)/tdsa_chan.o" in mk and re.search(r"^CAPI\s*=.*\bchan\b", mk, re.M)
+    assert re.search(r"^HDRS\s*=.*\btdsa_chan\.hpp\b", mk, re.M)
     asm = str(tmp_path_factory.mktemp("chan") / "tdsa_chan.s")
-    r = subprocess.run(_flags() + ["-Rpass-analysis=kernel-resource-usage", "-S", "tdsa_chan.hip", "-o", asm],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stderr, open(asm).read()
+    return compile_kernels("tdsa_chan.hip", asm), open(asm).read()
 
 
 def test_chan_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(compiled):
-    remarks, _ = compiled
-    kernels, cur = {}, None
-    for ln in remarks.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
+    kernels, _ = compiled
     assert sorted(k for k in kernels if "chan_" in k) == sorted(k for k in kernels), sorted(kernels)
     for name, count in KERNELS.items():
         found = [k for k in kernels if name in k]

@@ -5,13 +5,11 @@ accepts."""
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-CSRC = os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_build import CSRC, HIPCC, compile_kernels, makefile
+
 KERNELS = {"demod_audio_kernel": 2, "demod_history_kernel": 2, "demod_post_kernel": 1}     # name -> instantiations (FM, AM)
 
 
@@ -20,35 +18,17 @@ def _const(name):
     return int(eval(m.group(1)))
 
 
-def _flags():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "$(B)/tdsa_demod.o" in mk and re.search(r"^CAPI\s*=.*\bdemod\b", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_demod\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_demod_math\.hpp\b", mk, re.M)
-    extra = re.search(r"^EXTRA\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["--cuda-device-only"]
-
-
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
+def kernels(tmp_path_factory):
     if not shutil.which(HIPCC):
         pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("demod") / "tdsa_demod.o")
-    r = subprocess.run(_flags() + ["-Rpass-analysis=kernel-resource-usage", "-c", "tdsa_demod.hip", "-o", out],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stderr
+    mk = makefile()
+    assert "$(B)/tdsa_demod.o" in mk and re.search(r"^CAPI\s*=.*\bdemod\b", mk, re.M)
+    assert re.search(r"^HDRS\s*=.*\btdsa_demod\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_demod_math\.hpp\b", mk, re.M)
+    return compile_kernels("tdsa_demod.hip", str(tmp_path_factory.mktemp("demod") / "tdsa_demod.o"))
 
 
-def test_demod_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(remarks):
-    kernels, cur = {}, None
-    for ln in remarks.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
+def test_demod_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(kernels):
     assert sorted(k for k in kernels if "demod_" in k) == sorted(k for k in kernels), sorted(kernels)
     for name, count in KERNELS.items():
         found = [k for k in kernels if name in k]

@@ -5,15 +5,11 @@ CU's 160 KiB."""
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
+from kernel_build import CSRC, HIPCC, compile_kernels, makefile
 from topdogspectrumanalyser_amd import detect as dt
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-CSRC = os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _const(name):
@@ -22,36 +18,18 @@ def _const(name):
     return int(eval(expr))
 
 
-def _flags():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    if not shutil.which(HIPCC):
+        pytest.skip("hipcc not available")
+    mk = makefile()
     assert "$(B)/tdsa_detect.o" in mk and re.search(r"^CAPI\s*=.*\bdetect\b", mk, re.M)
     assert re.search(r"^HDRS\s*=.*\btdsa_detect\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_rows_align\.hpp\b", mk, re.M)
     assert not re.search(r"^\$\(B\)/tdsa_detect\.o:", mk, re.M)          # no flags of its own: the Makefile's
-    extra = re.search(r"^EXTRA\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["--cuda-device-only"]
+    return compile_kernels("tdsa_detect.hip", str(tmp_path_factory.mktemp("detect") / "tdsa_detect.o"))
 
 
-@pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("detect") / "tdsa_detect.o")
-    r = subprocess.run(_flags() + ["-Rpass-analysis=kernel-resource-usage", "-c", "tdsa_detect.hip", "-o", out],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stderr
-
-
-def test_detect_kernel_has_no_scratch_no_spills_and_fits_two_workgroups_per_cu(remarks):
-    kernels, cur = {}, None
-    for ln in remarks.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
+def test_detect_kernel_has_no_scratch_no_spills_and_fits_two_workgroups_per_cu(kernels):
     found = [k for k in kernels if "detect_kernel" in k]
     assert len(found) == 2 and len(kernels) == 2, sorted(kernels)          # 16-byte loads and float loads
     row_bytes = 4 * _const("kDetMaxBins")

@@ -8,42 +8,16 @@ the compiler's own report.  The long-frame kernels (column pass, row pass) are c
 """
 import concurrent.futures
 import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-CSRC = os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def _flags_from_makefile():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    extra = re.search(r"^EXTRA\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra
+from kernel_build import FRAME_SIZES as SIZES, FRAME_SOURCE, HIPCC, compile_kernels
 
 
 def _report(log2n, tmp):
-    out = os.path.join(tmp, f"spec_{log2n}.o")
-    cmd = [HIPCC] + _flags_from_makefile() + [f"-DTDSA_LOG2N={log2n}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                                              os.path.join(CSRC, "tdsa_spectrum_inst.hip"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
-    return kernels
+    return compile_kernels(FRAME_SOURCE, os.path.join(tmp, f"spec_{log2n}.o"), log2n)
 
-
-SIZES = tuple(range(6, 15))
 
 
 @pytest.fixture(scope="module")
@@ -121,23 +95,10 @@ def test_mixed_radix_kernel_is_free_of_scratch(tmp_path):
     """tdsa_smooth.hip (frame lengths 2^a 3^b 5^c): three instantiations of one kernel, no scratch, <= 64 VGPRs."""
     if not shutil.which(HIPCC):
         pytest.skip("hipcc not available")
-    cmd = [HIPCC] + _flags_from_makefile() + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "tdsa_smooth.hip"),
-                                              "-o", str(tmp_path / "s.o")]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-2000:]
-    reps, cur = [], None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = {"Function Name": m.group(1)}
-            reps.append(cur)
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
+    reps = compile_kernels("tdsa_smooth.hip", str(tmp_path / "s.o"))
     # one pass in LDS (frames up to 10 000 points), column pass and row pass of the two-pass transform above
-    assert sorted(rep["Function Name"] for rep in reps) == [f"_ZN4tdsa13smooth_kernelILi{k}EEEvNS_12SmoothParamsE" for k in (0, 1, 2)], reps
-    for rep in reps:
+    assert sorted(reps) == [f"_ZN4tdsa13smooth_kernelILi{k}EEEvNS_12SmoothParamsE" for k in (0, 1, 2)], reps
+    for rep in reps.values():
         assert int(rep["ScratchSize [bytes/lane]"]) == 0 and int(rep["VGPRs Spill"]) == 0 and int(rep["VGPRs"]) <= 64, rep
 
 
@@ -156,34 +117,27 @@ def test_long_frame_column_pass_keeps_three_waves_and_no_vmem_wait_between_its_s
     if not shutil.which(HIPCC):
         pytest.skip("hipcc not available")
     asm = str(tmp_path / "big.s")
-    cmd = [HIPCC] + _flags_from_makefile() + ["-Rpass-analysis=kernel-resource-usage", "-S", "--cuda-device-only",
-                                              os.path.join(CSRC, "tdsa_big.hip"), "-o", asm]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-2000:]
+    reports = compile_kernels("tdsa_big.hip", asm)
+
+    def body_of(name):
+        body, on = [], False
+        for ln in open(asm):
+            if ln.startswith(name + ":"):
+                on = True
+            elif on and ln.startswith(".Lfunc_end"):
+                break
+            elif on:
+                body.append(ln.split(";")[0].strip())
+        return body
+
     # four instantiations per size: the window from a table / one value for every sample, with / without DC removal
     for flat in (0, 1):
         for dc in (0, 1):
             name = f"_ZN4tdsa15big_cols_kernelILi6ELb{flat}ELb{dc}ELb0EEEvNS_13BigColsParamsE"
-            rep, on = {}, False
-            for ln in r.stderr.splitlines():
-                m = re.search(r"Function Name: (\S+)", ln)
-                if m:
-                    on = m.group(1) == name
-                    continue
-                m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-                if m and on:
-                    rep[m.group(1).strip()] = m.group(2)
+            rep = reports[name]
             assert int(rep["ScratchSize [bytes/lane]"]) == 0 and int(rep["VGPRs"]) <= 168 and int(rep["Occupancy [waves/SIMD]"]) >= 3, rep
             assert int(rep["SGPRs Spill"]) == 0, rep
-            body, on = [], False
-            for ln in open(asm):
-                if ln.startswith(name + ":"):
-                    on = True
-                elif on and ln.startswith(".Lfunc_end"):
-                    break
-                elif on:
-                    body.append(ln.split(";")[0].strip())
-            body = [ln for ln in body if ln]
+            body = [ln for ln in body_of(name) if ln]
             stores = [i for i, ln in enumerate(body) if ln.startswith("buffer_store_dwordx4")]
             assert len(stores) == 32, len(stores)
             tail = body[stores[0]:stores[-1] + 1]
@@ -198,38 +152,15 @@ def test_long_frame_column_pass_keeps_three_waves_and_no_vmem_wait_between_its_s
     # the long chirp-z frames' instantiations (raw frames in, times window x chirp; power / dB rows out): no scratch
     for name in ("_ZN4tdsa15big_cols_kernelILi6ELb1ELb0ELb1EEEvNS_13BigColsParamsE",
                  "_ZN4tdsa19big_cols_out_kernelILi6EEEvNS_16BigColsOutParamsE"):
-        rep, on = {}, False
-        for ln in r.stderr.splitlines():
-            m = re.search(r"Function Name: (\S+)", ln)
-            if m:
-                on = m.group(1) == name
-                continue
-            m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-            if m and on:
-                rep[m.group(1).strip()] = m.group(2)
+        rep = reports[name]
         assert int(rep["ScratchSize [bytes/lane]"]) == 0 and int(rep["SGPRs Spill"]) == 0, (name, rep)
 
     # row pass (big_rows_kernel): 128 VGPRs / 4 waves per SIMD without scratch, and the fetch of the next row spread over
     # the row's work - eight 16-byte loads, one at a time, each behind a stretch of arithmetic (bursts cost 13 %)
     name = "_ZN4tdsa15big_rows_kernelENS_13BigRowsParamsE"
-    rep, on = {}, False
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            on = m.group(1) == name
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-        if m and on:
-            rep[m.group(1).strip()] = m.group(2)
+    rep = reports[name]
     assert int(rep["ScratchSize [bytes/lane]"]) == 0 and int(rep["VGPRs"]) <= 128 and int(rep["Occupancy [waves/SIMD]"]) >= 4, rep
-    body, on = [], False
-    for ln in open(asm):
-        if ln.startswith(name + ":"):
-            on = True
-        elif on and ln.startswith(".Lfunc_end"):
-            break
-        elif on:
-            body.append(ln.split(";")[0].strip())
+    body = body_of(name)
     barriers = [i for i, ln in enumerate(body) if ln.startswith("s_barrier")]
     loop = body[barriers[0] + 1:barriers[-1] + 1]                 # from behind the prologue's barrier to the loop's last one
     loads = [i for i, ln in enumerate(loop) if ln.startswith("buffer_load_dwordx4")]

@@ -4,15 +4,11 @@ and the dynamic LDS the launcher asks for stays within ~100 KiB of a CU's 160 fo
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
+from kernel_build import CSRC, HIPCC, compile_kernels, flags, makefile
 from topdogspectrumanalyser_amd import symbols as sy
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-CSRC = os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _const(name):
@@ -21,36 +17,19 @@ def _const(name):
     return int(eval(expr))
 
 
-def _flags():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    if not shutil.which(HIPCC):
+        pytest.skip("hipcc not available")
+    mk = makefile()
     assert "$(B)/tdsa_symsync.o" in mk and re.search(r"^CAPI\s*=.*\bsymsync\b", mk, re.M)
     assert re.search(r"^HDRS\s*=.*\btdsa_symsync\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_symsync_math\.hpp\b", mk, re.M)
     assert re.search(r"^\$\(B\)/tdsa_symsync\.o: EXTRA \+= -ffp-contract=off$", mk, re.M)      # contraction is off for the file
-    extra = re.search(r"^EXTRA\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["-ffp-contract=off", "--cuda-device-only"]
+    assert "-ffp-contract=off" in flags("tdsa_symsync.hip")
+    return compile_kernels("tdsa_symsync.hip", str(tmp_path_factory.mktemp("symsync") / "tdsa_symsync.o"))
 
 
-@pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("symsync") / "tdsa_symsync.o")
-    r = subprocess.run(_flags() + ["-Rpass-analysis=kernel-resource-usage", "-c", "tdsa_symsync.hip", "-o", out],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stderr
-
-
-def test_symsync_kernel_has_no_scratch_no_spills_and_the_budgeted_static_lds(remarks):
-    kernels, cur = {}, None
-    for ln in remarks.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\S+)\s+\[-Rpass", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
+def test_symsync_kernel_has_no_scratch_no_spills_and_the_budgeted_static_lds(kernels):
     found = [k for k in kernels if "symsync_kernel" in k]
     assert len(found) == 1 and len(kernels) == 1, sorted(kernels)
     k = kernels[found[0]]

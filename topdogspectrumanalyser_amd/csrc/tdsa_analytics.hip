@@ -14,6 +14,7 @@
 #include "tdsa_fft.hpp"        // static_for
 #include "tdsa_kernels.hpp"
 #include "tdsa_rows_align.hpp"
+#include "tdsa_wave.hpp"
 
 #include <math.h>
 
@@ -21,76 +22,13 @@ namespace tdsa {
 
 namespace {
 
-struct PeakPair {
-  float v;
-  int i;
-};
 // np.max / np.argmax order: NaN beats everything, then larger value, then smaller index
 __device__ __forceinline__ bool better(PeakPair a, PeakPair b) {
   const bool an = a.v != a.v, bn = b.v != b.v;
   if (an || bn) return an && (!bn || a.i < b.i);
   return a.v > b.v || (a.v == b.v && a.i < b.i);
 }
-__device__ __forceinline__ PeakPair wave_best(PeakPair p) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    PeakPair q{__shfl_xor(p.v, o), __shfl_xor(p.i, o)};
-    if (better(q, p)) p = q;
-  }
-  return p;
-}
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-// the same reductions with DPP moves (no LDS round trip per step as with ds_bpermute); the result is valid in
-// lane 63 only.  Lanes without a source lane keep their own value, which is the identity of min / "better".
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float x) {
-  return __uint_as_float(__builtin_amdgcn_update_dpp(__float_as_uint(x), __float_as_uint(x), CTRL, ROW_MASK, 0xf, false));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_i(int x) {
-  return __builtin_amdgcn_update_dpp(x, x, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ float wave_min_to_lane63(float x) {
-  x = fminf(x, dpp_f<0xB1, 0xf>(x));     // quad_perm [1,0,3,2]
-  x = fminf(x, dpp_f<0x4E, 0xf>(x));     // quad_perm [2,3,0,1]
-  x = fminf(x, dpp_f<0x141, 0xf>(x));    // row_half_mirror
-  x = fminf(x, dpp_f<0x140, 0xf>(x));    // row_mirror: every lane = row minimum
-  x = fminf(x, dpp_f<0x142, 0xa>(x));    // row_bcast:15 -> rows 1, 3
-  x = fminf(x, dpp_f<0x143, 0xc>(x));    // row_bcast:31 -> rows 2, 3
-  return x;
-}
-// strongest candidate of the wave, equal values: larger index (the order of the reference's reversed ascending sort)
-__device__ __forceinline__ PeakPair row_strongest(PeakPair p) {      // every lane: the strongest of its row of 16 lanes
-  auto step = [&](float qv, int qi) {
-    if (qv > p.v || (qv == p.v && qi > p.i)) p = PeakPair{qv, qi};
-  };
-  step(dpp_f<0xB1, 0xf>(p.v), dpp_i<0xB1, 0xf>(p.i));
-  step(dpp_f<0x4E, 0xf>(p.v), dpp_i<0x4E, 0xf>(p.i));
-  step(dpp_f<0x141, 0xf>(p.v), dpp_i<0x141, 0xf>(p.i));
-  step(dpp_f<0x140, 0xf>(p.v), dpp_i<0x140, 0xf>(p.i));
-  return p;
-}
-__device__ __forceinline__ float row_min(float x) {                   // every lane: the minimum of its row of 16 lanes
-  x = fminf(x, dpp_f<0xB1, 0xf>(x));
-  x = fminf(x, dpp_f<0x4E, 0xf>(x));
-  x = fminf(x, dpp_f<0x141, 0xf>(x));
-  x = fminf(x, dpp_f<0x140, 0xf>(x));
-  return x;
-}
-__device__ __forceinline__ PeakPair wave_strongest_to_lane63(PeakPair p) {
-  auto step = [&](float qv, int qi) {
-    if (qv > p.v || (qv == p.v && qi > p.i)) p = PeakPair{qv, qi};
-  };
-  p = row_strongest(p);
-  step(dpp_f<0x142, 0xa>(p.v), dpp_i<0x142, 0xa>(p.i));
-  step(dpp_f<0x143, 0xc>(p.v), dpp_i<0x143, 0xc>(p.i));
-  return p;
-}
-
+__device__ __forceinline__ PeakPair wave_best(PeakPair p) { return wave_best(p, better); }
 // ---- per-row peak / argmax / band power ------------------------------------------------------------
 __global__ void __launch_bounds__(256) rows_stats_kernel(const float* __restrict__ rows, int n, int band_lo,
                                                          int band_hi, double bin_width, float* peak_db,
@@ -206,8 +144,8 @@ __global__ void __launch_bounds__(1 << LOG2T) __attribute__((amdgpu_waves_per_eu
     const int i = tid + T * k;
     if (T * k < n) {                       // (uniform)
       if (i < n) row[i] = vals[k];
-      float mn = row_min(vals[k] != vals[k] ? -INFINITY : vals[k]);   // a NaN is the lowest floor there is (see the valley test)
-      mn = fminf(mn, dpp_f<0x142, 0xa>(mn));          // row_bcast:15: lanes 31 and 63 hold the minimum of their 32 bins
+      // a NaN is the lowest floor there is (see the valley test)
+      const float mn = half_min_to_lanes31_63(vals[k] != vals[k] ? -INFINITY : vals[k]);
       if ((lane & 31) == 31 && (i & ~31) < n) s_bmin[i >> 5] = mn;
     }
   }
@@ -303,11 +241,7 @@ __global__ void __launch_bounds__(1 << LOG2T) __attribute__((amdgpu_waves_per_eu
       const float craw = cidx < n ? row[cidx] : INFINITY;
       const float cv = craw != craw ? -INFINITY : craw;
       float part = (lane < 32 ? cidx <= cur : cidx >= cur) ? cv : INFINITY;
-      part = fminf(part, dpp_f<0xB1, 0xf>(part));
-      part = fminf(part, dpp_f<0x4E, 0xf>(part));
-      part = fminf(part, dpp_f<0x141, 0xf>(part));
-      part = fminf(part, dpp_f<0x140, 0xf>(part));
-      part = fminf(part, dpp_f<0x142, 0xa>(part));          // row_bcast:15: lanes 31 and 63 hold their half's minimum
+      part = half_min_to_lanes31_63(part);
       const float cur_upto = __shfl(part, 31), cur_from = __shfl(part, 63);
       // four accepted peaks at a time, one per row of 16 lanes: the row folds the peak's 16 wave minima, adds the end blocks
       bool rej = false;
@@ -568,9 +502,9 @@ __global__ void __launch_bounds__(kMarkThreads) marker_peaks_kernel(const float*
         }
       }
       // eight lanes hold a block of 32 bins: two quad steps and the mirror of each half-row (DPP, no LDS round trips)
-      mx = fmaxf(mx, dpp_f<0xB1, 0xf>(mx)); mn = fminf(mn, dpp_f<0xB1, 0xf>(mn));
-      mx = fmaxf(mx, dpp_f<0x4E, 0xf>(mx)); mn = fminf(mn, dpp_f<0x4E, 0xf>(mn));
-      mx = fmaxf(mx, dpp_f<0x141, 0xf>(mx)); mn = fminf(mn, dpp_f<0x141, 0xf>(mn));
+      mx = fmaxf(mx, dpp_f<QuadSwap1>(mx)); mn = fminf(mn, dpp_f<QuadSwap1>(mn));
+      mx = fmaxf(mx, dpp_f<QuadSwap2>(mx)); mn = fminf(mn, dpp_f<QuadSwap2>(mn));
+      mx = fmaxf(mx, dpp_f<RowHalfMirror>(mx)); mn = fminf(mn, dpp_f<RowHalfMirror>(mn));
       if ((lane & 7) == 0 && (c >> 3) < nw) {
         L.bmax1[c >> 3] = mx;
         L.bmin1[c >> 3] = mn;
@@ -863,12 +797,12 @@ __global__ void __launch_bounds__(kDensWaves * 64) __attribute__((amdgpu_waves_p
     // both rows in one word) and plain stores by their only writer (sixty-four atomics on one LDS word took the LDS pipe as long
     // as a hit wave's reads)
     unsigned bits = cell(v0, lr) | (cell(v1, lr + 16) << 16);
-    bits |= unsigned(dpp_i<0xB1, 0xf>(int(bits)));
-    bits |= unsigned(dpp_i<0x4E, 0xf>(int(bits)));
-    bits |= unsigned(dpp_i<0x141, 0xf>(int(bits)));
-    bits |= unsigned(dpp_i<0x140, 0xf>(int(bits)));
-    bits |= unsigned(dpp_i<0x142, 0xa>(int(bits)));
-    bits |= unsigned(dpp_i<0x143, 0xc>(int(bits)));
+    bits |= unsigned(dpp_i<QuadSwap1>(int(bits)));
+    bits |= unsigned(dpp_i<QuadSwap2>(int(bits)));
+    bits |= unsigned(dpp_i<RowHalfMirror>(int(bits)));
+    bits |= unsigned(dpp_i<RowMirror>(int(bits)));
+    bits |= unsigned(dpp_i<RowBcast15>(int(bits)));
+    bits |= unsigned(dpp_i<RowBcast31>(int(bits)));
     if (lane == 63) {
       s_wh[par][lr] = bits & 0xffffu;
       s_wh[par][lr + 16] = bits >> 16;

@@ -193,8 +193,7 @@ __global__ void __launch_bounds__(256) big_cols_kernel(const BigColsParams p) {
         // rows (k1 - 1, k1): the even lane keeps its row k1 - 1 value and sends its row k1 value, the odd lane the
         // other way round
         const float sx = odd ? xprev.x : x.x, sy = odd ? xprev.y : x.y;          // what the partner needs
-        const float rx = __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(sx), 0xB1, 0xf, 0xf, true));
-        const float ry = __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(sy), 0xB1, 0xf, 0xf, true));
+        const float rx = dpp_or0<QuadSwap1, true>(sx), ry = dpp_or0<QuadSwap1, true>(sy);
         const float ox = odd ? x.x : xprev.x, oy = odd ? x.y : xprev.y;          // own value of the row this lane stores
         const bu32x4 pk = {__float_as_uint(odd ? rx : ox), __float_as_uint(odd ? ry : oy),
                            __float_as_uint(odd ? ox : rx), __float_as_uint(odd ? oy : ry)};

@@ -30,22 +30,13 @@
 // [F][M] complex64 rows); the point of this path is that every size the reference accepts has a device path.
 #include "tdsa_fft.hpp"
 #include "tdsa_kernels.hpp"
+#include "tdsa_wave.hpp"
 
 namespace tdsa {
 
 namespace {
 
 constexpr float kTenLog10Of2 = 3.01029995663981195214f;   // 10*log10(2): dB = kTenLog10Of2 * log2(power)
-
-// float max/min through integer atomics (IEEE-754 order trick); NaN candidates are skipped (np.fmax / np.fmin)
-__device__ __forceinline__ void chirp_atomic_fmax(float* addr, float v) {
-  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else if (v < 0.f) atomicMin(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
-}
-__device__ __forceinline__ void chirp_atomic_fmin(float* addr, float v) {
-  if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else if (v < 0.f) atomicMax(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
-}
 
 }  // namespace
 
@@ -341,8 +332,8 @@ __global__ void __launch_bounds__(256) chirp_post_kernel(const ChirpPostParams p
     hmin = fminf(hmin, dmn);
   }
   if (p.out_lin == nullptr) {
-    if (p.hold_max != nullptr && hmax > p.hold_max[j]) chirp_atomic_fmax(p.hold_max + j, hmax);
-    if (p.hold_min != nullptr && hmin < p.hold_min[j]) chirp_atomic_fmin(p.hold_min + j, hmin);
+    if (p.hold_max != nullptr && hmax > p.hold_max[j]) atomic_fmax(p.hold_max + j, hmax);
+    if (p.hold_min != nullptr && hmin < p.hold_min[j]) atomic_fmin(p.hold_min + j, hmin);
   }
 }
 
@@ -406,8 +397,8 @@ __global__ void __launch_bounds__(256) chirp_hold_kernel(const float* rows, int 
     hmax = fmaxf(hmax, dmx);                 // a NaN operand is ignored, as by np.fmax
     hmin = fminf(hmin, dmn);
   }
-  if (hold_max != nullptr && hmax > hold_max[j]) chirp_atomic_fmax(hold_max + j, hmax);
-  if (hold_min != nullptr && hmin < hold_min[j]) chirp_atomic_fmin(hold_min + j, hmin);
+  if (hold_max != nullptr && hmax > hold_max[j]) atomic_fmax(hold_max + j, hmax);
+  if (hold_min != nullptr && hmin < hold_min[j]) atomic_fmin(hold_min + j, hmin);
 }
 
 hipError_t launch_chirp_hold(const float* rows, int n, int n_frames, int first_frame_index, float* hold_max, float* hold_min,

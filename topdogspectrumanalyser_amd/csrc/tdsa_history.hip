@@ -18,6 +18,7 @@
 // registers (tdsa_big.hip) is one the compiler's recognizer always pads for FLAT-class stores; the case it misses is the
 // buffer store with an SGPR offset, which this file does not use (tests/test_history_kernel_resources.py looks).
 #include "tdsa_history.hpp"
+#include "tdsa_wave.hpp"
 
 namespace tdsa {
 namespace {
@@ -103,11 +104,7 @@ __global__ __launch_bounds__(kBlock) void hist_push_kernel(HistPush a) {
       }
     }
     if (k >= a.skip) {   // the same for the whole workgroup
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o);
-        key = other > key ? other : key;
-      }
+      key = wave_reduce(key, [](unsigned long long a, unsigned long long b) { return b > a ? b : a; });
       if ((threadIdx.x & 63) == 0 && key != 0) atomicMax(a.keys + slot, key);
     }
   }

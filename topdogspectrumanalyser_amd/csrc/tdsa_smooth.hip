@@ -13,16 +13,13 @@
 // offset - tare or linear power rows on store; hold traces folded from the rows by chirp_hold_kernel.
 #include <hip/hip_runtime.h>
 
+#include "tdsa_fft.hpp"        // c32, cadd, csub, cmul
 #include "tdsa_kernels.hpp"
 
 namespace tdsa {
 
 namespace {
 
-using c32 = float2;
-__device__ __forceinline__ c32 cadd(c32 a, c32 b) { return c32{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ c32 csub(c32 a, c32 b) { return c32{a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ c32 cmul_(c32 a, c32 b) { return c32{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 __device__ __forceinline__ c32 mul_mi(c32 a) { return c32{a.y, -a.x}; }      // a * (-i)
 
 constexpr float kTenLog10Of2 = 3.01029995663981195214f;
@@ -91,7 +88,7 @@ __device__ __forceinline__ void stage(const c32* __restrict__ tw, int tw_step, i
     const int ws = pp * s * tw_step;                     // W_n^(p u) = W_N^(p u s); (two passes: W_N = W_Ntotal^tw_step)
     st(fr, q + s * (R * pp), a[0]);
 #pragma unroll
-    for (int u = 1; u < R; ++u) st(fr, q + s * (R * pp + u), m == 1 ? a[u] : cmul_(a[u], tw[ws * u]));   // (p u s < N)
+    for (int u = 1; u < R; ++u) st(fr, q + s * (R * pp + u), m == 1 ? a[u] : cmul(a[u], tw[ws * u]));   // (p u s < N)
   }
 }
 
@@ -184,7 +181,7 @@ __global__ void __launch_bounds__(1024) smooth_kernel(const SmoothParams p) {
     if (fr >= nf) return;
     if constexpr (MODE == 1) {                           // column pass: times W_N^(n2' k1), to z[k1][n2']
       const int n2 = f0 + fr;
-      p.z[(long long)fy * NT + (long long)kk * p.n2 + n2] = cmul_(X, p.tw[n2 * kk]);
+      p.z[(long long)fy * NT + (long long)kk * p.n2 + n2] = cmul(X, p.tw[n2 * kk]);
       return;
     }
     const int k = MODE == 0 ? kk : f0 + fr + p.n1 * kk;  // (row pass: bin k1 + n1 k2)

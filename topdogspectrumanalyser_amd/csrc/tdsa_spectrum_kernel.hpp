@@ -34,6 +34,7 @@
 #endif
 #include "tdsa_fft.hpp"
 #include "tdsa_kernels.hpp"
+#include "tdsa_wave.hpp"
 
 namespace tdsa {
 
@@ -95,13 +96,6 @@ __device__ __forceinline__ void load_raw(const unsigned char* q, uint32_t* dst) 
   }
 }
 
-template <int W, class T>
-__device__ __forceinline__ T seg_sum(T x) {
-#pragma unroll
-  for (int off = W / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-
 // keeps a value opaque to loop-invariant code motion (the twiddle products must be rebuilt per frame,
 // hoisting them would cost 42 VGPRs per pass)
 __device__ __forceinline__ void opaque(c32& w) { asm volatile("" : "+v"(w.x), "+v"(w.y)); }
@@ -113,50 +107,6 @@ __device__ __forceinline__ float in_vgpr(float x) { asm volatile("" : "+v"(x)); 
 __device__ __forceinline__ float hw_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float hw_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float hw_max3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-// wave64 float maximum (NaN operands ignored) / sum across the lanes; the result is valid in lane 63
-__device__ __forceinline__ float dpp_wave_max63(float x) {
-  // v_max_f32 with the DPP operand in ONE instruction each (through the builtins it is v_mov, v_mov_dpp, v_max and three
-  // s_nop per step); the two wait states a DPP read of a freshly written VGPR needs sit inside every statement, whatever
-  // the compiler puts in front of it (its hazard recognizer does not look into inline assembly)
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\ts_nop 0" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ float dpp_wave_sum63(float x) {
-  x += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(x), 0xB1, 0xf, 0xf, true));
-  x += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(x), 0x4E, 0xf, 0xf, true));
-  x += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(x), 0x141, 0xf, 0xf, true));
-  x += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(x), 0x140, 0xf, 0xf, true));
-  x += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(x), 0x142, 0xa, 0xf, false));
-  x += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(x), 0x143, 0xc, 0xf, false));
-  return x;
-}
-
-// wave64 integer sum with DPP adds (no LDS round trips); the total is valid in lanes 48..63
-__device__ __forceinline__ int dpp_wave_sum(int x) {
-  // bound_ctrl: every source lane of these four steps exists and the masks are full, so `old` is never read
-  x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, true);     // quad_perm [1,0,3,2]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, true);     // quad_perm [2,3,0,1]
-  x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, true);    // row_half_mirror
-  x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, true);    // row_mirror: every lane = row sum
-  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-  x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-  return x;
-}
-
-// float max/min through integer atomics (IEEE-754 order trick); NaN candidates are skipped (np.fmax)
-__device__ __forceinline__ void atomic_fmax_dev(float* addr, float v) {
-  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else if (v < 0.f) atomicMin(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
-}
-__device__ __forceinline__ void atomic_fmin_dev(float* addr, float v) {
-  if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else if (v < 0.f) atomicMax(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
-}
 
 using rsrc_t = __amdgpu_buffer_rsrc_t;
 __device__ __forceinline__ rsrc_t make_rsrc(const void* base, unsigned bytes) {
@@ -1093,10 +1043,10 @@ __global__ void __launch_bounds__(Cfg<LOG2N>::WGT, 4) spectrum_kernel(const Spec
           constexpr int q = decltype(ic)::value;
           constexpr int kcs = (q < 8 ? q : q + 8) ^ 16;
           if constexpr ((HOLD & 1) != 0) {
-            if (hmax[q] > cmax[q]) atomic_fmax_dev(p.part_max + prow + kcs * SG, hmax[q]);
+            if (hmax[q] > cmax[q]) atomic_fmax(p.part_max + prow + kcs * SG, hmax[q]);
           }
           if constexpr ((HOLD & 2) != 0) {
-            if (hmin[q] < cmin[q]) atomic_fmin_dev(p.part_min + prow + kcs * SG, hmin[q]);
+            if (hmin[q] < cmin[q]) atomic_fmin(p.part_min + prow + kcs * SG, hmin[q]);
           }
         });
       }
@@ -1115,18 +1065,18 @@ __global__ void __launch_bounds__(Cfg<LOG2N>::WGT, 4) spectrum_kernel(const Spec
         static_for<0, 16>([&](auto ic) {
           constexpr int q = decltype(ic)::value;
           constexpr int kcs = (q < 8 ? q : q + 8) ^ 16;
-          if constexpr ((HOLD & 1) != 0) atomic_fmax_dev(lmax + prow + kcs * SG, hmax[q]);
-          if constexpr ((HOLD & 2) != 0) atomic_fmin_dev(lmin + prow + kcs * SG, hmin[q]);
+          if constexpr ((HOLD & 1) != 0) atomic_fmax(lmax + prow + kcs * SG, hmax[q]);
+          if constexpr ((HOLD & 2) != 0) atomic_fmin(lmin + prow + kcs * SG, hmin[q]);
         });
       }
       __syncthreads();
       if (u1 > u0) {
         for (int i = tid; i < N; i += C::WGT) {
           if constexpr ((HOLD & 1) != 0) {
-            if (lmax[i] > p.part_max[i]) atomic_fmax_dev(p.part_max + i, lmax[i]);
+            if (lmax[i] > p.part_max[i]) atomic_fmax(p.part_max + i, lmax[i]);
           }
           if constexpr ((HOLD & 2) != 0) {
-            if (lmin[i] < p.part_min[i]) atomic_fmin_dev(p.part_min + i, lmin[i]);
+            if (lmin[i] < p.part_min[i]) atomic_fmin(p.part_min + i, lmin[i]);
           }
         }
       }

@@ -34,23 +34,7 @@
         // lane (l mod WPF) fetches one wave's partial (a single conflict-free ds_read_b64 per wave),
         // the WPF partials are then summed inside the 16-lane row with DPP adds
         const int2 q = *reinterpret_cast<const int2*>(&redi[(w0 + (tid & (C::WPF - 1))) * 2]);
-        int ti = q.x, tq = q.y;
-        if constexpr (C::WPF >= 2) {
-          ti += __builtin_amdgcn_update_dpp(0, ti, 0xB1, 0xf, 0xf, false);
-          tq += __builtin_amdgcn_update_dpp(0, tq, 0xB1, 0xf, 0xf, false);
-        }
-        if constexpr (C::WPF >= 4) {
-          ti += __builtin_amdgcn_update_dpp(0, ti, 0x4E, 0xf, 0xf, false);
-          tq += __builtin_amdgcn_update_dpp(0, tq, 0x4E, 0xf, 0xf, false);
-        }
-        if constexpr (C::WPF >= 8) {
-          ti += __builtin_amdgcn_update_dpp(0, ti, 0x141, 0xf, 0xf, false);
-          tq += __builtin_amdgcn_update_dpp(0, tq, 0x141, 0xf, 0xf, false);
-        }
-        if constexpr (C::WPF >= 16) {
-          ti += __builtin_amdgcn_update_dpp(0, ti, 0x140, 0xf, 0xf, false);
-          tq += __builtin_amdgcn_update_dpp(0, tq, 0x140, 0xf, 0xf, false);
-        }
+        const int ti = dpp_row_sum<C::WPF>(q.x), tq = dpp_row_sum<C::WPF>(q.y);
         sub_re = float(ti) * (1.0f / N);     // exact: sums < 2^24, N a power of two
         sub_im = float(tq) * (1.0f / N);
         if (p.dc_state != nullptr && frame == p.n_frames - 1 && t == 0 && h == 0)
@@ -67,23 +51,7 @@
         si = __builtin_amdgcn_udot4(raw[i], 0x00010001u, si, false);
         sq = __builtin_amdgcn_udot4(raw[i], 0x01000100u, sq, false);
       });
-      int ti = int(si), tq = int(sq);
-      if constexpr (SG >= 2) {
-        ti += __builtin_amdgcn_update_dpp(0, ti, 0xB1, 0xf, 0xf, false);
-        tq += __builtin_amdgcn_update_dpp(0, tq, 0xB1, 0xf, 0xf, false);
-      }
-      if constexpr (SG >= 4) {
-        ti += __builtin_amdgcn_update_dpp(0, ti, 0x4E, 0xf, 0xf, false);
-        tq += __builtin_amdgcn_update_dpp(0, tq, 0x4E, 0xf, 0xf, false);
-      }
-      if constexpr (SG >= 8) {
-        ti += __builtin_amdgcn_update_dpp(0, ti, 0x141, 0xf, 0xf, false);
-        tq += __builtin_amdgcn_update_dpp(0, tq, 0x141, 0xf, 0xf, false);
-      }
-      if constexpr (SG >= 16) {
-        ti += __builtin_amdgcn_update_dpp(0, ti, 0x140, 0xf, 0xf, false);
-        tq += __builtin_amdgcn_update_dpp(0, tq, 0x140, 0xf, 0xf, false);
-      }
+      int ti = dpp_row_sum<SG>(int(si)), tq = dpp_row_sum<SG>(int(sq));
       ti += __shfl_xor(ti, 32);
       tq += __shfl_xor(tq, 32);
       TDSA_SYNC();
@@ -99,7 +67,7 @@
         s_re += double(v[i].x); s_im += double(v[i].y);
       });
       constexpr int W = SG < 32 ? SG : 32;                  // rows of this frame inside the half-wave
-      s_re = seg_sum<W>(s_re); s_im = seg_sum<W>(s_im);
+      s_re = wave_sum<W>(s_re); s_im = wave_sum<W>(s_im);
       s_re += __shfl_xor(s_re, 32); s_im += __shfl_xor(s_im, 32);   // the other half-thread's rows
       if constexpr (SG > 32) {
         if constexpr (HOLD >= 3 || STATS) {          // (scalar wave index rebuilt per frame: see the byte path above)

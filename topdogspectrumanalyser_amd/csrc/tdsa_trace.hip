@@ -5,20 +5,11 @@
 //   trace_update  : DataProcessor's per-frame cal offset / tare / hold on a dB row handed in from the
 //                   host (display_data_processor.py:317-395)
 #include "tdsa_kernels.hpp"
+#include "tdsa_wave.hpp"
 
 namespace tdsa {
 
 constexpr float k10Log10_2f = 3.01029995663981195214f;
-
-// float max/min through integer atomics (IEEE-754 order trick); the state is initialised to -inf / +inf
-__device__ __forceinline__ void atomic_fmax(float* addr, float v) {
-  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else atomicMin(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
-}
-__device__ __forceinline__ void atomic_fmin(float* addr, float v) {
-  if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else atomicMax(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
-}
 
 // One thread per bin walks the batch in frame order (the recurrence is order dependent: SURVEY.md 7).
 __global__ void __launch_bounds__(64) avg_scan_kernel(const AvgParams p) {

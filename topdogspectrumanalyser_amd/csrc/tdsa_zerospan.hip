@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tdsa_hip.h"
+#include "tdsa_wave.hpp"
 #include "tdsa_zerospan.hpp"
 
 // every rounding of the detectors is written out
@@ -118,15 +119,6 @@ __global__ __launch_bounds__(kThreads) void zspan_push_kernel(ZsPush a) {
   }
 }
 
-__device__ inline int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const int t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(kThreads) void zspan_trigger_kernel(ZsTrigger a) {
   __shared__ int part[kThreads / 64];
   const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -177,24 +169,6 @@ struct MinMax {
   __device__ inline float lo() const { return nan ? NAN : mn; }
   __device__ inline float hi() const { return nan ? NAN : mx; }
 };
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, 64);   // a + b on one lane, b + a on its partner: the same bits
-  return v;
-}
-
-__device__ inline long long wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ inline int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the chunk statistics a lane gathers over the samples it reads
 struct Stats {
