@@ -9,14 +9,14 @@ into one 32768-bin row of the whole capture at RBW 610 Hz.  The same capture thr
 complex64 streams in HBM; one of them - the channel a pulsed carrier sits in - goes straight into a ZeroSpan ring, on the
 same stream, without touching the host.
 """
-import ctypes as C
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import Channelizer, ChannelSpectra, SpectrumEngine, ZeroSpan, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd import (Channelizer, ChannelSpectra, DeviceBuffer, SpectrumEngine, ZeroSpan,  # noqa: E402
+                                        _native as nat)
 
 FS, FC = 20e6, 2.45e9
 M, OS, NFFT, FRAMES = 64, 2, 1024, 4
@@ -53,17 +53,14 @@ def main():
             ZeroSpan(bank.output_rate, detector="mag", buffer_s=0.01) as zs:
         c = int(np.argmin(np.abs(bank.channel_centres() - F_PULSED)))
         n_out = bank.outputs_completed_by(SAMPLES)
-        d_in, d_y = nat._dev_alloc(0, iq.nbytes), nat._dev_alloc(0, 8 * M * n_out)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-        bank.process_device(eng, nat.IN_I8, d_in.value, SAMPLES, d_y.value, n_out)
-        zs.push_device(eng, nat.IN_C64, d_y.value + 8 * c * n_out, n_out)     # channel c's run, behind the bank
-        v = zs.view("rise", level=0.05, points=64, n_display=n_out // 2)
-        print(f"channel {c} (centre {bank.channel_centres(FC)[c] / 1e6:.4f} MHz, {bank.output_rate / 1e3:.1f} kHz wide): "
-              f"{v.total} envelope samples in the ring, triggered={v.triggered}, min {v.min:.3f}, max {v.max:.3f}, "
-              f"{v.n_rise} rising edges in the window")
-        eng.synchronize()
-        for p in (d_in, d_y):
-            nat.lib.tdsa_dev_free(0, p)
+        with DeviceBuffer.of(iq) as d_in, DeviceBuffer(8 * M * n_out) as d_y:
+            bank.process_device(eng, nat.IN_I8, d_in.ptr, SAMPLES, d_y.ptr, n_out)
+            zs.push_device(eng, nat.IN_C64, d_y.at(8 * c * n_out, 8 * n_out), n_out)     # channel c's run, behind the bank
+            v = zs.view("rise", level=0.05, points=64, n_display=n_out // 2)
+            print(f"channel {c} (centre {bank.channel_centres(FC)[c] / 1e6:.4f} MHz, {bank.output_rate / 1e3:.1f} kHz wide): "
+                  f"{v.total} envelope samples in the ring, triggered={v.triggered}, min {v.min:.3f}, max {v.max:.3f}, "
+                  f"{v.n_rise} rising edges in the window")
+            eng.synchronize()
 
 
 if __name__ == "__main__":

@@ -8,14 +8,13 @@ third of the time and a wide burst.  SpectrumEngine turns it into 2440 rows of 1
 HBM; SignalDetector reads them in place, on the engine's stream, and returns a few records per row.  Printed: the
 emissions of the last row, and the ten bins that were occupied most often with the share of the rows they were in.
 """
-import ctypes as C
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import SignalDetector, SpectrumEngine, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd import DeviceBuffer, SignalDetector, SpectrumEngine, _native as nat  # noqa: E402
 
 FS, CENTRE, NFFT, HOP = 20e6, 100e6, 16384, 8192
 FRAMES, CHUNK = 2440, 244                                            # ten calls of 244 frames
@@ -45,17 +44,15 @@ def main():
             SignalDetector(NFFT, margin_db=12.0, max_gap=4, min_width=3, max_signals=8, bins=(8, NFFT - 9)) as det:
         eng.set_window(np.hanning(NFFT).astype(np.float32))
         eng.configure(db_mode="mag", log_floor=1e-12)
-        d_rows = nat._dev_alloc(0, 4 * FRAMES * NFFT)
-        d_iq = nat._dev_alloc(0, 2 * (HOP * (CHUNK - 1) + NFFT))
-        for c in range(FRAMES // CHUNK):
-            iq = chunk_iq(c, rng)
-            eng.synchronize()                                         # the previous chunk has left d_iq
-            nat.check(nat.lib.tdsa_memcpy_h2d(0, d_iq, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-            eng.process_device(nat.IN_I8, d_iq.value, iq.size // 2, HOP, CHUNK, d_rows.value + 4 * c * CHUNK * NFFT)
-        r = det.process_device(eng, d_rows.value, FRAMES)             # behind the last chunk, on the same stream
-        counts, seen, flagged = det.occupancy()
-        for p in (d_rows, d_iq):
-            nat.lib.tdsa_dev_free(0, p)
+        with DeviceBuffer(4 * FRAMES * NFFT) as d_rows, DeviceBuffer(2 * (HOP * (CHUNK - 1) + NFFT)) as d_iq:
+            for c in range(FRAMES // CHUNK):
+                iq = chunk_iq(c, rng)
+                eng.synchronize()                                     # the previous chunk has left d_iq
+                d_iq.put(iq)
+                eng.process_device(nat.IN_I8, d_iq.ptr, iq.size // 2, HOP, CHUNK,
+                                   d_rows.at(4 * c * CHUNK * NFFT, 4 * CHUNK * NFFT))
+            r = det.process_device(eng, d_rows.ptr, FRAMES)           # behind the last chunk, on the same stream
+            counts, seen, flagged = det.occupancy()
     print(f"{FRAMES} rows of {NFFT} bins ({FS / 1e6:g} Msps around {CENTRE / 1e6:g} MHz): median noise floor "
           f"{np.median(r.floor):.1f} dB, {seen} rows seen, {flagged} flagged")
     print(f"last row: floor {r.floor[-1]:.1f} dB, threshold {r.thr[-1]:.1f} dB, {r.n_found[-1]} emissions")

@@ -9,14 +9,14 @@ decimation 2), which leaves 4 samples per symbol in HBM; SymbolSync finds the sy
 4096-sample segment and leaves one sample per symbol, derotated, next to them; Constellation reads those in place.  All
 three run on one engine stream; per segment three numbers and an EVM come back to the host.
 """
-import ctypes as C
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import Constellation, DownConverter, SpectrumEngine, SymbolSync, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd import (Constellation, DeviceBuffer, DownConverter, SpectrumEngine, SymbolSync,  # noqa: E402
+                                        _native as nat)
 from topdogspectrumanalyser_amd.analytics import constellation_points  # noqa: E402
 from topdogspectrumanalyser_amd.symbols import rrc_taps  # noqa: E402
 
@@ -49,14 +49,11 @@ def main():
             Constellation(modulation=mod) as cst:
         K = sync.symbols_per_segment(SEG)
         ny = (x.size + D - 1) // D
-        d_x, d_y, d_s = nat._dev_alloc(0, x.nbytes), nat._dev_alloc(0, 8 * ny), nat._dev_alloc(0, 8 * K * N_SEG)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_x, x.ctypes.data_as(C.c_void_p), x.nbytes))
         skip = 8 * ddc.first_full_output                             # past the matched filter's fill, 8-byte samples
-        ddc.process_device(eng, nat.IN_C64, d_x.value, x.size, d_y.value)
-        r = sync.process_device(eng, d_y.value + skip, SEG, SEG, N_SEG, d_s.value, K)       # behind it, on the same stream
-        _, evm = cst.process_segments(eng, d_s.value, nat.IN_C64, K, K, N_SEG)              # K symbols per segment, in place
-        for p in (d_x, d_y, d_s):
-            nat.lib.tdsa_dev_free(0, p)
+        with DeviceBuffer.of(x) as d_x, DeviceBuffer(8 * ny) as d_y, DeviceBuffer(8 * K * N_SEG) as d_s:
+            ddc.process_device(eng, nat.IN_C64, d_x.ptr, x.size, d_y.ptr)
+            r = sync.process_device(eng, d_y.at(skip, 8 * SEG * N_SEG), SEG, SEG, N_SEG, d_s.ptr, K)   # behind it, on the same stream
+            _, evm = cst.process_segments(eng, d_s.ptr, nat.IN_C64, K, K, N_SEG)            # K symbols per segment, in place
     print(f"{mod}, {SYMBOL_RATE / 1e6:g} Msym/s at {FS / 1e6:g} Msps, {OFFSET_HZ:g} Hz off tune, noise {SNR_DB:g} dB down: "
           f"{N_SEG} segments of {SEG} samples at {SPS} samples per symbol, {K} symbols each")
     print("segment   timing (samples)   quality   carrier Hz    phase rad     lock   EVM rms")

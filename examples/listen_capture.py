@@ -9,7 +9,6 @@ of 192 kHz in HBM; the demodulator takes all of them from there on the same stre
 decimation by 4 to 48 kHz, 75 us de-emphasis - and only the audio and five numbers per channel come back to the host.
 One channel is written as a 16-bit WAV; the table lists carrier offset and deviation per channel.
 """
-import ctypes as C
 import os
 import sys
 import wave
@@ -17,7 +16,7 @@ import wave
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import Channelizer, Demodulator, SpectrumEngine, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd import Channelizer, Demodulator, DeviceBuffer, SpectrumEngine, _native as nat  # noqa: E402
 
 FS, M, OS, R = 1.536e6, 16, 2, 4
 D = M // OS
@@ -45,18 +44,13 @@ def main():
             Demodulator("fm", bank.output_rate, R, M, deemphasis=75e-6, max_host_samples=M) as dm:
         ny = bank.outputs_completed_by(n)
         na = dm.outputs_completed_by(ny)
-        d_x, d_y, d_a = nat._dev_alloc(0, x.nbytes), nat._dev_alloc(0, 8 * M * ny), nat._dev_alloc(0, 4 * M * na)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_x, x.ctypes.data_as(C.c_void_p), x.nbytes))
-        bank.process_device(eng, nat.IN_C64, d_x.value, n, d_y.value, ny)
-        dm.process_device(eng, d_y.value, ny, ny, d_a.value, na)          # behind the bank, on the same stream
-        meas = dm.measure()                                               # waits for both
-        audio = np.empty(na, np.float32)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, audio.ctypes.data_as(C.c_void_p), C.c_void_p(d_a.value + 4 * LISTEN * na),
-                                          audio.nbytes))
+        with DeviceBuffer.of(x) as d_x, DeviceBuffer(8 * M * ny) as d_y, DeviceBuffer(4 * M * na) as d_a:
+            bank.process_device(eng, nat.IN_C64, d_x.ptr, n, d_y.ptr, ny)
+            dm.process_device(eng, d_y.ptr, ny, ny, d_a.ptr, na)          # behind the bank, on the same stream
+            meas = dm.measure()                                           # waits for both
+            audio = d_a.get(na, np.float32, 4 * LISTEN * na)
         rate = dm.audio_rate
         skip = dm.first_full_output + bank.first_full_output // R + 1
-        for p in (d_x, d_y, d_a):
-            nat.lib.tdsa_dev_free(0, p)
 
     audio = audio[skip:]
     pcm = np.clip(np.round(audio / max(float(np.abs(audio).max()), 1e-12) * 0.8 * 32767), -32768, 32767).astype("<i2")

@@ -1,6 +1,6 @@
 """GPU parity of the trace analytics / display accumulators against
 oracle/analytics_oracle.py and the vectors captured from the imported reference."""
-import ctypes as C
+import contextlib
 import os
 
 import numpy as np
@@ -8,6 +8,7 @@ import pytest
 
 from oracle import analytics_oracle as ao
 from oracle import spectrum_oracle as so
+from topdogspectrumanalyser_amd import DeviceBuffer
 
 pytestmark = pytest.mark.gpu
 
@@ -29,22 +30,11 @@ def gold(golden_dir):
     return np.load(os.path.join(golden_dir, "analytics.npz"))
 
 
-class DevRows:
-    """rows uploaded to the device for the duration of a with-block"""
-
-    def __init__(self, pkg, rows):
-        self.nat = pkg._native
-        self.rows = np.ascontiguousarray(rows, dtype=np.float32)
-        self.ptr = C.c_void_p()
-
-    def __enter__(self):
-        nat = self.nat
-        nat.check(nat.lib.tdsa_dev_alloc(0, self.rows.nbytes, C.byref(self.ptr)))
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, self.ptr, self.rows.ctypes.data_as(C.c_void_p), self.rows.nbytes))
-        return self.ptr.value
-
-    def __exit__(self, *exc):
-        self.nat.lib.tdsa_dev_free(0, self.ptr)
+@contextlib.contextmanager
+def _device_rows(rows):
+    """the address of the rows, as float32, on the device for the duration of a with-block"""
+    with DeviceBuffer.of(np.asarray(rows, dtype=np.float32)) as buf:
+        yield buf.ptr
 
 
 def test_top_peaks_match_reference_vectors(pkg, an, gold):
@@ -53,7 +43,7 @@ def test_top_peaks_match_reference_vectors(pkg, an, gold):
         n, kind, exc = key.split("_")[1:]
         n = int(n)
         tr = gold[key + "_trace"]
-        with pkg.SpectrumEngine(max(n, 64), max_frames=1) as e, DevRows(pkg, tr[None, :]) as d:
+        with pkg.SpectrumEngine(max(n, 64), max_frames=1) as e, _device_rows(tr[None, :]) as d:
             bins, db = an.rows_top_peaks(e, d, 1, n_bins=n, n=5, min_excursion_db=float(exc))
         want = list(gold[key + "_bins"])
         got = [int(b) for b in bins[0] if b >= 0]
@@ -71,7 +61,7 @@ def test_top_peaks_batch_on_spectra(pkg, an):
         e.set_window(so.hackrf_window(nfft))
         e.configure(db_mode="mag", log_floor=so.LOG_FLOOR, dc_alpha=1.0)
         rows = e.process(iq, hop=hop)
-        with DevRows(pkg, rows) as d:
+        with _device_rows(rows) as d:
             for exc in (6.0, 10.0):
                 bins, db = an.rows_top_peaks(e, d, nf, min_excursion_db=exc)
                 for r in range(nf):
@@ -85,7 +75,7 @@ def test_rows_stats_peak_argmax_band(pkg, an, gold):
     rng = np.random.default_rng(5)
     rows = np.stack([tr, tr[::-1].copy(), np.roll(tr, 100), rng.normal(-80, 5, tr.size).astype(np.float32)])
     rows[1, 7] = rows[1, 900] = rows[1].max() + 1.0          # equal maxima: first index wins
-    with pkg.SpectrumEngine(4096, max_frames=4) as e, DevRows(pkg, rows) as d:
+    with pkg.SpectrumEngine(4096, max_frames=4) as e, _device_rows(rows) as d:
         for (a, b), want in zip(gold["band_edges"], gold["band_db"]):
             peak, pbin, bdb = an.rows_stats(e, d, 4, freq_bins=bins, band=(a, b))
             for r in range(4):
@@ -101,7 +91,7 @@ def test_rows_stats_peak_argmax_band(pkg, an, gold):
         assert bdb is None and pbin[1] == 7
     nanrow = tr.copy()
     nanrow[[300, 20]] = np.nan
-    with pkg.SpectrumEngine(4096, max_frames=1) as e, DevRows(pkg, nanrow[None, :]) as d:
+    with pkg.SpectrumEngine(4096, max_frames=1) as e, _device_rows(nanrow[None, :]) as d:
         peak, pbin, _ = an.rows_stats(e, d, 1)
         assert np.isnan(peak[0]) and pbin[0] == 20 == int(np.argmax(nanrow))    # numpy: first NaN
 
@@ -110,10 +100,10 @@ def test_duty_cycle_from_device_rows(pkg, an, gold):
     frames = gold["duty_frames"]
     d = an.DutyCycle()
     with pkg.SpectrumEngine(1024, max_frames=130) as e:
-        with DevRows(pkg, frames[:130]) as a:
+        with _device_rows(frames[:130]) as a:
             d.update_from_rows(e, a, 130, threshold_dbm=-60.0)
         assert d.duty_pct == gold["duty_pct"][129]
-        with DevRows(pkg, frames[130:]) as b:
+        with _device_rows(frames[130:]) as b:
             d.update_from_rows(e, b, 130, threshold_dbm=-45.0)
     ref = ao.DutyCycleOracle()
     for i, fr in enumerate(frames):
@@ -139,7 +129,7 @@ def test_density_histogram_matches_restatement(pkg, an, decay):
     ref = ao.DensityOracle(decay)
     for r in rows:
         ref.update(r)
-    with an.DensityHistogram(n, decay) as dh, DevRows(pkg, rows) as d:
+    with an.DensityHistogram(n, decay) as dh, _device_rows(rows) as d:
         dh.update_rows(None, d, nf)
         h = dh.hist()
         assert h.shape == (n, ao.AMP_BINS)
@@ -180,7 +170,7 @@ def test_density_histogram_random(pkg, an, seed):
                 rows = np.round(rows * 512 / 300) * np.float32(300 / 512) - np.float32(200.0) + np.float32(200.0)   # near bin edges
             for r in rows:
                 ref.update(r)
-            with DevRows(pkg, rows) as d:
+            with _device_rows(rows) as d:
                 dh.update_rows(None, d, nf)
             assert np.array_equal(dh.hist(), ref.hist), (seed, n, decay, nf)
 
@@ -193,19 +183,14 @@ def test_density_from_engine_rows(pkg, an):
         e.set_window(so.hackrf_window(nfft))
         e.configure(db_mode="mag", log_floor=so.LOG_FLOOR, dc_alpha=1.0)
         rows = e.process(iq, hop=nfft)
-        d_in, d_out = C.c_void_p(), C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(d_in)))
-        nat.check(nat.lib.tdsa_dev_alloc(0, rows.nbytes, C.byref(d_out)))
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-        e.set_overlap(2)
-        e.process_device(nat.IN_I8, d_in.value, nfft * nf, nfft, nf, d_out.value)
-        dh.update_rows(e, d_out.value, nf)                   # ordered after the producer by the library
-        ref = ao.DensityOracle(0.9)
-        for r in rows:
-            ref.update(r)
-        assert np.array_equal(dh.hist(), ref.hist)
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)
+        with DeviceBuffer.of(iq) as d_in, DeviceBuffer(rows.nbytes) as d_out:
+            e.set_overlap(2)
+            e.process_device(nat.IN_I8, d_in.ptr, nfft * nf, nfft, nf, d_out.ptr)
+            dh.update_rows(e, d_out.ptr, nf)                 # ordered after the producer by the library
+            ref = ao.DensityOracle(0.9)
+            for r in rows:
+                ref.update(r)
+            assert np.array_equal(dh.hist(), ref.hist)
 
 
 def test_waterfall_ring_matches_restatement(pkg, an):
@@ -225,7 +210,7 @@ def test_waterfall_ring_matches_restatement(pkg, an):
         assert np.array_equal(wf.view(), ref.view(), equal_nan=True)
         rest = np.stack(seq[9:])
         n_ref = sum(ref.update(r) for r in rest)
-        with DevRows(pkg, rest) as d:
+        with _device_rows(rest) as d:
             assert wf.push_rows(None, d, len(rest)) == n_ref      # batch larger than the history
         assert wf.ptr == ref.ptr
         assert np.array_equal(wf.view(), ref.view(), equal_nan=True)
@@ -253,7 +238,7 @@ def test_waterfall_ring_random(pkg, an, seed):
                     assert wf.push(r) == ref.update(r)
             else:
                 want = sum(ref.update(r) for r in rows)
-                with DevRows(pkg, rows) as d:
+                with _device_rows(rows) as d:
                     assert wf.push_rows(None, d, len(rows)) == want
             assert wf.ptr == ref.ptr
             assert np.array_equal(wf.view(), ref.view(), equal_nan=True), (seed, H, W)
@@ -278,7 +263,7 @@ def test_waterfall_ring_long_batches(pkg, an, H, W, k):
             picks = np.repeat(picks, rng.integers(1, 4, k))[:k]
             rows = np.ascontiguousarray(pool[picks])
             want = sum(ref.update(r) for r in rows)
-            with DevRows(pkg, rows) as d:
+            with _device_rows(rows) as d:
                 assert wf.push_rows(None, d, k) == want
             assert wf.ptr == ref.ptr
             assert np.array_equal(wf.view(), ref.view(), equal_nan=True)
@@ -302,7 +287,7 @@ def test_rows_stats_random(pkg, an, seed):
     a, b = sorted(rng.uniform(95e6, 125e6, 2))
     if rng.integers(0, 6) == 0:
         a, b = 130e6, 140e6                                     # no bin inside
-    with pkg.SpectrumEngine(max(n, 64), max_frames=1) as e, DevRows(pkg, rows) as d:
+    with pkg.SpectrumEngine(max(n, 64), max_frames=1) as e, _device_rows(rows) as d:
         peak, pbin, bdb = an.rows_stats(e, d, nr, n_bins=n, freq_bins=bins, band=(a, b))
     for r in range(nr):
         want_bin = int(np.argmax(rows[r]))
@@ -326,7 +311,7 @@ def test_density_histogram_matches_reference_fixture(pkg, an, golden_dir, mode):
     with an.DensityHistogram(rows.shape[1], decay) as dh:
         for i, r in enumerate(g["density_snap_rows"]):
             chunk = np.ascontiguousarray(rows[prev:int(r) + 1])
-            with DevRows(pkg, chunk) as d:
+            with _device_rows(chunk) as d:
                 dh.update_rows(None, d, len(chunk))         # batch entry point, state carried across calls
             assert np.array_equal(dh.hist(), g[f"density_{mode}_hist"][i]), (mode, int(r))
             prev = int(r) + 1
@@ -350,14 +335,14 @@ def test_waterfall_ring_matches_reference_fixture(pkg, an, golden_dir):
                 assert np.array_equal(wf.view(), g["wf_views"][steps[step]])
     with an.WaterfallRing(H, W, float(g["wf_min_db"])) as wf:    # the same sequence as ONE device batch
         seq = np.ascontiguousarray(g["wf_rows"][g["wf_order"]])
-        with DevRows(pkg, seq) as d:
+        with _device_rows(seq) as d:
             assert wf.push_rows(None, d, len(seq)) == int(g["wf_added"].sum())
         assert wf.ptr == int(g["wf_ptr"][-1])
         assert np.array_equal(wf.view(), g["wf_views"][-1])
 
 
 def test_analytics_error_paths(pkg, an):
-    with pkg.SpectrumEngine(1024, max_frames=1) as e, DevRows(pkg, np.zeros((1, 1024), np.float32)) as d:
+    with pkg.SpectrumEngine(1024, max_frames=1) as e, _device_rows(np.zeros((1, 1024), np.float32)) as d:
         with pytest.raises(Exception):
             an.rows_top_peaks(e, d, 1, n=9)
         with pytest.raises(Exception):
@@ -394,7 +379,7 @@ def test_top_peaks_random_traces(pkg, an, seed):
     exc = float(rng.choice([3.0, 6.0, 10.0]))
     sep = int(rng.choice([max(10, n // 50), 2, 5, 600, 31, 33]))  # (600: wider than the stride of a thread's bins)
     npk = int(rng.integers(1, 9))
-    with pkg.SpectrumEngine(64 if n < 64 else 1 << (n - 1).bit_length(), max_frames=1) as e, DevRows(pkg, rows) as d:
+    with pkg.SpectrumEngine(64 if n < 64 else 1 << (n - 1).bit_length(), max_frames=1) as e, _device_rows(rows) as d:
         bins, db = an.rows_top_peaks(e, d, len(rows), n_bins=n, n=npk, min_sep_bins=sep, min_excursion_db=exc)
     for r, tr in enumerate(rows):
         want = ao.find_top_peak_bins(tr, npk, sep, exc)
@@ -426,7 +411,7 @@ def test_marker_peaks_match_reference_vectors(pkg, an, markers):
         thr, exc, dist, start = markers[key + "_params"]
         want_pk, want_prom = markers[key + "_peaks"], markers[key + "_prom"]
         cap = max(len(want_pk) + 3, 8)
-        with pkg.SpectrumEngine(max(1 << (n - 1).bit_length(), 64), max_frames=1) as e, DevRows(pkg, tr[None, :]) as d:
+        with pkg.SpectrumEngine(max(1 << (n - 1).bit_length(), 64), max_frames=1) as e, _device_rows(tr[None, :]) as d:
             kw = {} if bool(markers[key + "_defaults"]) else dict(peak_threshold=float(thr), peak_excursion=float(exc))
             r = an.rows_marker_peaks(e, d, 1, n_bins=n, current_idx=int(start), max_list=cap, **kw)
             assert r["n_peaks"][0] == len(want_pk), key
@@ -484,7 +469,7 @@ def test_marker_peaks_random_traces(pkg, an, seed):
     exc = float(rng.choice([0.0, 3.0, 6.0, 10.0, 6.3, 0.7, 1e-3, 2.5000001, 250.0]))   # (exact and inexact against 0.5 dB steps)
     dist = int(rng.choice([1, 2, 3, 3, 3, 7, 40]))
     cur = int(rng.integers(-1, n + 1))
-    with pkg.SpectrumEngine(64, max_frames=1) as e, DevRows(pkg, rows) as d:
+    with pkg.SpectrumEngine(64, max_frames=1) as e, _device_rows(rows) as d:
         r = an.rows_marker_peaks(e, d, len(rows), n_bins=n, peak_threshold=thr, peak_excursion=exc, distance=dist,
                                  current_idx=cur, max_list=n // 2 + 1)
     for i, tr in enumerate(rows):
@@ -504,7 +489,7 @@ def test_marker_peaks_on_spectra_and_errors(pkg, an):
         e.set_window(so.hackrf_window(nfft))
         e.configure(db_mode="mag", log_floor=so.LOG_FLOOR, dc_alpha=1.0)
         rows = e.process(iq, hop=hop)
-        with DevRows(pkg, rows) as d:
+        with _device_rows(rows) as d:
             r = an.rows_marker_peaks(e, d, nf, current_idx=nfft // 2, max_list=nfft // 2)
             for i in range(nf):
                 pk, _, prom = ao.marker_find_peaks(rows[i])
@@ -570,7 +555,7 @@ def test_frame_stats_fused_match_rows(pkg, an, nfft, fmt):
             rows = e.process(iq, hop=hop)
             _check_frame_stats(e, rows, lo, hi, (nfft, fmt, k, lo, hi))
             # the same scalars as tdsa_rows_stats of those rows
-            with DevRows(pkg, rows) as d:
+            with _device_rows(rows) as d:
                 fb = np.arange(nfft, dtype=np.float64)
                 peak, pbin, bdb = an.rows_stats(e, d, nf, freq_bins=fb, band=(lo, hi) if lo <= hi else None)
             p2, b2, band2 = e.frame_stats(bin_width=1.0)
@@ -650,37 +635,28 @@ def test_frame_stats_full_c3_second_and_overlapped_calls(pkg, an):
     nfft, hop, nf = 16384, 8192, 2440
     n_samples = hop * (nf - 1) + nfft
     iq = so.synth_iq_int8(n_samples, nfft, seed=3)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_dev_alloc(0, nf * nfft * 4, C.byref(d_out)))
-    try:
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-        with pkg.SpectrumEngine(nfft, max_frames=nf) as e:
-            e.set_window(so.hackrf_window(nfft))
-            e.configure(db_mode="mag", log_floor=so.LOG_FLOOR, dc_alpha=1.0, hold_max=True)
-            lo, hi = 3000, 11000
-            e.set_frame_stats(True, (lo, hi))
-            e.process_device(nat.IN_I8, d_in.value, n_samples, hop, nf, d_out.value)
-            peak, pbin, band = e.frame_stats(bin_width=1.0)
-            rp, rb, rband = an.rows_stats(e, d_out.value, nf, freq_bins=np.arange(nfft, dtype=np.float64), band=(lo, hi))
-            assert np.array_equal(peak, rp) and np.array_equal(pbin, rb)
-            assert np.max(np.abs(band - rband)) <= 5e-5
-            mx, _ = e.hold()
-            rows = np.empty((nf, nfft), dtype=np.float32)
-            nat.check(nat.lib.tdsa_memcpy_d2h(0, rows.ctypes.data_as(C.c_void_p), d_out, rows.nbytes))
-            assert np.array_equal(mx, rows.max(axis=0))           # the hold trace is untouched by the extra epilogue
-            assert peak.max() == mx.max()
-            # overlapped calls of different lengths: each slot keeps its own call
-            e.set_overlap(3)
-            lens = [2440, 1000, 37]
-            for n in lens:
-                e.process_device(nat.IN_I8, d_in.value, hop * (n - 1) + nfft, hop, n, None)
-            for back, n in enumerate(reversed(lens)):
-                p2, b2, _ = e.frame_stats(calls_back=back)
-                assert len(p2) == n and np.array_equal(p2, peak[:n]) and np.array_equal(b2, pbin[:n])
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)
+    with DeviceBuffer.of(iq) as d_in, DeviceBuffer(nf * nfft * 4) as d_out, pkg.SpectrumEngine(nfft, max_frames=nf) as e:
+        e.set_window(so.hackrf_window(nfft))
+        e.configure(db_mode="mag", log_floor=so.LOG_FLOOR, dc_alpha=1.0, hold_max=True)
+        lo, hi = 3000, 11000
+        e.set_frame_stats(True, (lo, hi))
+        e.process_device(nat.IN_I8, d_in.ptr, n_samples, hop, nf, d_out.ptr)
+        peak, pbin, band = e.frame_stats(bin_width=1.0)
+        rp, rb, rband = an.rows_stats(e, d_out.ptr, nf, freq_bins=np.arange(nfft, dtype=np.float64), band=(lo, hi))
+        assert np.array_equal(peak, rp) and np.array_equal(pbin, rb)
+        assert np.max(np.abs(band - rband)) <= 5e-5
+        mx, _ = e.hold()
+        rows = d_out.get((nf, nfft), np.float32)
+        assert np.array_equal(mx, rows.max(axis=0))           # the hold trace is untouched by the extra epilogue
+        assert peak.max() == mx.max()
+        # overlapped calls of different lengths: each slot keeps its own call
+        e.set_overlap(3)
+        lens = [2440, 1000, 37]
+        for n in lens:
+            e.process_device(nat.IN_I8, d_in.ptr, hop * (n - 1) + nfft, hop, n, None)
+        for back, n in enumerate(reversed(lens)):
+            p2, b2, _ = e.frame_stats(calls_back=back)
+            assert len(p2) == n and np.array_equal(p2, peak[:n]) and np.array_equal(b2, pbin[:n])
 
 
 def test_frame_stats_batched_captures(pkg):
@@ -689,23 +665,14 @@ def test_frame_stats_batched_captures(pkg):
     nfft, hop, nf, nseg = 8192, 8192, 32, 5
     per = hop * (nf - 1) + nfft
     iq = so.synth_iq_int8(per * nseg, nfft, seed=9)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_dev_alloc(0, nseg * nf * nfft * 4, C.byref(d_out)))
-    try:
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-        with pkg.SpectrumEngine(nfft, max_frames=nf) as e:
-            e.set_window(np.hanning(nfft).astype(np.float32))
-            e.configure(db_mode="pow", power_scale=1.0, log_floor=1e-10, dc_alpha=-1.0)
-            e.set_frame_stats(True, (10, 8000))
-            e.process_device_batch(nat.IN_I8, d_in.value, per * 2, nseg, per, hop, nf, d_out.value)
-            rows = np.empty((nseg * nf, nfft), dtype=np.float32)
-            e.synchronize()
-            nat.check(nat.lib.tdsa_memcpy_d2h(0, rows.ctypes.data_as(C.c_void_p), d_out, rows.nbytes))
-            _check_frame_stats(e, rows, 10, 8000, "batch")
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)
+    with DeviceBuffer.of(iq) as d_in, DeviceBuffer(nseg * nf * nfft * 4) as d_out, pkg.SpectrumEngine(nfft, max_frames=nf) as e:
+        e.set_window(np.hanning(nfft).astype(np.float32))
+        e.configure(db_mode="pow", power_scale=1.0, log_floor=1e-10, dc_alpha=-1.0)
+        e.set_frame_stats(True, (10, 8000))
+        e.process_device_batch(nat.IN_I8, d_in.ptr, per * 2, nseg, per, hop, nf, d_out.ptr)
+        e.synchronize()
+        rows = d_out.get((nseg * nf, nfft), np.float32)
+        _check_frame_stats(e, rows, 10, 8000, "batch")
 
 
 # ---- levels -> uint8 views (what ImageItem.setImage makes of the images before the colour table) -------------------

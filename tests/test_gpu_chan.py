@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import chan_contract as cc
-from topdogspectrumanalyser_amd import SpectrumEngine, ZeroSpan, _native as nat
+from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine, ZeroSpan, _native as nat
 from topdogspectrumanalyser_amd.channelizer import Channelizer, ChannelSpectra
 from topdogspectrumanalyser_amd.utils.constants import DSPConstants
 from topdogspectrumanalyser_amd.zoom import design_decimator, zoom_window
@@ -51,34 +51,6 @@ def _raw(rng, n, fmt):
     if fmt == cc.FMT_U8:
         return rng.integers(0, 256, 2 * n).astype(np.uint8)
     return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.3).astype(np.complex64)
-
-
-class _Dev:
-    """A device buffer (freed on exit)."""
-
-    def __init__(self, a=None, nbytes=0):
-        self.p = C.c_void_p()
-        a = None if a is None else np.ascontiguousarray(a)
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes if a is None else a.nbytes), 16), C.byref(self.p)))
-        if a is not None:
-            self.put(a)
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-        return self
-
-    def get(self, n, dtype, offset=0):
-        out = np.empty(n, dtype=dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.p.value + offset),
-                                          out.nbytes))
-        return out
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 def _bits(y):
@@ -175,10 +147,10 @@ def test_against_the_float64_contract(M, os_, T):
 def _device_run(bank, raw, fmt, pieces, n_out, engine=None):
     """The block piece by piece through process_device, every piece's outputs behind those before it."""
     bps = 8 if fmt == cc.FMT_C64 else 2
-    with _Dev(raw) as d_in, _Dev(nbytes=8 * bank.channels * n_out) as d_out:
+    with DeviceBuffer.of(raw) as d_in, DeviceBuffer(8 * bank.channels * n_out) as d_out:
         got = at = 0
         for k in pieces:
-            got += bank.process_device(engine, fmt, d_in.p.value + bps * at, k, d_out.p.value + 8 * got, n_out)
+            got += bank.process_device(engine, fmt, d_in.at(bps * at, bps * k), k, d_out.at(8 * got), n_out)
             at += k
         bank.reset()                                    # waits for the handle's work
         assert got == n_out
@@ -249,13 +221,13 @@ def test_streams_past_2_32_inputs(M, os_):
     raw = _long_block()
     checked = (127, 128, 255, 256)
     cap = nb // D + 2
-    with Channelizer(M, FS, os_, max_host_samples=64) as bank, _Dev(raw) as d_in, \
-            _Dev(nbytes=8 * M * cap * (1 + len(checked))) as d_y:
+    with Channelizer(M, FS, os_, max_host_samples=64) as bank, DeviceBuffer.of(raw) as d_in, \
+            DeviceBuffer(8 * M * cap * (1 + len(checked))) as d_y:
         h = bank.taps
         total, spans = 0, []
         for i in range(reps):                               # every other call overwrites slot 0
             slot = 1 + checked.index(i) if i in checked else 0
-            k = bank.process_device(None, cc.FMT_I8, d_in.p.value, nb, d_y.p.value + 8 * M * cap * slot, cap)
+            k = bank.process_device(None, cc.FMT_I8, d_in.ptr, nb, d_y.at(8 * M * cap * slot), cap)
             assert k <= cap
             if slot:
                 spans.append((total, k, slot))
@@ -361,8 +333,8 @@ def test_stride_leaves_the_gaps_alone(branches):
                                             host.ctypes.data_as(C.c_void_p), stride, int(branches), C.byref(cnt)))
         assert cnt.value == n_out
         bank.reset()
-        with _Dev(raw) as d_in, _Dev(np.full((M + 1, stride), sentinel, dtype=np.complex64)) as d_out:
-            assert bank.process_device(None, cc.FMT_I8, d_in.p.value, n, d_out.p.value, stride, branches) == n_out
+        with DeviceBuffer.of(raw) as d_in, DeviceBuffer.of(np.full((M + 1, stride), sentinel, dtype=np.complex64)) as d_out:
+            assert bank.process_device(None, cc.FMT_I8, d_in.ptr, n, d_out.ptr, stride, branches) == n_out
             bank.reset()
             dev = d_out.get((M + 1) * stride, np.complex64).reshape(M + 1, stride)
     for got in (host, dev):
@@ -384,16 +356,16 @@ def _spectra_rows_are_the_engine(M, os_):
         with pytest.raises(ValueError):
             cs.process(np.zeros(D * nfft, np.float32))       # real input
         with Channelizer(M, FS, os_, max_host_samples=3 * D * nfft) as bank, \
-                SpectrumEngine(nfft, max_frames=3) as eng, _Dev(nbytes=4 * 3 * nfft) as d_rows:
+                SpectrumEngine(nfft, max_frames=3) as eng, DeviceBuffer(4 * 3 * nfft) as d_rows:
             eng.set_window(zoom_window(nfft))
             eng.configure(db_mode="mag", log_floor=DSPConstants.LOG_FLOOR, dc_alpha=-1.0)
             for b, got in zip(blocks, rows):
                 F = got.shape[1]
                 y = bank.process(b)
                 assert y.shape == (M, F * nfft)
-                with _Dev(y) as d_y:
+                with DeviceBuffer.of(y) as d_y:
                     for c in range(M):
-                        eng.process_device(nat.IN_C64, d_y.p.value + 8 * c * F * nfft, F * nfft, nfft, F, d_rows.p.value)
+                        eng.process_device(nat.IN_C64, d_y.at(8 * c * F * nfft, 8 * F * nfft), F * nfft, nfft, F, d_rows.ptr)
                         eng.synchronize()
                         want = d_rows.get(F * nfft, np.float32).reshape(F, nfft)
                         assert np.array_equal(got[c].view(np.uint32), want.view(np.uint32)), c
@@ -437,16 +409,16 @@ def _order_run(streams):
     h = _float_taps(M, 3 * M)
     with Channelizer(M, 64.0 * M, os_, taps=h, max_host_samples=64) as bank:
         n_out = bank.outputs_completed_by(x.size)
-        with _Dev(x) as d_in, _Dev(nbytes=8 * M * n_out) as d_out:
+        with DeviceBuffer.of(x) as d_in, DeviceBuffer(8 * M * n_out) as d_out:
             got = 0
             for i, eng in enumerate(streams):
-                got += bank.process_device(eng, cc.FMT_C64, d_in.p.value + 8 * 10 * i, 10, d_out.p.value + 8 * got, n_out)
+                got += bank.process_device(eng, cc.FMT_C64, d_in.at(8 * 10 * i, 8 * 10), 10, d_out.at(8 * got), n_out)
             assert got == n_out
             if streams[-1] is None:
                 bank.reset()                # the reference run: wait for the bank, the consumer has a stream of its own
             # a consumer on the last producer's stream, behind the bank's work there: zero span of channel 1
             with ZeroSpan(64.0, detector="mag", buffer_s=1.0, max_host_samples=64) as zs:
-                assert zs.push_device(streams[-1], nat.IN_C64, d_out.p.value + 8 * n_out, n_out) == n_out
+                assert zs.push_device(streams[-1], nat.IN_C64, d_out.at(8 * n_out, 8 * n_out), n_out) == n_out
                 view = zs.view("free_run", n_display=n_out)
             bank.reset()
             y = d_out.get(M * n_out, np.complex64).reshape(M, n_out)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import constellation_contract as cc
+from topdogspectrumanalyser_amd import DeviceBuffer
 
 pytestmark = pytest.mark.gpu
 
@@ -122,26 +123,6 @@ def test_nan_block(cst):
     assert cc.readout(res.evm_rms, "qpsk") == ""
 
 
-def _to_dev(arr):
-    from topdogspectrumanalyser_amd import _native as nat
-    p = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, arr.nbytes, C.byref(p)))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes))
-    return p
-
-
-def _from_dev(p, off, shape, dtype):
-    from topdogspectrumanalyser_amd import _native as nat
-    out = np.empty(shape, dtype=dtype)
-    nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), C.c_void_p(p.value + int(off)), out.nbytes))
-    return out
-
-
-def _free(p):
-    from topdogspectrumanalyser_amd import _native as nat
-    nat.check(nat.lib.tdsa_dev_free(0, p))
-
-
 @pytest.mark.parametrize("mod", ["64qam", "qpsk"])
 def test_c3_capture_in_hbm(cst, mod):
     """20 M int8 samples in HBM as 16 384-sample ticks: per-segment rms / EVM and histograms are the reference's."""
@@ -152,20 +133,14 @@ def test_c3_capture_in_hbm(cst, mod):
                   -128, 127).astype(np.int8)
     cst.set_modulation(mod)
     cst.set_range(1.5)
-    d_in = _to_dev(raw)
-    d_cnt = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, n_seg * 128 * 128 * 4, C.byref(d_cnt)))
-    try:
-        rms, evm = cst.process_segments(None, d_in.value, nat.IN_I8, seg, seg, n_seg, d_cnt.value)
+    with DeviceBuffer.of(raw) as d_in, DeviceBuffer(n_seg * 128 * 128 * 4) as d_cnt:
+        rms, evm = cst.process_segments(None, d_in.ptr, nat.IN_I8, seg, seg, n_seg, d_cnt.ptr)
         for s in list(rng.choice(n_seg, 10, replace=False)) + [0, n_seg - 1]:
             want = cc.evaluate(cc.to_complex(raw[2 * s * seg:2 * (s + 1) * seg], cc.IN_I8), mod, 1.5)
             assert rms[s] == want["rms"] and evm[s] == want["evm"], (s, rms[s], want["rms"], evm[s], want["evm"])
             if s % 3 == 0 or s in (0, n_seg - 1):
-                got = _from_dev(d_cnt, s * 128 * 128 * 4, (128, 128), np.uint32)
+                got = d_cnt.get((128, 128), np.uint32, s * 128 * 128 * 4)
                 assert np.array_equal(got, want["counts"]), s
-    finally:
-        _free(d_in)
-        _free(d_cnt)
 
 
 def test_overlapping_odd_segments_equal_host_blocks(cst):
@@ -177,18 +152,12 @@ def test_overlapping_odd_segments_equal_host_blocks(cst):
           ).astype(np.complex64)
     cst.set_modulation("8psk")
     cst.set_range(2.0)
-    d_in = _to_dev(iq)
-    d_cnt = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, n_seg * 128 * 128 * 4, C.byref(d_cnt)))
-    try:
-        rms, evm = cst.process_segments(None, d_in.value, nat.IN_C64, seg, hop, n_seg, d_cnt.value)
+    with DeviceBuffer.of(iq) as d_in, DeviceBuffer(n_seg * 128 * 128 * 4) as d_cnt:
+        rms, evm = cst.process_segments(None, d_in.ptr, nat.IN_C64, seg, hop, n_seg, d_cnt.ptr)
         for s in range(n_seg):
             res = cst.process(iq[s * hop:s * hop + seg])
             assert rms[s] == res.rms and evm[s] == res.evm_rms, s
-            assert np.array_equal(_from_dev(d_cnt, s * 128 * 128 * 4, (128, 128), np.uint32), res.counts), s
-    finally:
-        _free(d_in)
-        _free(d_cnt)
+            assert np.array_equal(d_cnt.get((128, 128), np.uint32, s * 128 * 128 * 4), res.counts), s
 
 
 def test_hot_bin_counts_exactly(cst):
@@ -197,12 +166,9 @@ def test_hot_bin_counts_exactly(cst):
     raw = np.tile(np.array([40, -40], np.int8), n)
     cst.set_modulation("qpsk")
     cst.set_range(1.5)
-    d_in = _to_dev(raw)
-    d_cnt = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, 128 * 128 * 4, C.byref(d_cnt)))
-    try:
-        rms, evm = cst.process_segments(None, d_in.value, nat.IN_I8, n, n, 1, d_cnt.value)
-        got = _from_dev(d_cnt, 0, (128, 128), np.uint32)
+    with DeviceBuffer.of(raw) as d_in, DeviceBuffer(128 * 128 * 4) as d_cnt:
+        rms, evm = cst.process_segments(None, d_in.ptr, nat.IN_I8, n, n, 1, d_cnt.ptr)
+        got = d_cnt.get((128, 128), np.uint32)
         assert int(got.max()) == n and int(got.sum()) == n
         x = cc.to_complex(raw[:2], cc.IN_I8)                 # every sample: the same |x|^2, summed 2^24 times
         a = cc.cabs(x)
@@ -212,9 +178,6 @@ def test_hot_bin_counts_exactly(cst):
         i = (x.real + x.imag * np.float32(0)) * scl
         q = (x.imag - x.real * np.float32(0)) * scl
         assert np.array_equal(np.argwhere(got), np.argwhere(cc.histogram(i, q, 1.5)))
-    finally:
-        _free(d_in)
-        _free(d_cnt)
 
 
 def test_error_paths_leave_the_handle_usable(cst):

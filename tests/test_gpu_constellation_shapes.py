@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 import constellation_contract as cc
+from device_room import room_or_skip
+from topdogspectrumanalyser_amd import DeviceBuffer
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]        # every test under a time limit of its own
 
@@ -36,38 +38,6 @@ def cst(handle):
 def _nat():
     from topdogspectrumanalyser_amd import _native as nat
     return nat
-
-
-class _Dev:
-    """A device buffer of nbytes.  skip_if_full (the 4 GiB buffers only): the test skips when the device has no room
-    for it, and for nothing else; every other allocation that fails is an error."""
-
-    def __init__(self, nbytes, skip_if_full=False):
-        nat = _nat()
-        self.p = C.c_void_p()
-        rc = nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(self.p))
-        if rc != 0 and skip_if_full and b"out of memory" in nat.lib.tdsa_last_error_string().lower():
-            pytest.skip(f"no room for {nbytes} bytes on the device: {nat.lib.tdsa_last_error_string().decode()}")
-        nat.check(rc)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        _nat().check(_nat().lib.tdsa_dev_free(0, self.p))
-
-    def put(self, arr, off=0):
-        arr = np.ascontiguousarray(arr)
-        nat = _nat()
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, C.c_void_p(self.p.value + int(off)), arr.ctypes.data_as(C.c_void_p),
-                                          arr.nbytes))
-
-    def get(self, off, shape, dtype):
-        out = np.empty(shape, dtype=dtype)
-        nat = _nat()
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.p.value + int(off)),
-                                          out.nbytes))
-        return out
 
 
 def _bits(a, b, dt):
@@ -327,15 +297,15 @@ def test_empty_table_oversized_table_and_non_finite_points(cst):
     assert none["evm"] is None and np.array_equal(none["counts"], want["counts"])
     _check(cst.process(iq, n_tail=100), none, "no table", n_tail=100)
     seg, hop, n_seg = 4000, 2500, 3
-    with _Dev(iq.nbytes) as d_in, _Dev(n_seg * 128 * 128 * 4) as d_cnt:
+    with DeviceBuffer(iq.nbytes) as d_in, DeviceBuffer(n_seg * 128 * 128 * 4) as d_cnt:
         d_in.put(iq)
         d_cnt.put(np.full(n_seg * 128 * 128, 0xFFFFFFFF, np.uint32))
-        rms, evm = cst.process_segments(None, d_in.p.value, nat.IN_C64, seg, hop, n_seg, d_cnt.p.value)
+        rms, evm = cst.process_segments(None, d_in.ptr, nat.IN_C64, seg, hop, n_seg, d_cnt.ptr)
         assert np.isnan(evm).all()
         for s in range(n_seg):
             w = cc.evaluate(iq[s * hop:s * hop + seg], pts=np.zeros((0, 2), np.float32))
             assert _bits(rms[s], w["rms"], np.float32), s
-            assert np.array_equal(d_cnt.get(s * 128 * 128 * 4, (128, 128), np.uint32), w["counts"]), s
+            assert np.array_equal(d_cnt.get((128, 128), np.uint32, s * 128 * 128 * 4), w["counts"]), s
 
 
 # ---- 4. the segment path at small shapes -----------------------------------------------------------------------------
@@ -383,22 +353,22 @@ def test_segments_at_small_shapes(cst, fmt_name, seg_len, hop):
         slices = np.lib.stride_tricks.sliding_window_view(cc.to_complex(raw, fmt), seg_len)[::hop]
         assert len(slices) == n_seg
         want = cc.evaluate_rows(slices, mod, 0.7, all_bins[0])   # every segment, the contract of its slice
-        with _Dev(max(raw.nbytes, 8)) as d_in:
+        with DeviceBuffer(max(raw.nbytes, 8)) as d_in:
             d_in.put(raw)
             for bins in all_bins:
                 cst.set_bins(bins)
                 nb2 = bins * bins
-                with _Dev(n_seg * nb2 * 4) as d_cnt:
+                with DeviceBuffer(n_seg * nb2 * 4) as d_cnt:
                     d_cnt.put(np.full(n_seg * nb2, 0xFFFFFFFF, np.uint32))
-                    rms, evm = cst.process_segments(None, d_in.p.value, fmt, seg_len, hop, n_seg, d_cnt.p.value)
-                    counts = d_cnt.get(0, (n_seg, bins, bins), np.uint32)
+                    rms, evm = cst.process_segments(None, d_in.ptr, fmt, seg_len, hop, n_seg, d_cnt.ptr)
+                    counts = d_cnt.get((n_seg, bins, bins), np.uint32)
                 want_counts = cc.histogram_rows(want["i"], want["q"], 0.7, bins)
                 for s in range(n_seg):
                     tag = (fmt_name, seg_len, hop, n_seg, bins, s)
                     assert _bits(rms[s], want["rms"][s], np.float32), (tag, rms[s], want["rms"][s])
                     assert _bits(evm[s], want["evm"][s], np.float64), (tag, evm[s], want["evm"][s])
                     assert np.array_equal(counts[s], want_counts[s]), tag
-            rms2, evm2 = cst.process_segments(None, d_in.p.value, fmt, seg_len, hop, n_seg, None)
+            rms2, evm2 = cst.process_segments(None, d_in.ptr, fmt, seg_len, hop, n_seg, None)
         assert _bits(rms, rms2, np.float32) and _bits(evm, evm2, np.float64), n_seg
         # the host call on the same handle: segment 0 again, from the host, against the contract of one block
         sl = raw[:per * seg_len]
@@ -498,12 +468,12 @@ def test_second_segment_past_4_gib(cst, fmt_name, hop):
     cst.set_modulation(mod)
     rng = np.random.default_rng(hop % 1000)
     segs = [_raw(fmt, seg_len, rng) for _ in range(2)]
-    with _Dev((hop + seg_len) * unit, skip_if_full=True) as d_in, _Dev(2 * 128 * 128 * 4) as d_cnt:
-        d_in.put(segs[0], 0)
+    with room_or_skip((hop + seg_len) * unit) as d_in, DeviceBuffer(2 * 128 * 128 * 4) as d_cnt:
+        d_in.put(segs[0])
         d_in.put(segs[1], hop * unit)
         d_cnt.put(np.full(2 * 128 * 128, 0xFFFFFFFF, np.uint32))
-        rms, evm = cst.process_segments(None, d_in.p.value, fmt, seg_len, hop, 2, d_cnt.p.value)
-        counts = d_cnt.get(0, (2, 128, 128), np.uint32)
+        rms, evm = cst.process_segments(None, d_in.ptr, fmt, seg_len, hop, 2, d_cnt.ptr)
+        counts = d_cnt.get((2, 128, 128), np.uint32)
     assert not np.array_equal(segs[0], segs[1])
     for s in range(2):
         res = cst.process(segs[s], fmt=fmt)
@@ -520,11 +490,11 @@ def test_misaligned_device_pointer_is_refused_on_the_host(cst):
     iq = _block(3000)
     want = cc.evaluate(iq, "qpsk", 1.5)
     rms, evm = np.zeros(1, np.float32), np.zeros(1, np.float64)
-    with _Dev(iq.nbytes + 64) as d_in:
+    with DeviceBuffer(iq.nbytes + 64) as d_in:
         d_in.put(iq)
         for fmt, offs in ((nat.IN_I8, (1, 3)), (nat.IN_U8, (1, 5)), (nat.IN_C64, (1, 2, 4, 7))):
             for off in offs:
-                rc = nat.lib.tdsa_constellation_process_dev(cst._h, None, fmt, C.c_void_p(d_in.p.value + off), 100, 100,
+                rc = nat.lib.tdsa_constellation_process_dev(cst._h, None, fmt, d_in.at(off), 100, 100,
                                                             1, rms.ctypes.data_as(C.c_void_p),
                                                             evm.ctypes.data_as(C.c_void_p), None)
                 assert rc == -1, (fmt, off, rc)
@@ -532,7 +502,7 @@ def test_misaligned_device_pointer_is_refused_on_the_host(cst):
                 assert rms[0] == 0 and evm[0] == 0
         _check(cst.process(iq), want, "after the refusals")
         # aligned to one sample, not to more: sample 1 of the buffer as the first
-        r1, e1 = cst.process_segments(None, d_in.p.value + 8, nat.IN_C64, 2999, 2999, 1, None)
+        r1, e1 = cst.process_segments(None, d_in.at(8), nat.IN_C64, 2999, 2999, 1, None)
         w1 = cc.evaluate(iq[1:], "qpsk", 1.5)
         assert _bits(r1[0], w1["rms"], np.float32) and _bits(e1[0], w1["evm"], np.float64)
 

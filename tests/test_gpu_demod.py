@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 import demod_contract as dc
-from topdogspectrumanalyser_amd import SpectrumEngine, _native as nat
+from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine, _native as nat
 from topdogspectrumanalyser_amd.channelizer import Channelizer
 from topdogspectrumanalyser_amd.demod import Demodulator, derive, design_audio_filter
 from topdogspectrumanalyser_amd.zoom import design_decimator
@@ -43,28 +43,6 @@ N_OUT = 3 * dc.TILE + 85
 def _n_in(R, n_out=N_OUT):
     """n_out outputs, ending between two outputs where R allows it."""
     return (n_out - 1) * R + 1 + R // 3
-
-
-class _Dev:
-    """A device buffer (freed on exit)."""
-
-    def __init__(self, a=None, nbytes=0):
-        self.p = C.c_void_p()
-        a = None if a is None else np.ascontiguousarray(a)
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes if a is None else a.nbytes), 16), C.byref(self.p)))
-        if a is not None:
-            nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-
-    def get(self, n, dtype):
-        out = np.empty(n, dtype=dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), self.p, out.nbytes))
-        return out
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 def _bits(y):
@@ -192,10 +170,10 @@ def test_against_the_float64_contract(R, T, name, mode):
 def _device_run(dm, x, pieces, n_out, engine=None):
     """The block piece by piece through process_device, every piece's outputs behind those before it."""
     chans, n = x.shape
-    with _Dev(x) as d_in, _Dev(nbytes=4 * chans * n_out) as d_out:
+    with DeviceBuffer.of(x) as d_in, DeviceBuffer(4 * chans * n_out) as d_out:
         got = at = 0
         for k in pieces:
-            got += dm.process_device(engine, d_in.p.value + 8 * at, k, n, d_out.p.value + 4 * got, n_out)
+            got += dm.process_device(engine, d_in.at(8 * at, 8 * ((chans - 1) * n + k)), k, n, d_out.at(4 * got), n_out)
             at += k
         dm.reset()                                               # waits for the handle's work
         assert got == n_out and at == n
@@ -279,14 +257,14 @@ def test_streams_past_2_32_inputs(name, mode, R, pole_mode, c):
     checked = (reps // 2 - 1, reps // 2, reps - 2, reps - 1)
     x = _long_block()
     cap = nb // R + 2
-    with Demodulator(name, FI, R, 1, max_host_samples=64) as dm, _Dev(x) as d_in, \
-            _Dev(nbytes=4 * cap * (1 + len(checked))) as d_a:
+    with Demodulator(name, FI, R, 1, max_host_samples=64) as dm, DeviceBuffer.of(x) as d_in, \
+            DeviceBuffer(4 * cap * (1 + len(checked))) as d_a:
         g = dm.taps
         dm.set_pole(pole_mode, c)
         total, spans = 0, []
         for i in range(reps):                               # every other call overwrites slot 0
             slot = 1 + checked.index(i) if i in checked else 0
-            k = dm.process_device(None, d_in.p.value, nb, nb, d_a.p.value + 4 * cap * slot, cap)
+            k = dm.process_device(None, d_in.ptr, nb, nb, d_a.at(4 * cap * slot), cap)
             assert k <= cap
             if slot:
                 spans.append((total, k, slot))
@@ -419,8 +397,8 @@ def test_strides_leave_the_gaps_alone_and_channels_are_independent(name):
                                              host.ctypes.data_as(C.c_void_p), out_stride, C.byref(cnt)))
         assert cnt.value == n_out
         dm.reset()
-        with _Dev(x) as d_in, _Dev(np.full((chans + 1, out_stride), sentinel, dtype=np.float32)) as d_out:
-            assert dm.process_device(None, d_in.p.value, n, in_stride, d_out.p.value, out_stride) == n_out
+        with DeviceBuffer.of(x) as d_in, DeviceBuffer.of(np.full((chans + 1, out_stride), sentinel, dtype=np.float32)) as d_out:
+            assert dm.process_device(None, d_in.ptr, n, in_stride, d_out.ptr, out_stride) == n_out
             dm.reset()
             dev = d_out.get((chans + 1) * out_stride, np.float32).reshape(chans + 1, out_stride)
     for got in (host, dev):
@@ -502,11 +480,11 @@ def _chain(streams, pieces):
             Demodulator("fm", FS * OS / M, RA, M, deemphasis=75e-6, max_host_samples=M * (n * OS // M + 1)) as dm:
         ny = bank.outputs_completed_by(n)
         na = dm.outputs_completed_by(ny)
-        with _Dev(x) as d_x, _Dev(nbytes=8 * M * ny) as d_y, _Dev(nbytes=4 * M * na) as d_a:
+        with DeviceBuffer.of(x) as d_x, DeviceBuffer(8 * M * ny) as d_y, DeviceBuffer(4 * M * na) as d_a:
             at = gy = ga = 0
             for eng, k in zip(streams, pieces):
-                ky = bank.process_device(eng, nat.IN_C64, d_x.p.value + 8 * at, k, d_y.p.value + 8 * gy, ny)
-                ga += dm.process_device(eng, d_y.p.value + 8 * gy, ky, ny, d_a.p.value + 4 * ga, na)   # no host wait between
+                ky = bank.process_device(eng, nat.IN_C64, d_x.at(8 * at, 8 * k), k, d_y.at(8 * gy), ny)
+                ga += dm.process_device(eng, d_y.at(8 * gy), ky, ny, d_a.at(4 * ga), na)   # no host wait between
                 at += k
                 gy += ky
             assert (at, gy, ga) == (n, ny, na)
@@ -567,10 +545,10 @@ def test_hopping_streams_give_the_bits_of_one_stream():
     def run(streams):
         with Demodulator("fm", FS * OS / M, RA, M, deemphasis=75e-6, max_host_samples=M) as dm:
             na = dm.outputs_completed_by(n)
-            with _Dev(y) as d_y, _Dev(nbytes=4 * M * na) as d_a:
+            with DeviceBuffer.of(y) as d_y, DeviceBuffer(4 * M * na) as d_a:
                 at = ga = 0
                 for eng, k in zip(streams, pieces):
-                    ga += dm.process_device(eng, d_y.p.value + 8 * at, k, n, d_a.p.value + 4 * ga, na)
+                    ga += dm.process_device(eng, d_y.at(8 * at, 8 * ((M - 1) * n + k)), k, n, d_a.at(4 * ga), na)
                     at += k
                 meas = dm.measure()                              # on the handle's stream, behind the last launch
                 return d_a.get(M * na, np.float32).reshape(M, na), meas

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import detect_contract as dc
-from topdogspectrumanalyser_amd import SpectrumEngine
+from device_room import room_or_skip
+from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine
 from topdogspectrumanalyser_amd import _native as nat
 from topdogspectrumanalyser_amd import detect as dt
 
@@ -20,30 +21,6 @@ INT_FIELDS = ("start", "stop", "peak_bin", "x_lo", "x_hi")
 f32 = np.float32
 
 
-class _Dev:
-    def __init__(self, nbytes, skip_if_full=False):
-        self.p = C.c_void_p()
-        rc = nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(self.p))
-        if rc != 0 and skip_if_full and b"out of memory" in nat.lib.tdsa_last_error_string().lower():
-            pytest.skip(f"no room for {nbytes} bytes on the device")
-        nat.check(rc)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.check(nat.lib.tdsa_dev_free(0, self.p))
-
-    def put(self, arr, off=0):
-        arr = np.ascontiguousarray(arr)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, C.c_void_p(self.p.value + int(off)), arr.ctypes.data_as(C.c_void_p), arr.nbytes))
-
-    def get(self, off, shape, dtype):
-        out = np.empty(shape, dtype=dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.p.value + int(off)), out.nbytes))
-        return out
-
-
 def _params(d):
     return dict(lo=d.bins[0], hi=d.bins[1], rank=d.rank, margin_db=d.margin_db, min_width=d.min_width, max_gap=d.max_gap,
                 xdb=d.xdb, S=d.max_signals)
@@ -52,10 +29,10 @@ def _params(d):
 def _on_device(d, rows, offset_floats=0, engine=None):
     """The rows through the device entry point, `offset_floats` floats into a 16-byte aligned buffer."""
     rows = np.ascontiguousarray(rows, dtype=f32)
-    with _Dev(rows.nbytes + 4 * offset_floats + 16) as buf:
-        assert buf.p.value % 16 == 0
+    with DeviceBuffer(rows.nbytes + 4 * offset_floats + 16) as buf:
+        assert buf.ptr % 16 == 0
         buf.put(rows, 4 * offset_floats)
-        return d.process_device(engine, buf.p.value + 4 * offset_floats, rows.shape[0])
+        return d.process_device(engine, buf.at(4 * offset_floats, rows.nbytes), rows.shape[0])
 
 
 def _same(got, want_rr, want_sig, tag=""):
@@ -363,15 +340,15 @@ def test_power_and_moment_against_rows_stats():
     runs = [(0, 0), (60, 70), (126, 129), (200, 460), (1000, 2100), (4090, 4096)]
     for a, b in runs:
         row[a:b + 1] = (-60.0 + 3.0 * rng.standard_normal(b - a + 1)).astype(f32)
-    with dt.SignalDetector(n, margin_db=20.0, max_gap=0) as d, SpectrumEngine(64) as eng, _Dev(4 * n) as buf:
+    with dt.SignalDetector(n, margin_db=20.0, max_gap=0) as d, SpectrumEngine(64) as eng, DeviceBuffer(4 * n) as buf:
         buf.put(row)
-        got = d.process_device(eng, buf.p.value, 1)
+        got = d.process_device(eng, buf.ptr, 1)
         s = got.signals[0]
         assert [(int(x["start"]), int(x["stop"])) for x in s[:got.count(0)]] == runs
 
         def band(a, b):
             out = C.c_double()
-            nat.check(nat.lib.tdsa_rows_stats(eng._h, buf.p, 1, n, a, b, -1.0, None, None, C.byref(out)))
+            nat.check(nat.lib.tdsa_rows_stats(eng._h, buf.ptr, 1, n, a, b, -1.0, None, None, C.byref(out)))
             return out.value
         for k, (a, b) in enumerate(runs):
             w = b - a + 1
@@ -408,16 +385,16 @@ def test_behind_the_engine_on_its_stream():
         x += a * np.exp(2j * np.pi * f * t)
     x = x.astype(np.complex64)
     with SpectrumEngine(nfft, max_frames=frames) as eng, dt.SignalDetector(nfft, margin_db=15.0, max_gap=2) as d, \
-            _Dev(x.nbytes) as d_x, _Dev(4 * nfft * frames) as d_rows:
+            DeviceBuffer(x.nbytes) as d_x, DeviceBuffer(4 * nfft * frames) as d_rows:
         eng.set_window(np.hanning(nfft).astype(f32))
         d_x.put(x)
-        eng.process_device(nat.IN_C64, d_x.p.value, x.size, nfft, frames, d_rows.p.value)
-        got = d.process_device(eng, d_rows.p.value, frames)
-        rows = d_rows.get(0, (frames, nfft), f32)
+        eng.process_device(nat.IN_C64, d_x.ptr, x.size, nfft, frames, d_rows.ptr)
+        got = d.process_device(eng, d_rows.ptr, frames)
+        rows = d_rows.get((frames, nfft), f32)
         rr, sig, occ, _, _ = dc.detect(rows, **_params(d))
         _same(got, rr, sig)
         assert np.all(got.n_found >= 2) and np.array_equal(d.occupancy()[0], occ)
-        again = d.process_device(None, d_rows.p.value, frames)
+        again = d.process_device(None, d_rows.ptr, frames)
         assert _bits(again.rows, got.rows) and _bits(again.signals, got.signals)
 
 
@@ -430,10 +407,10 @@ def test_occupancy_accumulates_resets_and_does_not_depend_on_the_split():
         assert flagged >= 1
         counts, seen, fl = one.occupancy()
         assert np.array_equal(counts, occ) and (seen, fl) == (257, flagged) and counts.dtype == np.uint32
-        with _Dev(rows.nbytes) as buf:
+        with DeviceBuffer(rows.nbytes) as buf:
             buf.put(rows)
             for r in range(257):
-                many.process_device(None, buf.p.value + 4 * n * r, 1)
+                many.process_device(None, buf.at(4 * n * r, 4 * n), 1)
         c2, s2, f2 = many.occupancy()
         assert _bits(c2, counts) and (s2, f2) == (257, flagged)
         one.process(rows[:100])
@@ -457,17 +434,17 @@ def test_rows_past_4_gib():
         planted[k, a:b + 1] = -50.0 - k
     block = np.full((1024, n), -100.0, dtype=f32)
     with dt.SignalDetector(n, max_signals=S, margin_db=10.0) as d, SpectrumEngine(64) as eng, \
-            _Dev(n_rows * n * 4, skip_if_full=True) as buf:
+            room_or_skip(n_rows * n * 4) as buf:
         row_bytes = 4 * n
         buf.put(block)
         size = block.nbytes                                           # double the constant block on the device
         while size < n_rows * row_bytes:
             step = min(size, n_rows * row_bytes - size)
-            nat.check(nat.lib.tdsa_plan_copy(eng._h, C.c_void_p(buf.p.value + size), buf.p, step, 1))
+            nat.check(nat.lib.tdsa_plan_copy(eng._h, buf.at(size, step), buf.ptr, step, 1))
             size += step
-        buf.put(planted[:2], 0)
+        buf.put(planted[:2])
         buf.put(planted[2:], (n_rows - 2) * row_bytes)
-        got = d.process_device(eng, buf.p.value, n_rows)
+        got = d.process_device(eng, buf.ptr, n_rows)
         rr, sig, occ, _, _ = dc.detect(planted, **_params(d))
         at = [0, 1, n_rows - 2, n_rows - 1]
         sub = dt.detections_from(got.rows[at], got.signals[at])
@@ -503,18 +480,18 @@ def test_library_refuses_bad_calls_on_a_live_handle():
         assert lib.tdsa_detect_timer_end(h, None) == -1
         rr[:] = 7
         assert lib.tdsa_detect_process(h, p(rows), 0, p(rr), p(sig)) == 0 and np.all(rr["n_found"] == 7)
-        with _Dev(1024) as buf:
-            assert lib.tdsa_detect_process_dev(h, None, C.c_void_p(buf.p.value + 2), 1, p(rr), p(sig)) == -1
+        with DeviceBuffer(1024) as buf:
+            assert lib.tdsa_detect_process_dev(h, None, buf.at(2), 1, p(rr), p(sig)) == -1
             assert b"aligned" in lib.tdsa_last_error_string()
-            assert lib.tdsa_detect_process_dev(h, None, buf.p, 0, p(rr), p(sig)) == 0 and np.all(rr["n_found"] == 7)
+            assert lib.tdsa_detect_process_dev(h, None, buf.ptr, 0, p(rr), p(sig)) == 0 and np.all(rr["n_found"] == 7)
         seen = C.c_uint64(9)
         nat.check(lib.tdsa_detect_read_occupancy(h, None, C.byref(seen), None))
         assert seen.value == 0
         cnt = C.c_int()
         nat.check(lib.tdsa_device_count(C.byref(cnt)))
         if cnt.value > 1:                                             # a plan on another device is refused
-            with SpectrumEngine(64, device=1) as other, _Dev(1024) as buf:
-                assert lib.tdsa_detect_process_dev(h, other._h, buf.p, 1, p(rr), p(sig)) == -1
+            with SpectrumEngine(64, device=1) as other, DeviceBuffer(1024) as buf:
+                assert lib.tdsa_detect_process_dev(h, other._h, buf.ptr, 1, p(rr), p(sig)) == -1
                 assert b"different devices" in lib.tdsa_last_error_string()
     finally:
         lib.tdsa_detect_destroy(h)

@@ -4,40 +4,17 @@ input in six pieces, hopping engine A's stream -> its own -> engine B's stream -
 second handle returns that was fed the same pieces on its own stream throughout.  Every piece depends on the state the
 piece before it left (filter history, ring position, hold row, a step written twice), so a launch that overtakes its
 predecessor shows.  Every comparison is np.array_equal on arrays of the same dtype and shape; there is no tolerance."""
-import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
-from topdogspectrumanalyser_amd import (Channelizer, Demodulator, DownConverter, SpectrumEngine, SweepAssembler,
-                                        TraceHistory, ZeroSpan, _native as nat)
+from topdogspectrumanalyser_amd import (Channelizer, Demodulator, DeviceBuffer, DownConverter, SpectrumEngine,
+                                        SweepAssembler, TraceHistory, ZeroSpan, _native as nat)
 
 pytestmark = pytest.mark.gpu
 
 PIECES = 6
-
-
-class _Dev:
-    """A device buffer holding `a` (freed on exit)."""
-
-    def __init__(self, a=None, nbytes=0):
-        self.p = C.c_void_p()
-        a = None if a is None else np.ascontiguousarray(a)
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes if a is None else a.nbytes), 16), C.byref(self.p)))
-        if a is not None:
-            nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-
-    def get(self, n, dtype):
-        a = np.empty(n, dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, a.ctypes.data_as(C.c_void_p), self.p, a.nbytes))
-        return a
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 def _same(a, b):
@@ -70,11 +47,11 @@ def _ddc_run(streams):
     rng = np.random.default_rng(11)
     x = (rng.normal(size=10 * PIECES) + 1j * rng.normal(size=10 * PIECES)).astype(np.complex64)
     taps = np.array([0.05, 0.12, 0.2, 0.26, 0.2, 0.12, 0.05], dtype=np.float32)
-    with DownConverter(3, 48000.0, 5000.0, taps=taps, max_host_samples=64) as ddc, _Dev(x) as d_in, \
-            _Dev(nbytes=8 * (x.size // 3 + 1)) as d_out:
+    with DownConverter(3, 48000.0, 5000.0, taps=taps, max_host_samples=64) as ddc, DeviceBuffer.of(x) as d_in, \
+            DeviceBuffer(8 * (x.size // 3 + 1)) as d_out:
         got = 0
         for i, eng in enumerate(streams):
-            got += ddc.process_device(eng, nat.IN_C64, d_in.p.value + 8 * 10 * i, 10, d_out.p.value + 8 * got)
+            got += ddc.process_device(eng, nat.IN_C64, d_in.at(8 * 10 * i, 8 * 10), 10, d_out.at(8 * got))
         ddc.reset()              # waits on the handle's own stream, which it first puts behind the last launch
         return got, d_out.get(got, np.complex64).view(np.uint64)
 
@@ -92,12 +69,12 @@ def _chan_run(streams):
     x = (rng.normal(size=7 * PIECES) + 1j * rng.normal(size=7 * PIECES)).astype(np.complex64)
     taps = np.array([0.02, 0.06, 0.12, 0.19, 0.22, 0.19, 0.12, 0.06, 0.02], dtype=np.float32)
     total = 7 * PIECES // 2                                    # 21 outputs per channel: the row stride
-    with Channelizer(4, 48000.0, oversample=2, taps=taps, max_host_samples=64) as bank, _Dev(x) as d_in, \
-            _Dev(nbytes=8 * 4 * total) as d_out:
+    with Channelizer(4, 48000.0, oversample=2, taps=taps, max_host_samples=64) as bank, DeviceBuffer.of(x) as d_in, \
+            DeviceBuffer(8 * 4 * total) as d_out:
         counts = []
         for i, eng in enumerate(streams):
-            counts.append(bank.process_device(eng, nat.IN_C64, d_in.p.value + 8 * 7 * i, 7,
-                                              d_out.p.value + 8 * sum(counts), total))
+            counts.append(bank.process_device(eng, nat.IN_C64, d_in.at(8 * 7 * i, 8 * 7), 7,
+                                              d_out.at(8 * sum(counts)), total))
         bank.reset()             # waits on the handle's own stream, which it first puts behind the last launch
         return counts, d_out.get(4 * total, np.complex64).view(np.uint64)
 
@@ -115,13 +92,13 @@ def _demod_run(streams):
     x = (rng.normal(size=(2, 10 * PIECES)) + 1j * rng.normal(size=(2, 10 * PIECES))).astype(np.complex64)
     taps = np.array([0.05, 0.12, 0.2, 0.26, 0.2, 0.12, 0.05], dtype=np.float32)
     total = 10 * PIECES // 3                                   # 20 outputs per channel: the row stride
-    with Demodulator("fm", 48000.0, decimation=3, channels=2, taps=taps, max_host_samples=64) as dem, _Dev(x) as d_in, \
-            _Dev(nbytes=4 * 2 * total) as d_out:
+    with Demodulator("fm", 48000.0, decimation=3, channels=2, taps=taps, max_host_samples=64) as dem, DeviceBuffer.of(x) as d_in, \
+            DeviceBuffer(4 * 2 * total) as d_out:
         dem.set_pole(nat.DEMOD_POLE_LOWPASS, 0.5)              # its block of 64 outputs is never completed
         counts = []
         for i, eng in enumerate(streams):
-            counts.append(dem.process_device(eng, d_in.p.value + 8 * 10 * i, 10, 10 * PIECES,
-                                             d_out.p.value + 4 * sum(counts), total))
+            counts.append(dem.process_device(eng, d_in.at(8 * 10 * i, 8 * (10 * PIECES + 10)), 10, 10 * PIECES,
+                                             d_out.at(4 * sum(counts)), total))
         m = dem.measure()        # waits on the handle's own stream, which it first puts behind the last launch
         return counts, d_out.get(2 * total, np.float32).view(np.uint32), (m.count, m.max, m.min, m.sum, m.sumsq)
 
@@ -145,11 +122,11 @@ def _sweep_run(streams, timer=False):
     bin_hz = 1000.0
     centres = 100e6 + np.arange(SW_S) * (SW_K1 - SW_K0) * bin_hz
     grid = np.linspace(centres[0] - 40e3, centres[-1] + 40e3, 97)
-    with SweepAssembler(SW_N, centres, (SW_K0, SW_K1), bin_hz, grid) as asm, _Dev(rows) as d:
+    with SweepAssembler(SW_N, centres, (SW_K0, SW_K1), bin_hz, grid) as asm, DeviceBuffer.of(rows) as d:
         if timer:
             asm.timer_begin()
         for i, eng in enumerate(streams):
-            asm.update_device(eng, i % SW_S, 1, d.p.value + 4 * i * SW_F * SW_N, SW_F, "max")
+            asm.update_device(eng, i % SW_S, 1, d.at(4 * i * SW_F * SW_N, 4 * SW_F * SW_N), SW_F, "max")
         ms = asm.timer_end() if timer else None
         T, present = asm.steps()
         return dict(T=T, present=present, interp=asm.read("interp"), peak=asm.read("peak")), ms
@@ -177,10 +154,10 @@ def test_sweep_timer_around_updates_on_an_engine_stream(engines, sweep_single):
 def _zspan_run(streams):
     rng = np.random.default_rng(13)
     x = (rng.normal(size=24 * PIECES) + 1j * rng.normal(size=24 * PIECES)).astype(np.complex64)
-    with ZeroSpan(64.0, detector="mag", buffer_s=1.0, max_host_samples=64) as zs, _Dev(x) as d:
+    with ZeroSpan(64.0, detector="mag", buffer_s=1.0, max_host_samples=64) as zs, DeviceBuffer.of(x) as d:
         assert zs.capacity == 64
         for i, eng in enumerate(streams):
-            assert zs.push_device(eng, nat.IN_C64, d.p.value + 8 * 24 * i, 24) == 24
+            assert zs.push_device(eng, nat.IN_C64, d.at(8 * 24 * i, 8 * 24), 24) == 24
         out = {}
         for name, v in (("free", zs.view("free_run", n_display=64)), ("rise", zs.view("rise", level=1.0, n_display=8))):
             out[name] = dict(samples=v.samples, start=v.start, total=v.total, length=v.length, triggered=v.triggered,
@@ -199,9 +176,9 @@ def test_zero_span_hopping_streams(engines):
 def _history_run(streams):
     rng = np.random.default_rng(14)
     rows = rng.normal(-60.0, 20.0, size=(3 * PIECES, 16)).astype(np.float32)
-    with TraceHistory(4, 16) as h, _Dev(rows) as d:
+    with TraceHistory(4, 16) as h, DeviceBuffer.of(rows) as d:
         for i, eng in enumerate(streams):
-            h.push_rows(eng, d.p.value + 4 * 3 * 16 * i, 3)
+            h.push_rows(eng, d.at(4 * 3 * 16 * i, 4 * 3 * 16), 3)
         return h.lines()
 
 

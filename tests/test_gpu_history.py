@@ -3,7 +3,6 @@
 batches against single pushes, the ring's wrap, bin counts from 2 to 2^17, the screen reduction, the argmax tie rule on
 a plateau, an amplitude change between pushes, device against host destinations, and the three view classes behind a
 DataProcessor tick.  Every comparison is np.array_equal on arrays of the same dtype and shape."""
-import ctypes as C
 import os
 import types
 
@@ -11,7 +10,7 @@ import numpy as np
 import pytest
 
 import history_contract as hc
-from topdogspectrumanalyser_amd import DataProcessor, RibbonView, SurfaceView, ThreeDView, TraceHistory, _native as nat
+from topdogspectrumanalyser_amd import DataProcessor, DeviceBuffer, RibbonView, SurfaceView, ThreeDView, TraceHistory, _native as nat
 from topdogspectrumanalyser_amd.utils.constants import DisplayMode
 
 pytestmark = pytest.mark.gpu
@@ -31,30 +30,6 @@ def _same(a, b):
 
 def _peak_same(a, b):
     return int(a[0]) == int(b[0]) and _same(np.float32(a[1]), np.float32(b[1]))
-
-
-class _Dev:
-    """A device buffer (freed on exit)."""
-
-    def __init__(self, nbytes):
-        self.p = C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes), 16), C.byref(self.p)))
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-        return self
-
-    def get(self, shape, dtype):
-        a = np.empty(shape, dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, a.ctypes.data_as(C.c_void_p), self.p, a.nbytes))
-        return a
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 def _rows(rng, n_rows, n, plateau=True):
@@ -179,7 +154,7 @@ def test_a_batch_of_device_rows_equals_single_pushes(n, depth, n_rows):
     rng = np.random.default_rng(n * depth + n_rows)
     rows = _rows(rng, n_rows, n)
     x = np.linspace(-10, 10, n, dtype=np.float32)
-    with TraceHistory(depth, n) as a, TraceHistory(depth, n) as b, _Dev(rows.nbytes) as d:
+    with TraceHistory(depth, n) as a, TraceHistory(depth, n) as b, DeviceBuffer(rows.nbytes) as d:
         m = hc.HistoryModel(depth, n, "heights")
         for h in (a, b, m):
             h.set_amplitude(-10.0, 90.0)
@@ -187,17 +162,17 @@ def test_a_batch_of_device_rows_equals_single_pushes(n, depth, n_rows):
         b.push(rows[0])
         m.push(rows[0])
         d.put(rows[1:])
-        a.push_rows(None, d.p.value, n_rows - 1)
+        a.push_rows(None, d.ptr, n_rows - 1)
         for r in rows[1:]:
             b.push(r)
             m.push(r)
         va, vb = _check_lines(a, m, what="batch"), _check_lines(b, m, what="single")
         assert va["pushed"] == vb["pushed"] == n_rows
         _check_ribbon(a, m, x, what="batch")
-    with TraceHistory(depth, n, "levels") as a, _Dev(rows.nbytes) as d:
+    with TraceHistory(depth, n, "levels") as a, DeviceBuffer(rows.nbytes) as d:
         m = hc.HistoryModel(depth, n, "levels")
         d.put(rows)
-        a.push_rows(None, d.p.value, n_rows)
+        a.push_rows(None, d.ptr, n_rows)
         m.push_rows(rows)
         _check_surface(a, m, what="batch")
 
@@ -208,14 +183,14 @@ def test_rows_of_an_engine_go_into_the_history_on_its_stream():
 
     nfft, nf = 1024, 12
     iq = so.synth_iq_int8(nfft * nf, nfft, seed=5)
-    with SpectrumEngine(nfft, max_frames=nf, device=0) as e, TraceHistory(8, nfft) as h, _Dev(4 * nfft * nf) as d, \
-            _Dev(iq.nbytes) as src:
+    with SpectrumEngine(nfft, max_frames=nf, device=0) as e, TraceHistory(8, nfft) as h, DeviceBuffer(4 * nfft * nf) as d, \
+            DeviceBuffer(iq.nbytes) as src:
         e.set_window(so.hackrf_window(nfft))
         e.configure(db_mode="mag", log_floor=so.LOG_FLOOR, dc_alpha=1.0)
         src.put(iq)
-        e.process_device(nat.IN_I8, src.p.value, nfft * nf, nfft, nf, d.p.value)
+        e.process_device(nat.IN_I8, src.ptr, nfft * nf, nfft, nf, d.ptr)
         h.set_amplitude(0.0, 120.0)
-        h.push_rows(e, d.p.value, nf)
+        h.push_rows(e, d.ptr, nf)
         v = h.lines()
         e.synchronize()
         rows = d.get((nf, nfft), np.float32)
@@ -348,30 +323,30 @@ def test_device_destinations_equal_host_destinations(n, columns):
             h.push(r, None, rows[0])
             s.push(r)
         v = h.ribbon(x, columns)
-        with _Dev(v["verts"].nbytes) as dv, _Dev(v["colours"].nbytes) as dc, _Dev(4 * 30 * P) as db:
-            h.ribbon(x, columns, device_out=dict(primary=dv.p.value, colours=dc.p.value, bins=db.p.value))
+        with DeviceBuffer(v["verts"].nbytes) as dv, DeviceBuffer(v["colours"].nbytes) as dc, DeviceBuffer(4 * 30 * P) as db:
+            h.ribbon(x, columns, device_out=dict(primary=dv.ptr, colours=dc.ptr, bins=db.ptr))
             assert _same(dv.get(v["verts"].shape, np.float32), v["verts"])
             assert _same(dc.get(v["colours"].shape, np.float32), v["colours"])
             if columns:
                 assert _same(db.get(v["bins"].shape, np.int32), v["bins"])
         for mode, dt in (("index", np.uint8), ("rgba", np.float32)):
             v = h.lines(2, 20, mode, columns)
-            with _Dev(v["z"].nbytes) as dz, _Dev(v[mode].nbytes) as dc, _Dev(4 * P) as dh, _Dev(4 * P) as dm, \
-                    _Dev(4 * P) as dhb:
-                w = h.lines(2, 20, mode, columns, device_out=dict(primary=dz.p.value, colours=dc.p.value, hold=dh.p.value,
-                                                                   min_row=dm.p.value, hold_bins=dhb.p.value))
+            with DeviceBuffer(v["z"].nbytes) as dz, DeviceBuffer(v[mode].nbytes) as dc, DeviceBuffer(4 * P) as dh, DeviceBuffer(4 * P) as dm, \
+                    DeviceBuffer(4 * P) as dhb:
+                w = h.lines(2, 20, mode, columns, device_out=dict(primary=dz.ptr, colours=dc.ptr, hold=dh.ptr,
+                                                                   min_row=dm.ptr, hold_bins=dhb.ptr))
                 assert _same(dz.get(v["z"].shape, np.float32), v["z"]) and _same(dc.get(v[mode].shape, dt), v[mode])
                 assert _same(dh.get(P, np.float32), v["hold"]) and _same(dm.get(P, np.float32), v["min"])
                 if columns:
                     assert _same(dhb.get(P, np.int32), v["hold_bins"])
                 assert w["live_peak"] == v["live_peak"] and w["hold_peak"] == v["hold_peak"]
         v = s.surface(columns)
-        with _Dev(v["z"].nbytes) as dz, _Dev(v["colours"].nbytes) as dc:
-            w = s.surface(columns, device_out=dict(primary=dz.p.value, colours=dc.p.value))
+        with DeviceBuffer(v["z"].nbytes) as dz, DeviceBuffer(v["colours"].nbytes) as dc:
+            w = s.surface(columns, device_out=dict(primary=dz.ptr, colours=dc.ptr))
             assert _same(dz.get(v["z"].shape, np.float32), v["z"]) and _same(dc.get(v["colours"].shape, np.float32), v["colours"])
             assert w["peak_norm"] == v["peak_norm"]
-        with pytest.raises(nat.TdsaError, match="16 bytes"):
-            s.surface(columns, device_out=dict(primary=dz.p.value + 4))
+            with pytest.raises(nat.TdsaError, match="16 bytes"):
+                s.surface(columns, device_out=dict(primary=dz.at(4)))
 
 
 def test_views_refuse_the_wrong_kind_and_bad_ranges():

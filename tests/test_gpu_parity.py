@@ -10,6 +10,7 @@ Tolerances (BASELINE.json north_star: 1e-4 relative float32):
     100 dB with no allowance - is NOT met by this path (nor by numpy's own float32 FFT): bench.py reports it
     separately as parity.survey_8d_strict_pass.
 """
+import contextlib
 import os
 import time
 
@@ -1412,14 +1413,10 @@ def test_c5_fused_launches_of_two_plans_share_the_gpu(pkg):
     """Two plans on their own streams, both with the fused row + gather launch, captures queued alternately without a
     synchronize in between: a device-wide barrier would deadlock here (each launch's waiting workgroups holding the CUs
     the other's unstarted ones need); with the ticket queue a waiting workgroup only waits for workgroups that are running."""
-    import ctypes as C
     nat = pkg._native
     n, k = 1 << 20, 16
     iq = so.synth_iq_int8(n * k, 1 << 16, seed=77)
-    d_in = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(d_in)))
-    try:
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
+    with pkg.DeviceBuffer.of(iq) as d_in:
         plans = []
         for knob in (1, 1, 0):
             e = pkg.SpectrumEngine(n, max_frames=k)
@@ -1430,7 +1427,7 @@ def test_c5_fused_launches_of_two_plans_share_the_gpu(pkg):
         for rep in range(40):
             for e in plans:
                 e.reset(nat.RESET_AVG)
-                e.process_device(nat.IN_I8, d_in.value, n * k, n, k, None)
+                e.process_device(nat.IN_I8, d_in.ptr, n * k, n, k, None)
         means = []
         for e in plans:
             e.synchronize()
@@ -1438,8 +1435,6 @@ def test_c5_fused_launches_of_two_plans_share_the_gpu(pkg):
             means.append(e.averaged()[0].copy())
             e.close()
         assert np.array_equal(means[0], means[2]) and np.array_equal(means[1], means[2])
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
 
 
 def test_c5_single_frame_with_dc_removal(pkg):
@@ -1862,7 +1857,6 @@ def test_averaging_for_the_state_alone(pkg, avg, nfft, nf):
     Welch at a native size (utils/signal_processing.py:35-61 with lin n >= frames): the frame kernel forms the chunk
     aggregates without writing the linear rows and the scan ends with its chain.  The state must be the one the full path
     leaves, bit for bit, and continue correctly into a following call that does want rows."""
-    import ctypes as C
     nat = pkg._native
     hop = nfft // 2
     ns = hop * (nf - 1) + nfft
@@ -1879,18 +1873,12 @@ def test_averaging_for_the_state_alone(pkg, avg, nfft, nf):
         want, want_cnt = e.averaged()
         rows2 = e.process(iq2, hop=hop)
         want2, _ = e.averaged()
-    d_in = C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-    try:
-        with configured() as e:
-            e.process_device(nat.IN_I8, d_in.value, ns, hop, nf, None)
-            got, got_cnt = e.averaged()
-            assert got_cnt == want_cnt and np.array_equal(got, want)
-            assert np.array_equal(e.process(iq2, hop=hop), rows2)
-            assert np.array_equal(e.averaged()[0], want2)
-    finally:
-        nat.check(nat.lib.tdsa_dev_free(0, d_in))
+    with pkg.DeviceBuffer.of(iq) as d_in, configured() as e:
+        e.process_device(nat.IN_I8, d_in.ptr, ns, hop, nf, None)
+        got, got_cnt = e.averaged()
+        assert got_cnt == want_cnt and np.array_equal(got, want)
+        assert np.array_equal(e.process(iq2, hop=hop), rows2)
+        assert np.array_equal(e.averaged()[0], want2)
     gold_src = so.HackrfBranchOracle(nfft, 20e6, precision="gold")
     gold_src.averager.set_mode(*avg)
     x = so.unpack_iq_int8(iq)
@@ -2134,7 +2122,6 @@ def test_real2_batch_matches_per_frame(pkg):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("streams", [2, 3, 4])
 def test_overlapped_launches_match_serial(pkg, streams):
-    import ctypes as C
     nat = pkg._native
     nfft, hop, nf, calls = 4096, 2048, 300, 7
     ns = hop * (nf - 1) + nfft
@@ -2145,70 +2132,46 @@ def test_overlapped_launches_match_serial(pkg, streams):
             serial.append(e.process(iq, hop=hop))
         smax, smin = e.hold()
 
-    d_in, d_out = [], []
-    for iq in batches:
-        a, b = C.c_void_p(), C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(a)))
-        nat.check(nat.lib.tdsa_dev_alloc(0, nf * nfft * 4, C.byref(b)))
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, a, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-        d_in.append(a)
-        d_out.append(b)
-    try:
-        with _hackrf_engine(pkg, nfft, nf, hold_max=True, hold_min=True) as e:
-            e.set_overlap(streams)
-            for rep in range(2):                      # second round exercises reset + re-dirtied state
-                for a, b in zip(d_in, d_out):
-                    e.process_device(nat.IN_I8, a.value, ns, hop, nf, b.value)
-                mx, mn = e.hold()                     # joins the auxiliary streams
-                assert np.array_equal(mx, smax) and np.array_equal(mn, smin)
-                for i, b in enumerate(d_out):
-                    got = np.empty((nf, nfft), dtype=np.float32)
-                    nat.check(nat.lib.tdsa_memcpy_d2h(0, got.ctypes.data_as(C.c_void_p), b, got.nbytes))
-                    assert np.array_equal(got, serial[i]), f"call {i} differs with {streams} streams"
-                e.reset()
-                assert e.hold() == (None, None)
-            # an order-dependent mode must fall back to the main stream and still be right
-            e.configure(db_mode="pow", power_scale=1.0, log_floor=so.POWER_LOG_FLOOR, dc_alpha=1.0, avg=("exp", 4))
-            gold, _, _ = so.hackrf_batch(batches[0], nfft, hop, 20e6, precision="gold", avg=("exp", 4))
-            out = e.process(batches[0], hop=hop)
-            _check(out, gold, "exp averaging with overlap enabled")
-    finally:
-        for a, b in zip(d_in, d_out):
-            nat.lib.tdsa_dev_free(0, a)
-            nat.lib.tdsa_dev_free(0, b)
+    with contextlib.ExitStack() as bufs, _hackrf_engine(pkg, nfft, nf, hold_max=True, hold_min=True) as e:
+        d_in = [bufs.enter_context(pkg.DeviceBuffer.of(iq)) for iq in batches]
+        d_out = [bufs.enter_context(pkg.DeviceBuffer(nf * nfft * 4)) for _ in batches]
+        e.set_overlap(streams)
+        for rep in range(2):                      # second round exercises reset + re-dirtied state
+            for a, b in zip(d_in, d_out):
+                e.process_device(nat.IN_I8, a.ptr, ns, hop, nf, b.ptr)
+            mx, mn = e.hold()                     # joins the auxiliary streams
+            assert np.array_equal(mx, smax) and np.array_equal(mn, smin)
+            for i, b in enumerate(d_out):
+                assert np.array_equal(b.get((nf, nfft), np.float32), serial[i]), f"call {i} differs with {streams} streams"
+            e.reset()
+            assert e.hold() == (None, None)
+        # an order-dependent mode must fall back to the main stream and still be right
+        e.configure(db_mode="pow", power_scale=1.0, log_floor=so.POWER_LOG_FLOOR, dc_alpha=1.0, avg=("exp", 4))
+        gold, _, _ = so.hackrf_batch(batches[0], nfft, hop, 20e6, precision="gold", avg=("exp", 4))
+        out = e.process(batches[0], hop=hop)
+        _check(out, gold, "exp averaging with overlap enabled")
 
 
 def test_averager_scan_row_alignment(pkg):
     """Chunked averager scan (> 128 frames): the 4-bins-per-thread kernels need 16-byte aligned rows; an output
     pointer that is only float aligned must fall back to the one-bin kernels with identical rows."""
-    import ctypes as C
     nat = pkg._native
     nfft, hop, nf = 1024, 512, 300
     ns = hop * (nf - 1) + nfft
     iq = so.synth_iq_int8(ns, nfft, seed=77)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_dev_alloc(0, nf * nfft * 4 + 64, C.byref(d_out)))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-    try:
+    with pkg.DeviceBuffer.of(iq) as d_in, pkg.DeviceBuffer(nf * nfft * 4 + 64) as d_out:
         rows = {}
         for off in (0, 4):
             with pkg.SpectrumEngine(nfft, max_frames=nf) as e:
                 e.set_window(so.hackrf_window(nfft))
                 e.configure(db_mode="pow", power_scale=1.0, log_floor=so.POWER_LOG_FLOOR, dc_alpha=1.0, avg=("exp", 8),
                             hold_max=True)
-                e.process_device(nat.IN_I8, d_in.value, ns, hop, nf, d_out.value + off)
+                e.process_device(nat.IN_I8, d_in.ptr, ns, hop, nf, d_out.at(off, nf * nfft * 4))
                 e.synchronize()
-                got = np.empty((nf, nfft), dtype=np.float32)
-                nat.check(nat.lib.tdsa_memcpy_d2h(0, got.ctypes.data_as(C.c_void_p), C.c_void_p(d_out.value + off),
-                                                  got.nbytes))
-                rows[off] = (got, e.hold()[0])
+                rows[off] = (d_out.get((nf, nfft), np.float32, off), e.hold()[0])
         assert np.array_equal(rows[0][0], rows[4][0]) and np.array_equal(rows[0][1], rows[4][1])
         gold, _, _ = so.hackrf_batch(iq, nfft, hop, 20e6, precision="gold", avg=("exp", 8))
         _check(rows[4][0], gold, "chunked exp scan, unaligned rows")
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)
 
 
 @pytest.mark.parametrize("streams", [2, 3, 4])
@@ -2303,7 +2266,6 @@ def test_host_pipe_rows_as_uint8_levels(pkg):
     """rows="u8": the read-back leg carries what ImageItem.setImage(rows, levels=(min_db, max_db)) makes of the dB rows
     (displays/waterfall.py:353-356) - byte for byte the numpy expression on the rows a synchronous call returns; levels
     changed between submissions apply to the slots submitted afterwards; the slot's float32 rows stay on the device."""
-    import ctypes as C
     nfft, hop, nf, chunks = 4096, 2048, 61, 7
     ns = hop * (nf - 1) + nfft
     batches = [so.synth_iq_int8(ns, nfft, seed=900 + i) for i in range(chunks)]
@@ -2332,9 +2294,7 @@ def test_host_pipe_rows_as_uint8_levels(pkg):
             while q.pending:
                 if q.pending == 1:                                       # the float32 rows of the slot are still there
                     rows_dev, dev_nf = q.collect_device()
-                    last = np.empty((dev_nf, nfft), dtype=np.float32)
-                    nat = pkg._native
-                    nat.check(nat.lib.tdsa_memcpy_d2h(0, last.ctypes.data_as(C.c_void_p), C.c_void_p(rows_dev), last.nbytes))
+                    last = pkg.devmem.read_device(rows_dev, (dev_nf, nfft), np.float32)     # blocking, on no stream
                     assert np.array_equal(last, ref[-1])
                     break
                 got.append(q.collect_u8().copy())
@@ -2708,8 +2668,6 @@ def test_host_pipe_device_rows_feed_analytics(pkg):
     """rows="device": the dB rows of every slot stay on the GPU and are handed to the analytics as a device
     pointer; results equal those computed from rows read back the ordinary way."""
     from topdogspectrumanalyser_amd import analytics as an
-    import ctypes as C
-    nat = pkg._native
     nfft, hop, nf, chunks = 4096, 2048, 60, 5
     ns = hop * (nf - 1) + nfft
     batches = [so.synth_iq_int8(ns, nfft, seed=1200 + i) for i in range(chunks)]
@@ -2724,8 +2682,7 @@ def test_host_pipe_device_rows_feed_analytics(pkg):
             nonlocal seen
             ptr, n = q.collect_device()
             assert n == nf and ptr
-            got = np.empty((nf, nfft), dtype=np.float32)
-            nat.check(nat.lib.tdsa_memcpy_d2h(0, got.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), got.nbytes))
+            got = pkg.devmem.read_device(ptr, (nf, nfft), np.float32)       # blocking, on no stream: collect's wait alone
             assert np.array_equal(got, ref[seen])
             peak, pbin, _ = an.rows_stats(e, ptr, n)
             assert np.array_equal(peak, ref[seen].max(axis=1)) and np.array_equal(pbin, ref[seen].argmax(axis=1))
@@ -2852,7 +2809,6 @@ def test_batched_captures_match_consecutive_calls(pkg, nfft, hop, nf, fmt, mode)
     consecutive calls - whether the captures leave as one persistent launch (order-free modes on LDS-resident sizes)
     or are run one after the other inside the call (averaging, tracked DC, chirp-z and long-frame plans).  The
     segment strides are larger than the captures and odd multiples of a sample, the output stride has a gap."""
-    import ctypes as C
     nat = pkg._native
     if nfft > 16384 and mode == "exp":
         pytest.skip("one frame per call there")
@@ -2880,10 +2836,6 @@ def test_batched_captures_match_consecutive_calls(pkg, nfft, hop, nf, fmt, mode)
         cfg = dict(db_mode="pow", power_scale=1.0, log_floor=so.POWER_LOG_FLOOR, dc_alpha=1.0, avg=("exp", 4), hold_max=True)
     elif mode == "tracked_dc":
         cfg.update(dc_alpha=0.25)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, blob.nbytes, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_dev_alloc(0, out_stride * n_seg * 4, C.byref(d_out)))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, blob.ctypes.data_as(C.c_void_p), blob.nbytes))
     rows_out = 1 if nfft > 16384 else nf
 
     def run(batched):
@@ -2892,28 +2844,21 @@ def test_batched_captures_match_consecutive_calls(pkg, nfft, hop, nf, fmt, mode)
             e.configure(**cfg)
             for rep in range(2):                              # the second round starts from non-trivial state
                 if batched:
-                    e.process_device_batch(in_fmt, d_in.value, seg_stride, n_seg, ns, hop, nf, d_out.value, out_stride)
+                    e.process_device_batch(in_fmt, d_in.ptr, seg_stride, n_seg, ns, hop, nf, d_out.ptr, out_stride)
                 else:
                     for sgi in range(n_seg):
-                        e.process_device(in_fmt, d_in.value + sgi * seg_stride, ns, hop, nf,
-                                         d_out.value + 4 * sgi * out_stride)
+                        e.process_device(in_fmt, d_in.at(sgi * seg_stride), ns, hop, nf, d_out.at(4 * sgi * out_stride))
             e.synchronize()
-            got = np.empty(out_stride * n_seg, dtype=np.float32)
-            nat.check(nat.lib.tdsa_memcpy_d2h(0, got.ctypes.data_as(C.c_void_p), d_out, got.nbytes))
+            got = d_out.get(out_stride * n_seg, np.float32)
             rows = [got[sgi * out_stride: sgi * out_stride + rows_out * nfft].reshape(rows_out, nfft).copy()
                     for sgi in range(n_seg)]
             return rows, e.hold(), e.dc_estimate, e.info().frames_held_max
 
-    try:
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_out, np.full(out_stride * n_seg, np.nan, np.float32).ctypes.data_as(C.c_void_p),
-                                          out_stride * n_seg * 4))
+    with pkg.DeviceBuffer.of(blob) as d_in, pkg.DeviceBuffer(out_stride * n_seg * 4) as d_out:
+        d_out.put(np.full(out_stride * n_seg, np.nan, np.float32))
         seq = run(False)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_out, np.full(out_stride * n_seg, np.nan, np.float32).ctypes.data_as(C.c_void_p),
-                                          out_stride * n_seg * 4))
+        d_out.put(np.full(out_stride * n_seg, np.nan, np.float32))
         bat = run(True)
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)
     for sgi in range(n_seg):
         assert np.array_equal(seq[0][sgi], bat[0][sgi]), f"capture {sgi} differs"
     for a, b in zip(seq[1], bat[1]):
@@ -2931,7 +2876,6 @@ def test_batched_single_frame_captures(pkg, nfft, fmt, out_gap):
     (hackrf_samples.py:254-305).  ceil(2^32 / 1) does not fit the kernel's 32-bit segment divisor, so the library runs
     such a batch as one capture whose frames sit a segment stride apart (contiguous rows) or capture by capture
     (gapped rows): rows, hold traces and DC state must be those of consecutive calls either way, with gapped input."""
-    import ctypes as C
     nat = pkg._native
     n_seg, nf, hop = 7, 1, nfft
     bps = 8 if fmt == "c64" else 2
@@ -2950,36 +2894,25 @@ def test_batched_single_frame_captures(pkg, nfft, fmt, out_gap):
     for sgi, iq in enumerate(caps):
         raw = iq.view(np.uint8)
         blob[sgi * seg_stride: sgi * seg_stride + raw.size] = raw
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, blob.nbytes, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_dev_alloc(0, out_stride * n_seg * 4, C.byref(d_out)))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, blob.ctypes.data_as(C.c_void_p), blob.nbytes))
-
     def run(batched):
-        nan = np.full(out_stride * n_seg, np.nan, np.float32)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_out, nan.ctypes.data_as(C.c_void_p), nan.nbytes))
+        d_out.put(np.full(out_stride * n_seg, np.nan, np.float32))
         with _hackrf_engine(pkg, nfft, 4, hold_max=True, hold_min=True) as e:
             for rep in range(2):
                 if batched:
-                    e.process_device_batch(in_fmt, d_in.value, seg_stride, n_seg, nfft, hop, nf, d_out.value, out_stride)
+                    e.process_device_batch(in_fmt, d_in.ptr, seg_stride, n_seg, nfft, hop, nf, d_out.ptr, out_stride)
                 else:
                     for sgi in range(n_seg):
-                        e.process_device(in_fmt, d_in.value + sgi * seg_stride, nfft, hop, nf,
-                                         d_out.value + 4 * sgi * out_stride)
+                        e.process_device(in_fmt, d_in.at(sgi * seg_stride), nfft, hop, nf, d_out.at(4 * sgi * out_stride))
             e.synchronize()
-            got = np.empty(out_stride * n_seg, dtype=np.float32)
-            nat.check(nat.lib.tdsa_memcpy_d2h(0, got.ctypes.data_as(C.c_void_p), d_out, got.nbytes))
+            got = d_out.get(out_stride * n_seg, np.float32)
             return got, e.hold(), e.dc_estimate, e.info().frames_held_max
 
-    try:
+    with pkg.DeviceBuffer.of(blob) as d_in, pkg.DeviceBuffer(out_stride * n_seg * 4) as d_out:
         seq = run(False)
         bat = run(True)
         with _hackrf_engine(pkg, nfft, 4) as e:               # rows that would overlap are refused, not raced
             with pytest.raises(Exception):
-                e.process_device_batch(in_fmt, d_in.value, seg_stride, n_seg, nfft, hop, nf, d_out.value, nfft // 2)
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)
+                e.process_device_batch(in_fmt, d_in.ptr, seg_stride, n_seg, nfft, hop, nf, d_out.ptr, nfft // 2)
     assert np.array_equal(seq[0], bat[0], equal_nan=True)      # the gaps keep their NaN fill in both
     for a, b in zip(seq[1], bat[1]):
         assert np.array_equal(a, b)
@@ -2994,36 +2927,27 @@ def test_batched_single_frame_captures(pkg, nfft, fmt, out_gap):
 def test_batched_captures_full_c3_shape(pkg):
     """Four seconds of the C3 shape (4 x 2440 frames of 16384 points, hop N/2) in one launch: the hold trace equals
     the column maximum of all 9760 rows and sampled rows match the gold oracle."""
-    import ctypes as C
     nat = pkg._native
     nfft, hop, ns, n_seg = 16384, 8192, 20_000_000, 4
     nf = (ns - nfft) // hop + 1
     base = so.synth_iq_int8(ns, nfft, seed=3)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, 2 * ns * n_seg, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_dev_alloc(0, nf * nfft * 4 * n_seg, C.byref(d_out)))
-    try:
+    with pkg.DeviceBuffer(2 * ns * n_seg) as d_in, pkg.DeviceBuffer(nf * nfft * 4 * n_seg) as d_out:
         hosts = [base if k == 0 else np.roll(base, 2 * 977 * k) for k in range(n_seg)]
         for k, hst in enumerate(hosts):
-            nat.check(nat.lib.tdsa_memcpy_h2d(0, C.c_void_p(d_in.value + 2 * ns * k), hst.ctypes.data_as(C.c_void_p), hst.nbytes))
+            d_in.put(hst, 2 * ns * k)
         with _hackrf_engine(pkg, nfft, nf, hold_max=True) as e:
-            e.process_device_batch(nat.IN_I8, d_in.value, 2 * ns, n_seg, ns, hop, nf, d_out.value, nf * nfft)
+            e.process_device_batch(nat.IN_I8, d_in.ptr, 2 * ns, n_seg, ns, hop, nf, d_out.ptr, nf * nfft)
             mx, _ = e.hold()
             assert e.info().frames_held_max == n_seg * nf
         colmax = None
         for k in range(n_seg):
-            got = np.empty((nf, nfft), dtype=np.float32)
-            nat.check(nat.lib.tdsa_memcpy_d2h(0, got.ctypes.data_as(C.c_void_p), C.c_void_p(d_out.value + 4 * nf * nfft * k),
-                                              got.nbytes))
+            got = d_out.get((nf, nfft), np.float32, 4 * nf * nfft * k)
             colmax = got.max(axis=0) if colmax is None else np.maximum(colmax, got.max(axis=0))
             gold_src = so.HackrfBranchOracle(nfft, 20e6, precision="gold")
             for f in (0, nf - 1):
                 x = so.unpack_iq_int8(hosts[k][2 * f * hop: 2 * (f * hop + nfft)])
                 _check(got[f], np.asarray(gold_src.power_levels(x)), f"second {k} frame {f}")
         assert np.array_equal(mx, colmax)
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)
 
 
 @pytest.mark.parametrize("group", [1, 3, 5])
@@ -3061,30 +2985,23 @@ def test_batched_captures_without_rows_and_with_tare(pkg):
     caps = [so.synth_iq_int8(ns, nfft, seed=900 + s) for s in range(n_seg)]
     blob = np.concatenate(caps)
     base = (np.linspace(-3.0, 3.0, nfft)).astype(np.float32)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    nat.check(nat.lib.tdsa_dev_alloc(0, blob.nbytes, C.byref(d_in)))
-    nat.check(nat.lib.tdsa_dev_alloc(0, n_seg * nf * nfft * 4, C.byref(d_out)))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, blob.ctypes.data_as(C.c_void_p), blob.nbytes))
-    try:
+    with pkg.DeviceBuffer.of(blob) as d_in, pkg.DeviceBuffer(n_seg * nf * nfft * 4) as d_out:
         holds = []
         for batched, rows in ((False, True), (True, True), (True, False)):
             with _hackrf_engine(pkg, nfft, nf, hold_max=True, hold_min=True) as e:
                 nat.check(nat.lib.tdsa_set_tare_baseline(e._h, base.ctypes.data_as(C.c_void_p), nfft))
-                out = d_out.value if rows else None
+                out = d_out.ptr if rows else None
                 if batched:
-                    e.process_device_batch(nat.IN_I8, d_in.value, 2 * ns, n_seg, ns, hop, nf, out, nf * nfft)
+                    e.process_device_batch(nat.IN_I8, d_in.ptr, 2 * ns, n_seg, ns, hop, nf, out, nf * nfft)
                 else:
                     for s in range(n_seg):
-                        e.process_device(nat.IN_I8, d_in.value + 2 * ns * s, ns, hop, nf, d_out.value + 4 * nf * nfft * s)
+                        e.process_device(nat.IN_I8, d_in.at(2 * ns * s, 2 * ns), ns, hop, nf,
+                                         d_out.at(4 * nf * nfft * s, 4 * nf * nfft))
                 holds.append(e.hold())
                 if rows:
-                    got = np.empty((n_seg * nf, nfft), dtype=np.float32)
-                    nat.check(nat.lib.tdsa_memcpy_d2h(0, got.ctypes.data_as(C.c_void_p), d_out, got.nbytes))
+                    got = d_out.get((n_seg * nf, nfft), np.float32)
                     assert np.array_equal(holds[-1][0], got.max(axis=0)) and np.array_equal(holds[-1][1], got.min(axis=0))
         for h in holds[1:]:
             assert np.array_equal(h[0], holds[0][0]) and np.array_equal(h[1], holds[0][1])
         gold, _, _ = so.hackrf_batch(caps[1], nfft, hop, 20e6, precision="gold")
         _check(got[nf: 2 * nf] + base[None, :], gold, "capture 1, tare added back")
-    finally:
-        nat.lib.tdsa_dev_free(0, d_in)
-        nat.lib.tdsa_dev_free(0, d_out)

@@ -10,12 +10,14 @@ the C-ABI's argument checks.
 No tolerance anywhere: bins and counts are integers, the dB values float32 copied from the row (compared as bit
 patterns), the prominences float64 (bit patterns); padding is -1 / NaN.  Every family asserts on the CPU that its rows
 discriminate (tests/test_peaks_host.py)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import peaks_contract as pc
+from topdogspectrumanalyser_amd import DeviceBuffer
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]        # every test under a time limit of its own
 
@@ -41,23 +43,14 @@ def eng():
         yield e
 
 
-class _Dev:
-    """Rows on the device, `offset` bytes into a buffer whose base is aligned to 256 bytes."""
-
-    def __init__(self, rows, offset=0):
-        nat = _nat()
-        rows = np.ascontiguousarray(rows, dtype=F32)
-        self.p = C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, rows.nbytes + 64, C.byref(self.p)))
-        assert self.p.value % 256 == 0
-        self.ptr = self.p.value + offset
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, C.c_void_p(self.ptr), rows.ctypes.data_as(C.c_void_p), rows.nbytes))
-
-    def __enter__(self):
-        return self.ptr
-
-    def __exit__(self, *exc):
-        _nat().lib.tdsa_dev_free(0, self.p)
+@contextlib.contextmanager
+def _on_device(rows, offset=0):
+    """The address of the rows on the device, `offset` bytes into a buffer whose base is aligned to 256 bytes."""
+    rows = np.ascontiguousarray(rows, dtype=F32)
+    with DeviceBuffer(rows.nbytes + 64) as buf:
+        assert buf.ptr % 256 == 0
+        buf.put(rows, offset)
+        yield buf.at(offset, rows.nbytes)
 
 
 def _bits(a):
@@ -81,7 +74,7 @@ def _top_wrong(case, bins, db):
 def _run_top(an, eng, cases, offset=0):
     bad = []
     for case in cases:
-        with _Dev(case["rows"], offset) as d:
+        with _on_device(case["rows"], offset) as d:
             bins, db = an.rows_top_peaks(eng, d, len(case["rows"]), n_bins=case["n"], n=case["n_peaks"],
                                          min_sep_bins=case["min_sep"], min_excursion_db=case["exc"])
         wrong = _top_wrong(case, bins, db)
@@ -111,7 +104,7 @@ def _run_mark(an, eng, cases, offset=0):
     bad = []
     for case in cases:
         kw = case["params"]
-        with _Dev(case["rows"], offset) as d:
+        with _on_device(case["rows"], offset) as d:
             got = an.rows_marker_peaks(eng, d, len(case["rows"]), n_bins=case["n"], peak_threshold=kw["height"],
                                        peak_excursion=kw["prominence"], distance=kw["distance"], current_idx=kw["current_idx"],
                                        max_list=kw["max_list"])
@@ -141,7 +134,7 @@ def test_top_excursion_is_a_float32(an, eng):
     """The constructed 6.3 case: the device agrees with the contract called with float32(6.3) - one peak - where the
     unrounded Python float would give two."""
     row = pc.excursion_63_row()
-    with _Dev(row[None, :]) as d:
+    with _on_device(row[None, :]) as d:
         bins, _ = an.rows_top_peaks(eng, d, 1, n_bins=len(row), n=5, min_sep_bins=2, min_excursion_db=6.3)
     assert bins[0].tolist() == [75, -1, -1, -1, -1] == pc.top_expected(row[None, :], 5, 2, float(F32(6.3)))[0][0].tolist()
 
@@ -181,7 +174,7 @@ def test_top_abi_arguments(eng):
         return nat.lib.tdsa_rows_top_peaks(eng._h, C.c_void_p(ptr), n_rows, n_bins, n_peaks, sep, exc,
                                            bins.ctypes.data_as(C.c_void_p) if bins_p is None else bins_p,
                                            db.ctypes.data_as(C.c_void_p) if db_p is None else db_p)
-    with _Dev(rows) as d:
+    with _on_device(rows) as d:
         assert call(d, exc=float("nan")) == ERR_ARG
         assert call(d, n_peaks=0) == ERR_ARG and call(d, n_peaks=9) == ERR_ARG
         assert call(d, n_bins=0) == ERR_ARG and call(d, n_bins=16385) == ERR_ARG
@@ -263,7 +256,7 @@ def test_marker_abi_arguments(eng):
         return nat.lib.tdsa_rows_marker_peaks(eng._h, C.c_void_p(ptr), n_rows, n_bins, -200.0, prominence, distance, -1, max_list,
                                               cnt.ctypes.data_as(C.c_void_p), snap.ctypes.data_as(C.c_void_p),
                                               nxt.ctypes.data_as(C.c_void_p), lst_p, None)
-    with _Dev(rows) as d:
+    with _on_device(rows) as d:
         assert call(d + 1) == ERR_ARG and call(d + 2) == ERR_ARG and call(d + 3) == ERR_ARG
         assert call(d, n_bins=0) == ERR_ARG and call(d, n_bins=16385) == ERR_ARG and call(d, distance=0) == ERR_ARG
         assert call(d, prominence=float("nan")) == ERR_ARG and call(d, lst_p=None) == ERR_ARG

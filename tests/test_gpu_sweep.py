@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import sweep_contract as sc
-from topdogspectrumanalyser_amd import IqSweepDataSource, SpectrumEngine, SweepAssembler, _native as nat, plan_steps
+from topdogspectrumanalyser_amd import DeviceBuffer, IqSweepDataSource, SpectrumEngine, SweepAssembler, _native as nat, plan_steps
 from topdogspectrumanalyser_amd.core.display_data_processor import DataProcessor
 from topdogspectrumanalyser_amd.sweep import frequency_grid, step_frequencies
 from topdogspectrumanalyser_amd.zoom import zoom_window
@@ -20,30 +20,6 @@ pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]        # every test und
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sweep.npz")
 AVG_BOUND_DB = 1e-3          # the project's row allowance (DESIGN.md section 4.9 derives the room it leaves; worst seen 1.8e-5)
-
-
-class _Dev:
-    """A device buffer (freed on exit)."""
-
-    def __init__(self, nbytes):
-        self.p = C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes), 8), C.byref(self.p)))
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-        return self
-
-    def get(self, n, dtype):
-        out = np.empty(n, dtype=dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), self.p, out.nbytes))
-        return out
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 def _same(a, b):
@@ -84,11 +60,11 @@ def test_update_dev_detectors(N, k0, k1, pad, F):
     centres = _centres(S, K, 1000.0)
     grid = np.linspace(centres[0], centres[-1], 50)
     worst = 0.0
-    with SweepAssembler(N, centres, (k0, k1), 1000.0, grid) as asm, _Dev(buf.nbytes) as d:
+    with SweepAssembler(N, centres, (k0, k1), 1000.0, grid) as asm, DeviceBuffer(buf.nbytes) as d:
         d.put(buf)
         for det in sc.DETECTORS:
             asm.reset()
-            asm.update_device(None, 0, S, d.p.value, F, det, stride)
+            asm.update_device(None, 0, S, d.ptr, F, det, stride)
             T, valid = asm.steps()
             assert valid.all() and T.shape == (S, K)
             for s in range(S):
@@ -113,20 +89,20 @@ def test_update_dev_marks_only_its_steps_and_refuses_bad_calls():
     buf, rows = _rows(rng, S, F, N, F * N)
     centres = _centres(S, k1 - k0, 1000.0)
     grid = np.linspace(centres[0], centres[-1], 64)
-    with SweepAssembler(N, centres, (k0, k1), 1000.0, grid) as asm, _Dev(buf.nbytes) as d:
+    with SweepAssembler(N, centres, (k0, k1), 1000.0, grid) as asm, DeviceBuffer(buf.nbytes) as d:
         d.put(buf)
         assert not asm.steps()[1].any()
-        asm.update_device(None, 1, 2, d.p.value + 4 * F * N, F, "max")
+        asm.update_device(None, 1, 2, d.at(4 * F * N), F, "max")
         T, valid = asm.steps()
         assert list(valid) == [False, True, True, False, False]
         assert _same(T[1], sc.detector(rows[1], k0, k1, "max")) and _same(T[2], sc.detector(rows[2], k0, k1, "max"))
         for first, n in ((-1, 1), (4, 2), (0, 6)):
             with pytest.raises(nat.TdsaError):
-                asm.update_device(None, first, n, d.p.value, F, "max")
+                asm.update_device(None, first, n, d.ptr, F, "max")
         with pytest.raises(nat.TdsaError):
-            asm.update_device(None, 0, 1, d.p.value, 0, "max")
+            asm.update_device(None, 0, 1, d.ptr, 0, "max")
         with pytest.raises(nat.TdsaError):
-            asm.update_device(None, 0, 1, d.p.value + 2, F, "max")
+            asm.update_device(None, 0, 1, d.at(2), F, "max")
         # the C-ABI refuses geometry the Python layer would have refused first
         bad = np.ascontiguousarray(centres[::-1])
         rc = nat.lib.tdsa_sweep_set_geometry(asm._h, bad.ctypes.data_as(C.c_void_p), 1000.0, k0, k1,
@@ -145,11 +121,11 @@ def _load_steps(asm, T, present, N, k0):
     S, K = T.shape
     rows = np.zeros((S, N), dtype=np.float32)
     rows[:, k0:k0 + K] = T
-    with _Dev(rows.nbytes) as d:
+    with DeviceBuffer(rows.nbytes) as d:
         d.put(rows)
         asm.reset()
         for s in np.nonzero(present)[0]:
-            asm.update_device(None, int(s), 1, d.p.value + 4 * int(s) * N, 1, "sample")
+            asm.update_device(None, int(s), 1, d.at(4 * int(s) * N, 4 * N), 1, "sample")
         got, valid = asm.steps()
     assert np.array_equal(valid, present)
     assert _same(got[present], T[present])
@@ -168,8 +144,8 @@ def test_read_equals_the_recorded_reference_sweep():
         assert out.dtype == np.float64 and _same(out, z["full_power_array"])
         assert _same(out, sc.assemble(T, present, centres, k0, k1, N, bin_hz, grid, "interp"))
         assert _same(asm.read("peak"), sc.assemble(T, present, centres, k0, k1, N, bin_hz, grid, "peak"))
-        with _Dev(8 * grid.size) as d:                                   # to a device buffer, no host pointer
-            assert asm.read("interp", out_dev=d.p.value, to_host=False) is None
+        with DeviceBuffer(8 * grid.size) as d:                                   # to a device buffer, no host pointer
+            assert asm.read("interp", out_dev=d.ptr, to_host=False) is None
             asm.steps()                                                  # waits for the handle's stream
             assert _same(d.get(grid.size, np.float64), out)
         asm.reset()
@@ -260,18 +236,18 @@ def test_run_dev_any_split_any_chunk_same_bits(fmt):
     else:
         iq = ((rng.standard_normal((S, n_per + 1)) + 1j * rng.standard_normal((S, n_per + 1))) * 0.2).astype(np.complex64)
         in_format, stride = nat.IN_C64, 8 * (n_per + 1)
-    with _engine(N, F) as eng, _Dev(iq.nbytes) as d_iq, _Dev(4 * S * F * N) as d_rows, \
+    with _engine(N, F) as eng, DeviceBuffer(iq.nbytes) as d_iq, DeviceBuffer(4 * S * F * N) as d_rows, \
             SweepAssembler(N, centres, (k0, k1), bin_hz, grid) as asm:
         d_iq.put(iq)
         # the parent's path plus the detector: rows of all steps, then one update
-        eng.process_device_batch(in_format, d_iq.p.value, stride, S, n_per, hop, F, d_rows.p.value)
+        eng.process_device_batch(in_format, d_iq.ptr, stride, S, n_per, hop, F, d_rows.ptr)
         eng.synchronize()
         rows = d_rows.get(S * F * N, np.float32).reshape(S, F, N)
         assert np.isfinite(rows).all()
         results = {}
         for det in sc.DETECTORS:
             asm.reset()
-            asm.update_device(eng, 0, S, d_rows.p.value, F, det)
+            asm.update_device(eng, 0, S, d_rows.ptr, F, det)
             ref_T = asm.steps()[0]
             ref_out = {m: asm.read(m) for m in ("interp", "peak")}
             for s in range(S):
@@ -286,7 +262,7 @@ def test_run_dev_any_split_any_chunk_same_bits(fmt):
             for cuts in ([(4, 3), (0, 4)], [(6, 1), (0, 1), (1, 5)], [(s, 1) for s in range(S)]):
                 asm.reset()
                 for first, n in cuts:
-                    asm.update_device(eng, first, n, d_rows.p.value + 4 * first * F * N, F, det)
+                    asm.update_device(eng, first, n, d_rows.at(4 * first * F * N, 4 * n * F * N), F, det)
                 assert _same(asm.steps()[0], ref_T), (det, cuts)
                 assert _same(asm.read("interp"), ref_out["interp"])
             # run_dev: one call, any chunk bound, any split
@@ -296,16 +272,16 @@ def test_run_dev_any_split_any_chunk_same_bits(fmt):
                 asm.reset()
                 asm.set_chunk_bytes(bound)
                 for first, n in cuts:
-                    asm.run_device(eng, in_format, d_iq.p.value + first * stride, stride, first, n, n_per, hop, F, det)
+                    asm.run_device(eng, in_format, d_iq.at(first * stride), stride, first, n, n_per, hop, F, det)
                 assert _same(asm.steps()[0], ref_T), (det, bound, cuts)
                 for m in ("interp", "peak"):
                     assert _same(asm.read(m), ref_out[m]), (det, bound, cuts, m)
             results[det] = ref_T
         assert not _same(results["max"], results["min"])
         with pytest.raises(nat.TdsaError):
-            asm.run_device(eng, 7, d_iq.p.value, stride, 0, S, n_per, hop, F, "max")
+            asm.run_device(eng, 7, d_iq.ptr, stride, 0, S, n_per, hop, F, "max")
         with _engine(2 * N, F) as other, pytest.raises(nat.TdsaError):
-            asm.run_device(other, in_format, d_iq.p.value, stride, 0, S, n_per, hop, F, "max")
+            asm.run_device(other, in_format, d_iq.ptr, stride, 0, S, n_per, hop, F, "max")
 
 
 # ---------------------------------------------------------------------------------------------------- end to end
@@ -347,8 +323,8 @@ def test_sweep_once_end_to_end(detector, frames, hop):
         # the same from the engine's own rows of those captures, through the contract
         S, n_per = src.centres.size, src.n_samples_per_step
         k0, k1 = src.kept
-        with _Dev(4 * S * frames * NFFT) as d_rows:
-            src.engine.process_device_batch(nat.IN_C64, src._d_in.value, 8 * n_per, S, n_per, src.hop, frames, d_rows.p.value)
+        with DeviceBuffer(4 * S * frames * NFFT) as d_rows:
+            src.engine.process_device_batch(nat.IN_C64, src._d_in.ptr, 8 * n_per, S, n_per, src.hop, frames, d_rows.ptr)
             src.engine.synchronize()
             rows = d_rows.get(S * frames * NFFT, np.float32).reshape(S, frames, NFFT)
         T_dev = src.assembler.steps()[0]

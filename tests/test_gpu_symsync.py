@@ -2,14 +2,14 @@
 where the contract's arithmetic is exact (integer positions, powers of two, quarter turns), within derived bounds stage
 by stage elsewhere - each stage is handed the device's own result of the stage before, so a bound never has to absorb a
 decision taken on the other side of a seam - and bit-equal across n_seg, the segment's place and the entry point."""
-import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
 import symsync_contract as sc
-from topdogspectrumanalyser_amd import _native as nat
+from device_room import room_or_skip
+from topdogspectrumanalyser_amd import DeviceBuffer, _native as nat
 from topdogspectrumanalyser_amd import symbols as sy
 
 pytestmark = pytest.mark.gpu
@@ -34,30 +34,6 @@ def layouts(seg_len):
     """(n_seg, hop) of every segment length: one segment; two with the hop above and at the segment's length; 257 that
     overlap, five samples apart."""
     return [(1, seg_len), (2, seg_len + 3), (2, seg_len), (257, 5)]
-
-
-class _Dev:
-    def __init__(self, nbytes, skip_if_full=False):
-        self.p = C.c_void_p()
-        rc = nat.lib.tdsa_dev_alloc(0, int(nbytes), C.byref(self.p))
-        if rc != 0 and skip_if_full and b"out of memory" in nat.lib.tdsa_last_error_string().lower():
-            pytest.skip(f"no room for {nbytes} bytes on the device")
-        nat.check(rc)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.check(nat.lib.tdsa_dev_free(0, self.p))
-
-    def put(self, arr, off=0):
-        arr = np.ascontiguousarray(arr)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, C.c_void_p(self.p.value + int(off)), arr.ctypes.data_as(C.c_void_p), arr.nbytes))
-
-    def get(self, off, shape, dtype):
-        out = np.empty(shape, dtype=dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.p.value + int(off)), out.nbytes))
-        return out
 
 
 @pytest.fixture(scope="module")
@@ -88,12 +64,12 @@ def _run(s, x, L, hop, n_seg, stride):
     if n_seg * L <= s.max_host_samples:
         r = s.process(x, L, hop, raw=True, out_stride=stride)
         return r.symbols, r.raw, r.records
-    with _Dev(x.nbytes) as d_x, _Dev(8 * n_seg * stride) as d_s, _Dev(8 * n_seg * stride) as d_r:
+    with DeviceBuffer(x.nbytes) as d_x, DeviceBuffer(8 * n_seg * stride) as d_s, DeviceBuffer(8 * n_seg * stride) as d_r:
         d_x.put(x)
         d_s.put(np.full(n_seg * stride, sy.SENTINEL))
         d_r.put(np.full(n_seg * stride, sy.SENTINEL))
-        r = s.process_device(None, d_x.p.value, L, hop, n_seg, d_s.p.value, stride, d_r.p.value)
-        return d_s.get(0, (n_seg, stride), np.complex64), d_r.get(0, (n_seg, stride), np.complex64), r.records
+        r = s.process_device(None, d_x.ptr, L, hop, n_seg, d_s.ptr, stride, d_r.ptr)
+        return d_s.get((n_seg, stride), np.complex64), d_r.get((n_seg, stride), np.complex64), r.records
 
 
 def _bits(a, b):
@@ -321,13 +297,13 @@ def test_a_segment_does_not_depend_on_n_seg_its_place_or_the_entry_point(syncs):
         assert _bits(one.symbols[0], many.symbols[g]) and _bits(one.raw[0], many.raw[g]), g
         assert one.records[0].tobytes() == many.records[g].tobytes(), g
     stride = K + 5
-    with _Dev(x.nbytes) as d_x, _Dev(8 * n_seg * stride) as d_s, _Dev(8 * n_seg * stride) as d_r:
+    with DeviceBuffer(x.nbytes) as d_x, DeviceBuffer(8 * n_seg * stride) as d_s, DeviceBuffer(8 * n_seg * stride) as d_r:
         d_x.put(x)
         d_s.put(np.full(n_seg * stride, sy.SENTINEL))
         d_r.put(np.full(n_seg * stride, sy.SENTINEL))
-        dev = s.process_device(None, d_x.p.value, L, hop, n_seg, d_s.p.value, stride, d_r.p.value)
-        sym = d_s.get(0, (n_seg, stride), np.complex64)
-        raw = d_r.get(0, (n_seg, stride), np.complex64)
+        dev = s.process_device(None, d_x.ptr, L, hop, n_seg, d_s.ptr, stride, d_r.ptr)
+        sym = d_s.get((n_seg, stride), np.complex64)
+        raw = d_r.get((n_seg, stride), np.complex64)
     assert dev.records.tobytes() == many.records.tobytes()
     assert _bits(sym[:, :K], many.symbols) and _bits(raw[:, :K], many.raw)
     assert np.all(sym[:, K:] == sy.SENTINEL) and np.all(raw[:, K:] == sy.SENTINEL)
@@ -347,11 +323,11 @@ def test_behind_the_down_converter_on_an_engine_stream(syncs):
     with SpectrumEngine(64) as eng, DownConverter(D, 1.0, taps=taps) as ddc, DownConverter(D, 1.0, taps=taps) as ddc_h:
         y = ddc_h.process(x)
         n_seg = (y.size - L) // L + 1
-        with _Dev(x.nbytes) as d_x, _Dev(8 * (y.size + 8)) as d_y, _Dev(8 * n_seg * K) as d_s:
+        with DeviceBuffer(x.nbytes) as d_x, DeviceBuffer(8 * (y.size + 8)) as d_y, DeviceBuffer(8 * n_seg * K) as d_s:
             d_x.put(x)
-            ny = ddc.process_device(eng, nat.IN_C64, d_x.p.value, x.size, d_y.p.value)
-            dev = s.process_device(eng, d_y.p.value, L, L, n_seg, d_s.p.value, K)
-            sym = d_s.get(0, (n_seg, K), np.complex64)
+            ny = ddc.process_device(eng, nat.IN_C64, d_x.ptr, x.size, d_y.ptr)
+            dev = s.process_device(eng, d_y.ptr, L, L, n_seg, d_s.ptr, K)
+            sym = d_s.get((n_seg, K), np.complex64)
     assert ny == y.size and n_seg == 3
     host = s.process(y, L)
     assert dev.records.tobytes() == host.records.tobytes() and _bits(sym, host.symbols)
@@ -396,11 +372,11 @@ def test_second_segment_past_4_gib(syncs):
     K = s.symbols_per_segment(L)
     segs = [sc.make_signal("qpsk", sps, L, seed=20 + g, alpha=0.9)[0].astype(np.complex64) for g in range(2)]
     stride = (1 << 29) + 3                                            # the outputs past 2^32 bytes as well
-    with _Dev((hop + L) * 8, skip_if_full=True) as d_x, _Dev((stride + K) * 8, skip_if_full=True) as d_s:
-        d_x.put(segs[0], 0)
+    with room_or_skip((hop + L) * 8) as d_x, room_or_skip((stride + K) * 8) as d_s:
+        d_x.put(segs[0])
         d_x.put(segs[1], hop * 8)
-        dev = s.process_device(None, d_x.p.value, L, hop, 2, d_s.p.value, stride)
-        sym = [d_s.get(g * stride * 8, (K,), np.complex64) for g in range(2)]
+        dev = s.process_device(None, d_x.ptr, L, hop, 2, d_s.ptr, stride)
+        sym = [d_s.get((K,), np.complex64, g * stride * 8) for g in range(2)]
     for g in range(2):
         one = s.process(segs[g], L)
         assert dev.records[g].tobytes() == one.records[0].tobytes() and _bits(sym[g], one.symbols[0]), g
@@ -422,10 +398,10 @@ def test_device_evm_matches_the_contracts_evm(syncs, mod, sps):
     x = x.astype(np.complex64)
     s = syncs(sps, modulation=mod)
     K = s.symbols_per_segment(L)
-    with Constellation(modulation=mod) as cst, _Dev(x.nbytes) as d_x, _Dev(8 * n_seg * K) as d_s:
+    with Constellation(modulation=mod) as cst, DeviceBuffer(x.nbytes) as d_x, DeviceBuffer(8 * n_seg * K) as d_s:
         d_x.put(x)
-        r = s.process_device(None, d_x.p.value, L, L, n_seg, d_s.p.value, K)
-        _, evm_dev = cst.process_segments(None, d_s.p.value, nat.IN_C64, K, K, n_seg)
+        r = s.process_device(None, d_x.ptr, L, L, n_seg, d_s.ptr, K)
+        _, evm_dev = cst.process_segments(None, d_s.ptr, nat.IN_C64, K, K, n_seg)
         for g in range(n_seg):
             want = sc.recover(_c128(x[g * L:(g + 1) * L]), sps, M, s.ref_arg)
             evm_ref = cst.process(want["symbols"].astype(np.complex64), counts=False).evm_rms

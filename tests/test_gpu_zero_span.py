@@ -2,7 +2,6 @@
 bit for bit, random 20 Msps histories over a wrapping 40 M sample ring (any split, device against host pushes, all four
 input formats, crossings that straddle the physical wrap and a push boundary), the column detectors, the detectors'
 tolerances, the tuned channel behind a DownConverter, and DataProcessor with the device path on."""
-import ctypes as C
 import os
 import types
 
@@ -10,7 +9,7 @@ import numpy as np
 import pytest
 
 import zero_span_contract as zc
-from topdogspectrumanalyser_amd import DataProcessor, ZeroSpan, _native as nat
+from topdogspectrumanalyser_amd import DataProcessor, DeviceBuffer, ZeroSpan, _native as nat
 from topdogspectrumanalyser_amd.zoom import DownConverter, design_decimator
 
 pytestmark = pytest.mark.gpu
@@ -24,24 +23,6 @@ BYTES = {"i8": 2, "u8": 2, "c64": 8, "f32r": 4}
 def _same(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True)
-
-
-class _Dev:
-    """A device buffer (freed on exit)."""
-
-    def __init__(self, nbytes):
-        self.p = C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes), 8), C.byref(self.p)))
-
-    def put(self, a, at=0):
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, C.c_void_p(self.p.value + at), a.ctypes.data_as(C.c_void_p), a.nbytes))
-        return self
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 def _check_view(zs, history, mode, level, n_display, what=""):
@@ -158,7 +139,7 @@ def test_random_histories_at_20_msps(fmt):
     def piece(a, b):
         return raw[step * a:step * b]
 
-    with ZeroSpan(FS) as za, ZeroSpan(FS) as zb, _Dev(n * bps) as dev:
+    with ZeroSpan(FS) as za, ZeroSpan(FS) as zb, DeviceBuffer(n * bps) as dev:
         assert za.capacity == cap
         for a in range(0, n, 8_000_000):
             dev.put(np.ascontiguousarray(piece(a, min(n, a + 8_000_000))), a * bps)
@@ -189,7 +170,7 @@ def test_random_histories_at_20_msps(fmt):
             if pos in (after_e2, after_wrap, n):
                 # handle B: the same stream from device memory, split elsewhere
                 for cb in [c for c in cuts_b if done_b < c <= pos]:
-                    zb.push_device(None, NAT_FMT[fmt], dev.p.value + done_b * bps, cb - done_b)
+                    zb.push_device(None, NAT_FMT[fmt], dev.at(done_b * bps, (cb - done_b) * bps), cb - done_b)
                     done_b = cb
                 assert done_b == pos
                 for nd, mode in ((20_000, "rise"), (1_000_000, "fall"), (40_000_000, "rise"), (3_000_000, "free_run")):
@@ -203,7 +184,7 @@ def test_random_histories_at_20_msps(fmt):
         v = za.view(mode="free_run", n_display=cap)
         assert v.total == n - 1_000_000 and _same(v.samples, history[n - cap:])
         zb.reset()
-        zb.push_device(None, NAT_FMT[fmt], dev.p.value + 1_000_000 * bps, n - 1_000_000)
+        zb.push_device(None, NAT_FMT[fmt], dev.at(1_000_000 * bps, (n - 1_000_000) * bps), n - 1_000_000)
         v = zb.view(mode="free_run", n_display=cap)
         assert v.total == n - 1_000_000 and _same(v.samples, history[n - cap:])
 
@@ -341,10 +322,10 @@ def test_tuned_channel_is_the_down_converter_then_the_detector(D):
     raw = np.clip(np.rint(np.stack([x.real, x.imag], axis=1) * 100), -128, 127).astype(np.int8).reshape(-1)
     with DownConverter(D, FS, f, taps) as ddc:
         y8 = ddc.process(raw)
-    with ZeroSpan(FS, decimation=D, offset_hz=f) as zs, _Dev(raw.nbytes) as dev:
+    with ZeroSpan(FS, decimation=D, offset_hz=f) as zs, DeviceBuffer(raw.nbytes) as dev:
         dev.put(raw)
-        assert zs.push_device(None, nat.IN_I8, dev.p.value, 123_457) + \
-            zs.push_device(None, nat.IN_I8, dev.p.value + 2 * 123_457, n - 123_457) == y8.size
+        assert zs.push_device(None, nat.IN_I8, dev.ptr, 123_457) + \
+            zs.push_device(None, nat.IN_I8, dev.at(2 * 123_457, 2 * (n - 123_457)), n - 123_457) == y8.size
         assert _same(zs.view(n_display=y8.size).samples, y8.real.copy())
 
 

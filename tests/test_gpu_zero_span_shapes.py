@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import zero_span_contract as zc
+from topdogspectrumanalyser_amd import DeviceBuffer
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]        # every test under a time limit of its own
 
@@ -35,32 +36,11 @@ def _fmt(fmt):
     return {"i8": nat.IN_I8, "u8": nat.IN_U8, "c64": nat.IN_C64, "f32r": nat.IN_F32R}[fmt]
 
 
-class _Dev:
-    """A device buffer (freed on exit); the base is aligned to at least 256 bytes."""
-
-    def __init__(self, nbytes):
-        nat = _nat()
-        self.p = C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes), 8), C.byref(self.p)))
-        assert self.p.value % 256 == 0
-
-    def put(self, a, at=0):
-        a = np.ascontiguousarray(a)
-        nat = _nat()
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, C.c_void_p(self.p.value + int(at)), a.ctypes.data_as(C.c_void_p), a.nbytes))
-        return self
-
-    def get(self, at, n, dtype=np.float32):
-        out = np.empty(int(n), dtype=dtype)
-        nat = _nat()
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.p.value + int(at)), out.nbytes))
-        return out
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        _nat().lib.tdsa_dev_free(0, self.p)
+def _aligned(nbytes):
+    """A DeviceBuffer whose base is aligned to at least 256 bytes."""
+    buf = DeviceBuffer(nbytes)
+    assert buf.ptr % 256 == 0
+    return buf
 
 
 class _Zs:
@@ -197,9 +177,9 @@ def test_push_every_head_body_and_tail_by_every_route(fmt, detector, cap):
     kw = dict(detector=detector, log_floor=LOG_FLOOR, offset_db=OFFSET_DB)
     worst = 0.0
     with _Zs(cap, **kw) as host, _Zs(cap, **kw) as d1, _Zs(cap, **kw) as d2, _Zs(cap, **kw) as d3, \
-            _Zs(cap, 1, **kw) as c1, _Zs(cap, 3, **kw) as c3, _Zs(cap, 8, **kw) as c8, _Dev(raw.nbytes + 64) as dev:
+            _Zs(cap, 1, **kw) as c1, _Zs(cap, 3, **kw) as c3, _Zs(cap, 8, **kw) as c8, _aligned(raw.nbytes + 64) as dev:
         # one copy of the stream per source offset: 1, 2 and 3 samples into the 16-byte-aligned allocation
-        with _Dev(raw.nbytes + 64) as dev2, _Dev(raw.nbytes + 64) as dev3:
+        with _aligned(raw.nbytes + 64) as dev2, _aligned(raw.nbytes + 64) as dev3:
             devs = ((d1, dev, 1), (d2, dev2, 2), (d3, dev3, 3))
             for _, buf, s in devs:
                 buf.put(raw, s * bps)
@@ -209,8 +189,8 @@ def test_push_every_head_body_and_tail_by_every_route(fmt, detector, cap):
                 for zs in (host, c1, c3, c8):
                     zs.push(piece, fmt)
                 for zs, buf, s in devs:
-                    assert (buf.p.value + s * bps) % 16 != 0 or fmt == "c64"
-                    zs.push_dev(buf.p.value + (s + done) * bps, fmt, n)
+                    assert buf.at(s * bps) % 16 != 0 or fmt == "c64"
+                    zs.push_dev(buf.at((s + done) * bps, n * bps), fmt, n)
                 done += n
                 lo = max(0, done - cap)
                 ring = host.ring()
@@ -306,16 +286,16 @@ def test_one_crossing_at_every_position(cap, nd, which, mode):
         ss, se = plan["search"]
         assert ss < cap - total % cap - 1 < se - 2
     starts, hits = set(), {}
-    with _Zs(cap) as zs, _Dev(both.nbytes) as dev:
+    with _Zs(cap) as zs, _aligned(both.nbytes) as dev:
         dev.put(both)
         for i in range(held - 1):
             k = base + i + 1                                      # the history: k samples before the step, the rest after
             history = both[total - k:2 * total - k]
             assert history[base + i] == a and history[base + i + 1] == b
             zs.reset()
-            src = dev.p.value + 4 * (total - k)
-            zs.push_dev(src, "f32r", total - held)                # the part that has left the ring, then the ring:
-            zs.push_dev(src + 4 * (total - held), "f32r", held)   # two launches when it starts inside the ring
+            src = 4 * (total - k)
+            zs.push_dev(dev.at(src, 4 * (total - held)), "f32r", total - held)     # the part that has left the ring,
+            zs.push_dev(dev.at(src + 4 * (total - held), 4 * held), "f32r", held)  # then the ring: two launches when it starts inside
             info, _ = _check_view(zs, history, mode, LEVEL, nd, tag=(cap, nd, total, mode, i))
             starts.add(info.start)
             hits[i] = info.triggered
@@ -454,7 +434,7 @@ def test_out_dev_out_host_and_both_give_the_same_bits():
     length = 1024 * 3 + 1
     rng = np.random.default_rng(5)
     e, cap, start = zc.train_case(length, 99)
-    with _Zs(cap) as zs, _Dev(4 * (length + 64)) as dev:
+    with _Zs(cap) as zs, _aligned(4 * (length + 64)) as dev:
         zs.push(_as_i8(e, rng), "i8")
         for points, column, n_out in ((0, "minmax", length), (3, "minmax", 6), (300, "minmax", 600), (300, "mean", 300)):
             chunk = zc.view(e, cap, length, "rise", 0.0)[2]
@@ -463,8 +443,8 @@ def test_out_dev_out_host_and_both_give_the_same_bits():
             got = {}
             for name, host in (("dev only", False), ("both", True)):
                 dev.put(np.full(length + 64, SENTINEL, dtype=F32))
-                info, out = zs.view("rise", 0.0, length, points, column, host=host, dev_ptr=dev.p.value + 16)
-                back = dev.get(0, length + 64)
+                info, out = zs.view("rise", 0.0, length, points, column, host=host, dev_ptr=dev.at(16))
+                back = dev.get(length + 64, F32)
                 assert np.all(back[:4] == SENTINEL) and np.all(back[4 + n_out:] == SENTINEL), (points, column, name)
                 got[name] = back[4:4 + n_out]
                 assert (info.start, info.triggered, info.length) == (start, 1, length)
@@ -476,7 +456,7 @@ def test_out_dev_out_host_and_both_give_the_same_bits():
         host = np.zeros(length, dtype=F32)
         for off in (1, 2, 3):
             rc = nat.lib.tdsa_zspan_view(zs.h, nat.ZS_RISE, 0.0, length, 0, 0, C.byref(info),
-                                         host.ctypes.data_as(C.c_void_p), C.c_void_p(dev.p.value + off))
+                                         host.ctypes.data_as(C.c_void_p), dev.at(off))
             assert rc == ERR_ARG and "aligned" in nat.lib.tdsa_last_error_string().decode()
     print("out_dev only / out_host only / both: the same bits, sentinels kept, odd pointers refused")
 
@@ -546,7 +526,7 @@ def test_totals_past_2_to_the_31_and_2_to_the_32():
             assert _same_values(v.min, st["min"]) and _same_values(v.max, st["max"]) and v.mean == st["mean"]
             return v
 
-    with ZeroSpan(rate) as za, ZeroSpan(rate) as zb, _Dev(2 * big) as dev:
+    with ZeroSpan(rate) as za, ZeroSpan(rate) as zb, _aligned(2 * big) as dev:
         assert za.capacity == cap and cap & (cap - 1) != 0
         a, b = Stream(za), Stream(zb)
 
@@ -554,12 +534,12 @@ def test_totals_past_2_to_the_31_and_2_to_the_32():
             """2^30 samples from device memory: only the last `cap` of them are read, and only those were written."""
             raw = _i8_block(rng, cap)
             dev.put(raw, 2 * (big - cap))
-            za.push_device(None, nat.IN_I8, dev.p.value, big)
+            za.push_device(None, nat.IN_I8, dev.ptr, big)
             a.add(raw, big)
             # the second handle starts again at 0 after every step, with a stream of its own through the same buffer
             zb.reset()
             b.tail, b.total = np.empty(0, dtype=F32), 0
-            zb.push_device(None, nat.IN_I8, dev.p.value + 2 * (big - cap - 7), cap + 7)
+            zb.push_device(None, nat.IN_I8, dev.at(2 * (big - cap - 7), 2 * (cap + 7)), cap + 7)
             b.add(raw, cap + 7)
             small = _i8_block(rng, 123)
             zb.push(small)

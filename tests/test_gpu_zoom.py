@@ -8,7 +8,7 @@ import pytest
 
 import zoom_contract as zc
 from oracle import spectrum_oracle as so
-from topdogspectrumanalyser_amd import Constellation, SpectrumEngine, _native as nat
+from topdogspectrumanalyser_amd import Constellation, DeviceBuffer, SpectrumEngine, _native as nat
 from topdogspectrumanalyser_amd.zoom import DownConverter, ZoomSpectrum, design_decimator, nco_step, zoom_window
 
 pytestmark = pytest.mark.gpu
@@ -32,29 +32,6 @@ def _split(raw, fmt, cuts):
 
 def _run(ddc, parts):
     return np.concatenate([ddc.process(p) for p in parts])
-
-
-class _Dev:
-    """A device buffer (freed on exit)."""
-
-    def __init__(self, nbytes):
-        self.p = C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes), 8), C.byref(self.p)))
-
-    def put(self, a):
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-        return self
-
-    def get(self, n, dtype):
-        out = np.empty(n, dtype=dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), self.p, out.nbytes))
-        return out
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 @pytest.mark.parametrize("D,T", [(8, 34 * 8), (5, 37), (3, 2)])
@@ -259,16 +236,16 @@ def test_composition_on_the_device():
     with DownConverter(D, FS, 0.05 * FS) as ddc:
         y_host = ddc.process(raw)
     with DownConverter(D, FS, 0.05 * FS) as ddc, SpectrumEngine(N, max_frames=64) as eng, \
-            Constellation(max_host_samples=1 << 16) as cst, _Dev(raw.nbytes) as d_in, \
-            _Dev(8 * (n // D + 1)) as d_y, _Dev(4 * 64 * N) as d_rows:
+            Constellation(max_host_samples=1 << 16) as cst, DeviceBuffer(raw.nbytes) as d_in, \
+            DeviceBuffer(8 * (n // D + 1)) as d_y, DeviceBuffer(4 * 64 * N) as d_rows:
         eng.set_window(zoom_window(N))
         eng.configure(db_mode="mag", dc_alpha=-1.0)
         d_in.put(raw)
-        n_out = ddc.process_device(eng, nat.IN_I8, d_in.p.value, n, d_y.p.value)
+        n_out = ddc.process_device(eng, nat.IN_I8, d_in.ptr, n, d_y.ptr)
         nf = (n_out - N) // N + 1
-        eng.process_device(nat.IN_C64, d_y.p.value, n_out, N, nf, d_rows.p.value)
+        eng.process_device(nat.IN_C64, d_y.ptr, n_out, N, nf, d_rows.ptr)
         seg = 1000
-        rms, evm = cst.process_segments(eng, d_y.p.value, nat.IN_C64, seg, seg, n_out // seg)
+        rms, evm = cst.process_segments(eng, d_y.ptr, nat.IN_C64, seg, seg, n_out // seg)
         eng.synchronize()
         rows_dev = d_rows.get(nf * N, np.float32).reshape(nf, N)
         y_dev = d_y.get(n_out, np.complex64)
@@ -290,18 +267,18 @@ def test_full_c3_capture():
     raw = rng.integers(-128, 128, 2 * n).astype(np.int8)
     h = design_decimator(D)
     n_out = zc.n_outputs(n, D)
-    with DownConverter(D, FS, 0.123 * FS) as ddc, SpectrumEngine(1024) as eng, _Dev(raw.nbytes) as d_in, \
-            _Dev(8 * (n_out + 8)) as d_y:
+    with DownConverter(D, FS, 0.123 * FS) as ddc, SpectrumEngine(1024) as eng, DeviceBuffer(raw.nbytes) as d_in, \
+            DeviceBuffer(8 * (n_out + 8)) as d_y:
         step = ddc.phase_step
         d_in.put(raw)
-        assert ddc.process_device(eng, nat.IN_I8, d_in.p.value, n, d_y.p.value) == n_out
+        assert ddc.process_device(eng, nat.IN_I8, d_in.ptr, n, d_y.ptr) == n_out
         eng.synchronize()
         one = d_y.get(n_out, np.complex64)
         ddc.reset()
         cuts = [0, 1, 999_999, 5_000_003, 5_000_064, 12_345_678, 19_999_999, n]
         got = 0
         for a, b in zip(cuts[:-1], cuts[1:]):
-            got += ddc.process_device(eng, nat.IN_I8, d_in.p.value + 2 * a, b - a, d_y.p.value + 8 * got)
+            got += ddc.process_device(eng, nat.IN_I8, d_in.at(2 * a, 2 * (b - a)), b - a, d_y.at(8 * got))
         assert got == n_out
         eng.synchronize()
         chunked = d_y.get(n_out, np.complex64)

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import zoom_contract as zc
-from topdogspectrumanalyser_amd import SpectrumEngine, _native as nat
+from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine, _native as nat
 from topdogspectrumanalyser_amd.utils.constants import DSPConstants
 from topdogspectrumanalyser_amd.zoom import DownConverter, ZoomSpectrum, design_decimator, zoom_window
 
@@ -58,30 +58,6 @@ def _check_bound(y, ref, bound, what):
     assert rmax <= 1.0, (what, "max", rmax)
     assert rrms <= 1.0, (what, "rms", rrms)
     return rmax, rrms
-
-
-class _Dev:
-    """A device buffer (freed on exit)."""
-
-    def __init__(self, nbytes):
-        self.p = C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, max(int(nbytes), 8), C.byref(self.p)))
-
-    def put(self, a):
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, self.p, a.ctypes.data_as(C.c_void_p), a.nbytes))
-        return self
-
-    def get(self, n, dtype, offset=0):
-        out = np.empty(n, dtype=dtype)
-        nat.check(nat.lib.tdsa_memcpy_d2h(0, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.p.value + offset),
-                                          out.nbytes))
-        return out
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        nat.lib.tdsa_dev_free(0, self.p)
 
 
 # ---- 1. exact-integer FIR ------------------------------------------------------------------------------------------
@@ -252,14 +228,14 @@ def test_streams_past_2_32_inputs(D):
     T = h.size
     checked = (127, 128, 255, 256)
     cap = nb // D + 2
-    with DownConverter(D, FS, 0.123 * FS, max_host_samples=64) as ddc, _Dev(raw.nbytes) as d_in, \
-            _Dev(8 * cap * (1 + len(checked))) as d_y:
+    with DownConverter(D, FS, 0.123 * FS, max_host_samples=64) as ddc, DeviceBuffer(raw.nbytes) as d_in, \
+            DeviceBuffer(8 * cap * (1 + len(checked))) as d_y:
         step = ddc.phase_step
         d_in.put(raw)
         total, spans = 0, []
         for i in range(reps):                               # every other call overwrites slot 0
             slot = 1 + checked.index(i) if i in checked else 0
-            k = ddc.process_device(None, nat.IN_I8, d_in.p.value, nb, d_y.p.value + 8 * cap * slot)
+            k = ddc.process_device(None, nat.IN_I8, d_in.ptr, nb, d_y.at(8 * cap * slot))
             assert k <= cap
             if slot:
                 spans.append((total, k, slot))

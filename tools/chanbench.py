@@ -17,7 +17,6 @@ work is launched on.
     python tools/chanbench.py [--out profiles/chanbench.txt] [--reps 20]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -46,12 +45,11 @@ def median_us(eng, f, warm, reps):
     return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
-def capture(nat, n):
+def capture(n):
+    from topdogspectrumanalyser_amd import DeviceBuffer
     rng = np.random.default_rng(4)
     iq = rng.integers(-128, 128, 2 * n).astype(np.int8)
-    d = nat._dev_alloc(0, iq.nbytes)
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-    return iq, d
+    return iq, DeviceBuffer.of(iq)
 
 
 def step_copy(args):
@@ -75,15 +73,15 @@ def step_copy(args):
 
 
 def step_bank(args, M, os_):
-    from topdogspectrumanalyser_amd import Channelizer, DownConverter, SpectrumEngine, _native as nat
+    from topdogspectrumanalyser_amd import Channelizer, DeviceBuffer, DownConverter, SpectrumEngine, _native as nat
     from topdogspectrumanalyser_amd.zoom import design_decimator
     D = M // os_
     n = N_SEC // D * D
     n_out = n // D
-    _, d_in = capture(nat, n)
-    d_out = nat._dev_alloc(0, 8 * M * n_out)
+    _, d_in = capture(n)
+    d_out = DeviceBuffer(8 * M * n_out)
     with SpectrumEngine(64) as eng, Channelizer(M, FS, os_) as bank:
-        us, lo, hi = median_us(eng, lambda: bank.process_device(eng, nat.IN_I8, d_in.value, n, d_out.value, n_out),
+        us, lo, hi = median_us(eng, lambda: bank.process_device(eng, nat.IN_I8, d_in.ptr, n, d_out.ptr, n_out),
                                args.warm, args.reps)
         floor = n * (2 + 8 * os_) / args.copy_bps * 1e6
         taps = bank.taps if bank.taps.size <= 64 * D else design_decimator(M, 32)
@@ -91,10 +89,10 @@ def step_bank(args, M, os_):
             def passes():
                 for c in range(M):
                     nat.check(nat.lib.tdsa_ddc_set_nco(ddc._h, (c << 32) // M))
-                    ddc.process_device(eng, nat.IN_I8, d_in.value, n, d_out.value + 8 * c * n_out)
+                    ddc.process_device(eng, nat.IN_I8, d_in.ptr, n, d_out.at(8 * c * n_out))
             us_d = median_us(eng, passes, 1, args.reps)
     for p in (d_in, d_out):
-        nat.lib.tdsa_dev_free(0, p)
+        p.close()
     return dict(text=[
         f"bank M={M:3d} os={os_}: {n} samples, {bank.taps.size // M} taps per branch: {us:9.1f} us (min {lo:.1f}, max {hi:.1f}); "
         f"memory floor {floor:8.1f} us ({2 + 8 * os_} bytes per sample at the copy rate) = {100 * floor / us:5.1f}% of the time; "
@@ -103,18 +101,18 @@ def step_bank(args, M, os_):
 
 
 def step_spectra(args):
-    from topdogspectrumanalyser_amd import ChannelSpectra, _native as nat
+    from topdogspectrumanalyser_amd import ChannelSpectra, DeviceBuffer, _native as nat
     M, os_, nfft = 64, 2, 1024
     F = N_SEC // (M // os_ * nfft)
     n = F * (M // os_) * nfft
-    _, d_in = capture(nat, n)
-    d_rows = nat._dev_alloc(0, 4 * M * F * nfft)
+    _, d_in = capture(n)
+    d_rows = DeviceBuffer(4 * M * F * nfft)
     with ChannelSpectra(FS, M, nfft, oversample=os_, max_frames=F) as cs:
-        us, lo, hi = median_us(cs.engine, lambda: cs.process_device(nat.IN_I8, d_in.value, n, d_rows.value),
+        us, lo, hi = median_us(cs.engine, lambda: cs.process_device(nat.IN_I8, d_in.ptr, n, d_rows.ptr),
                                args.warm, args.reps)
         rbw = cs.rbw
     for p in (d_in, d_rows):
-        nat.lib.tdsa_dev_free(0, p)
+        p.close()
     return dict(text=[
         f"spectra M={M} os={os_} nfft={nfft}: {n} samples -> {M} x {F} frames ({M * F} in one frame-kernel launch), dB rows "
         f"in HBM, RBW {rbw:.1f} Hz: {us:9.1f} us (min {lo:.1f}, max {hi:.1f})"])

@@ -11,7 +11,6 @@
     python tools/constellationbench.py [--out profiles/constellationbench.txt]
 """
 import argparse
-import ctypes as C
 import os
 import sys
 import time
@@ -19,7 +18,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import Constellation, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd import Constellation, DeviceBuffer, _native as nat  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E peak, as bench.py
 MODS = ("bpsk", "qpsk", "8psk", "16qam", "64qam", "ofdm")
@@ -64,27 +63,26 @@ def main():
                                  127).astype(np.int8),
             "hot": np.tile(np.array([40, -40], np.int8), ns),
         }
-        d_in, d_cnt = C.c_void_p(), C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, 2 * ns, C.byref(d_in)))
-        nat.check(nat.lib.tdsa_dev_alloc(0, n_seg * 128 * 128 * 4, C.byref(d_cnt)))
+        d_in = DeviceBuffer(2 * ns)
+        d_cnt = DeviceBuffer(n_seg * 128 * 128 * 4)
         try:
             say(f"capture: {ns} int8 samples in HBM as {n_seg} segments of {seg}; floor = 4 B/sample at "
                 f"{HBM_PEAK_GBS:.0f} GB/s = {4 * ns / (HBM_PEAK_GBS * 1e9) * 1e6:.1f} us")
             for name, raw in cases.items():
-                nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, raw.ctypes.data_as(C.c_void_p), raw.nbytes))
+                d_in.put(raw)
                 for mod in ("qpsk", "64qam", "8psk"):
                     c.set_modulation(mod)
                     for hist in (True, False):
-                        cnt = d_cnt.value if hist else None
-                        med, _ = median_call(lambda: c.process_segments(None, d_in.value, nat.IN_I8, seg, seg, n_seg,
+                        cnt = d_cnt.ptr if hist else None
+                        med, _ = median_call(lambda: c.process_segments(None, d_in.ptr, nat.IN_I8, seg, seg, n_seg,
                                                                          cnt), warm=3, reps=15)
                         rate = ns / med
                         frac = 4 * ns / med / (HBM_PEAK_GBS * 1e9)
                         say(f"  {name:9s} {mod:6s} hist={'on ' if hist else 'off'} {med * 1e3:7.3f} ms  "
                             f"{rate / 1e9:6.2f} G samples/s  {frac * 100:5.1f} % of the HBM floor")
         finally:
-            nat.lib.tdsa_dev_free(0, d_in)
-            nat.lib.tdsa_dev_free(0, d_cnt)
+            d_in.close()
+            d_cnt.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

@@ -17,7 +17,6 @@ work is launched on.
 """
 import argparse
 import csv
-import ctypes as C
 import glob
 import json
 import os
@@ -79,23 +78,23 @@ def step_copy(args):
 
 
 def step_demod(args, mode):
-    from topdogspectrumanalyser_amd import Channelizer, Demodulator, SpectrumEngine, _native as nat
+    from topdogspectrumanalyser_amd import Channelizer, Demodulator, DeviceBuffer, SpectrumEngine, _native as nat
     D = M // OS
     n = N_SEC // D * D
     ny = n // D
     iq = capture(n)
-    d_in = nat._dev_alloc(0, iq.nbytes)
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-    d_y = nat._dev_alloc(0, 8 * M * ny)
+    d_in = DeviceBuffer(iq.nbytes)
+    d_in.put(iq)
+    d_y = DeviceBuffer(8 * M * ny)
     kw = dict(deemphasis=TAU) if mode == "fm" else dict(remove_carrier=True)
     with SpectrumEngine(64) as eng, Channelizer(M, FS, OS) as bank, \
             Demodulator(mode, FS / D, R, M, max_host_samples=M, **kw) as dm:
-        bank.process_device(eng, nat.IN_I8, d_in.value, n, d_y.value, ny)
+        bank.process_device(eng, nat.IN_I8, d_in.ptr, n, d_y.ptr, ny)
         na = ny // R                             # a whole number of outputs per call: every call does the same work
-        d_a = nat._dev_alloc(0, 4 * M * na)
+        d_a = DeviceBuffer(4 * M * na)
 
         def call():
-            dm.process_device(eng, d_y.value, na * R, ny, d_a.value, na)
+            dm.process_device(eng, d_y.ptr, na * R, ny, d_a.ptr, na)
 
         us, lo, hi = median_us(eng, call, args.warm, args.reps)
         eng.synchronize()
@@ -103,7 +102,7 @@ def step_demod(args, mode):
     ny = na * R
     floor = M * ny * (8 + 4.0 / R) / args.copy_bps * 1e6 if args.copy_bps else float("nan")
     for p in (d_in, d_y, d_a):
-        nat.lib.tdsa_dev_free(0, p)
+        p.close()
     return dict(text=[
         f"{mode} R={R}: {M} channels x {ny} samples at {FS / D / 1e3:.1f} kHz, {taps // R} taps per phase, one-pole section on: "
         f"{us:9.1f} us (min {lo:.1f}, max {hi:.1f}); memory floor {floor:8.1f} us (8 bytes in, 4 / {R} out per channel sample at "

@@ -17,7 +17,6 @@ advance: each figure stands next to its memory floor.
     python tools/detectbench.py [--out profiles/detectbench.txt] [--reps 20]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -87,14 +86,14 @@ def step_copy(args):
 
 
 def _detect(args, kind, **kw):
-    from topdogspectrumanalyser_amd import SignalDetector, _native as nat
+    from topdogspectrumanalyser_amd import DeviceBuffer, SignalDetector
     rows = capture(kind)
-    d_rows = nat._dev_alloc(0, rows.nbytes)
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_rows, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+    d_rows = DeviceBuffer(rows.nbytes)
+    d_rows.put(rows)
     with SignalDetector(N_BINS, max_host_rows=1, **kw) as d:
-        us, lo, hi = median_us(d, lambda: d.process_device(None, d_rows.value, N_ROWS), args.warm, args.reps)
-        r = d.process_device(None, d_rows.value, N_ROWS)
-    nat.lib.tdsa_dev_free(0, d_rows)
+        us, lo, hi = median_us(d, lambda: d.process_device(None, d_rows.ptr, N_ROWS), args.warm, args.reps)
+        r = d.process_device(None, d_rows.ptr, N_ROWS)
+    d_rows.close()
     fl = floor_us(args.copy_bps)
     return r, (f"{us:9.1f} us (min {lo:.1f}, max {hi:.1f}); memory floor {fl:7.1f} us (4 bytes read per bin at the copy "
                f"rate) = {100 * fl / us:5.1f}% of the time")
@@ -116,15 +115,15 @@ def step_worst(args):
 
 
 def step_scale(args):
-    from topdogspectrumanalyser_amd import SpectrumEngine, analytics as an, _native as nat
+    from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine, analytics as an
     rows = capture("second")
-    d_rows = nat._dev_alloc(0, rows.nbytes)
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_rows, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+    d_rows = DeviceBuffer(rows.nbytes)
+    d_rows.put(rows)
     freq = np.linspace(90e6, 110e6, N_BINS)
     with SpectrumEngine(64) as eng:
-        mk = median_us(eng, lambda: an.rows_marker_peaks(eng, d_rows.value, N_ROWS, N_BINS), args.warm, args.reps)
-        st = median_us(eng, lambda: an.rows_stats(eng, d_rows.value, N_ROWS, N_BINS, freq, (95e6, 105e6)), args.warm, args.reps)
-    nat.lib.tdsa_dev_free(0, d_rows)
+        mk = median_us(eng, lambda: an.rows_marker_peaks(eng, d_rows.ptr, N_ROWS, N_BINS), args.warm, args.reps)
+        st = median_us(eng, lambda: an.rows_stats(eng, d_rows.ptr, N_ROWS, N_BINS, freq, (95e6, 105e6)), args.warm, args.reps)
+    d_rows.close()
     fl = floor_us(args.copy_bps)
     return dict(text=[
         f"scale: on the rows of `second`, tdsa_rows_marker_peaks (reference defaults) {mk[0]:9.1f} us (min {mk[1]:.1f}, max "

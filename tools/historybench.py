@@ -14,7 +14,6 @@ calls, then the median of `--reps` (at least 20) single calls, each between devi
     python tools/historybench.py [--out profiles/historybench.txt] [--reps 20]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -48,13 +47,11 @@ def median_us(h, f, warm, reps):
     return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
-def fill(nat, h, rng, n_rows):
-    rows = rows_db(rng, n_rows)
-    d = nat._dev_alloc(0, rows.nbytes)
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
-    h.push_rows(None, d.value, n_rows)
-    h.lines(0, 1) if h.kind == "heights" else h.surface(columns=1)
-    nat.lib.tdsa_dev_free(0, d)
+def fill(h, rng, n_rows):
+    from topdogspectrumanalyser_amd import DeviceBuffer
+    with DeviceBuffer.of(rows_db(rng, n_rows)) as d:
+        h.push_rows(None, d.ptr, n_rows)
+        h.lines(0, 1) if h.kind == "heights" else h.surface(columns=1)
 
 
 def step_copy(args):
@@ -78,32 +75,32 @@ def step_copy(args):
 
 
 def step_push(args):
-    from topdogspectrumanalyser_amd import TraceHistory, _native as nat
+    from topdogspectrumanalyser_amd import DeviceBuffer, TraceHistory
     rng = np.random.default_rng(1)
     rows = rows_db(rng, PUSH_ROWS)
-    d = nat._dev_alloc(0, rows.nbytes)
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+    d = DeviceBuffer(rows.nbytes)
+    d.put(rows)
     text = []
     for kind, depth in (("heights", 300), ("levels", 100)):
         with TraceHistory(depth, N, kind) as h:
-            us, lo, hi = median_us(h, lambda: h.push_rows(None, d.value, PUSH_ROWS), args.warm, args.reps)
-            one = median_us(h, lambda: h.push_rows(None, d.value, 1), args.warm, args.reps)[0]
+            us, lo, hi = median_us(h, lambda: h.push_rows(None, d.ptr, PUSH_ROWS), args.warm, args.reps)
+            one = median_us(h, lambda: h.push_rows(None, d.ptr, 1), args.warm, args.reps)[0]
             moved = PUSH_ROWS * N * 8
             text.append(f"push {kind:8s}: {PUSH_ROWS} rows in one call {us:9.1f} us (min {lo:.1f}, max {hi:.1f}) = "
                         f"{us / PUSH_ROWS:7.3f} us per row, {moved / us / 1e6:7.3f} TB/s = "
                         f"{100 * moved / us * 1e6 / args.copy_bps:5.1f}% of the copy rate; one row per call {one:7.1f} us")
-    nat.lib.tdsa_dev_free(0, d)
+    d.close()
     return dict(text=text)
 
 
 def view_step(args, name):
-    from topdogspectrumanalyser_amd import TraceHistory, _native as nat
+    from topdogspectrumanalyser_amd import DeviceBuffer, TraceHistory
     rng = np.random.default_rng(2)
     x = np.linspace(-10, 10, N, dtype=np.float32)
     kind, depth = ("levels", 100) if name == "surface" else ("heights", 30 if name == "ribbon" else 300)
     text = []
     with TraceHistory(depth, N, kind) as h:
-        fill(nat, h, rng, depth + 5)
+        fill(h, rng, depth + 5)
         variants = [("index",), ("rgba",)] if name == "lines" else [()]
         for var in variants:
             for cols in (None, 1024):
@@ -112,8 +109,8 @@ def view_step(args, name):
                 per = {"ribbon": (24, 32), "surface": (4, 12), "lines": (4, 16 if var == ("rgba",) else 1)}[name]
                 out_bytes = R * n * (per[0] + per[1])
                 read_bytes = R * N * 4 + (R * n * 12 if cols else 0)       # the rows; reduced: values + bins written, values read
-                d0, d1 = nat._dev_alloc(0, R * n * per[0]), nat._dev_alloc(0, R * n * per[1])
-                dest = dict(primary=d0.value, colours=d1.value)
+                d0, d1 = DeviceBuffer(R * n * per[0]), DeviceBuffer(R * n * per[1])
+                dest = dict(primary=d0.ptr, colours=d1.ptr)
                 if name == "ribbon":
                     on_dev, on_host = (lambda: h.ribbon(x, cols, device_out=dest)), (lambda: h.ribbon(x, cols))
                 elif name == "lines":
@@ -134,8 +131,8 @@ def view_step(args, name):
                             f"(min {us_d[1]:.1f}, max {us_d[2]:.1f}), {moved / 1e6:8.2f} MB moved = {moved / us_d[0] / 1e6:6.3f} TB/s = "
                             f"{100 * moved / us_d[0] * 1e6 / args.copy_bps:5.1f}% of the copy rate; host destination "
                             f"{us_h[0]:9.1f} us on the stream, {np.median(walls):9.1f} us wall, {d2h / 1e6:8.2f} MB to the host")
-                nat.lib.tdsa_dev_free(0, d0)
-                nat.lib.tdsa_dev_free(0, d1)
+                d0.close()
+                d1.close()
     return dict(text=text)
 
 

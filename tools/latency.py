@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool: what one displayed frame costs through the host entry point (what the live sources do on every
 GUI tick): total per call, and the same frame with the samples already on the device."""
-import ctypes as C
 import os
 import sys
 import time
@@ -9,7 +8,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import SpectrumEngine, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine, _native as nat  # noqa: E402
 
 
 def main():
@@ -28,19 +27,17 @@ def main():
                 host = (time.perf_counter() - t0) / 2000 * 1e6
                 print(f"N={n:6d} {name:9s}: {host:6.1f} us per host call", end="")
                 if name == "int8":
-                    d_in, d_out = C.c_void_p(), C.c_void_p()
-                    nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(d_in)))
-                    nat.check(nat.lib.tdsa_dev_alloc(0, n * 4, C.byref(d_out)))
-                    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_in, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-                    for _ in range(200):
-                        e.process_device(nat.IN_I8, d_in.value, n, n, 1, d_out.value)
-                    e.synchronize()
-                    t0 = time.perf_counter()
-                    for _ in range(2000):
-                        e.process_device(nat.IN_I8, d_in.value, n, n, 1, d_out.value)
+                    with DeviceBuffer(iq.nbytes) as d_in, DeviceBuffer(n * 4) as d_out:
+                        d_in.put(iq)
+                        for _ in range(200):
+                            e.process_device(nat.IN_I8, d_in.ptr, n, n, 1, d_out.ptr)
                         e.synchronize()
-                    dev = (time.perf_counter() - t0) / 2000 * 1e6
-                    print(f"   device-resident + synchronize: {dev:6.1f} us", end="")
+                        t0 = time.perf_counter()
+                        for _ in range(2000):
+                            e.process_device(nat.IN_I8, d_in.ptr, n, n, 1, d_out.ptr)
+                            e.synchronize()
+                        dev = (time.perf_counter() - t0) / 2000 * 1e6
+                        print(f"   device-resident + synchronize: {dev:6.1f} us", end="")
                 print()
 
     # the display processor's share of a tick: calibration offset, tare, both holds in one launch (TraceState.update)
@@ -89,17 +86,15 @@ def main():
         row = np.random.default_rng(4).normal(-80, 5, n).astype(np.float32)
         row[n // 3] = -20.0
         with SpectrumEngine(n, max_frames=1) as e, an.DensityHistogram(n, 0.96) as dh, an.WaterfallRing(600, n, -120.0) as wf:
-            d_row = C.c_void_p()
-            nat.check(nat.lib.tdsa_dev_alloc(0, n * 4, C.byref(d_row)))
-            nat.check(nat.lib.tdsa_memcpy_h2d(0, d_row, row.ctypes.data_as(C.c_void_p), n * 4))
+            d_row = DeviceBuffer.of(row)
             rows2 = [row, row + np.float32(0.5)]
             calls = (("density update (host row)", lambda i: dh.update(rows2[i & 1])),
                      ("waterfall push (host row)", lambda i: wf.push(rows2[i & 1])),
                      ("waterfall view_u8 (600 lines back)", lambda i: wf.view_u8(-110.0, -20.0)),
-                     ("top-5 peaks of one device row", lambda i: an.rows_top_peaks(e, d_row.value, 1)),
-                     ("marker search of one device row", lambda i: an.rows_marker_peaks(e, d_row.value, 1, peak_threshold=-60.0,
+                     ("top-5 peaks of one device row", lambda i: an.rows_top_peaks(e, d_row.ptr, 1)),
+                     ("marker search of one device row", lambda i: an.rows_marker_peaks(e, d_row.ptr, 1, peak_threshold=-60.0,
                                                                                         peak_excursion=6.0)),
-                     ("peak / argmax / band of one device row", lambda i: an.rows_stats(e, d_row.value, 1)))
+                     ("peak / argmax / band of one device row", lambda i: an.rows_stats(e, d_row.ptr, 1)))
             for name, fn in calls:
                 reps = 200 if "view" in name else 2000
                 for i in range(50):
@@ -108,7 +103,7 @@ def main():
                 for i in range(reps):
                     fn(i)
                 print(f"N={n:6d} {name:40s}: {(time.perf_counter() - t0) / reps * 1e6:7.1f} us")
-            nat.lib.tdsa_dev_free(0, d_row)
+            d_row.close()
 
 if __name__ == "__main__":
     main()

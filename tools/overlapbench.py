@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Developer experiment: do consecutive frame-kernel launches overlap usefully when issued on two streams?
 Two plans (each with its own stream) take alternate steps; compares wall time per step with one plan."""
-import ctypes as C
 import os as _os
 if _os.environ.get("TDSA_TORCH_FIRST"):
     import torch  # noqa: F401  (same HIP runtime as bench.py)
@@ -12,7 +11,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import SpectrumEngine, _native as nat  # noqa: E402
+from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine, _native as nat  # noqa: E402
 
 
 def main():
@@ -23,11 +22,8 @@ def main():
     ins, outs = [], []
     for r in range(ring):
         iq = rng.integers(-100, 100, size=2 * ns, dtype=np.int8)
-        di, do = C.c_void_p(), C.c_void_p()
-        nat.check(nat.lib.tdsa_dev_alloc(0, iq.nbytes, C.byref(di)))
-        nat.check(nat.lib.tdsa_dev_alloc(0, F * n * 4, C.byref(do)))
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, di, iq.ctypes.data_as(C.c_void_p), iq.nbytes))
-        ins.append(di.value); outs.append(do.value)
+        ins.append(DeviceBuffer.of(iq))
+        outs.append(DeviceBuffer(F * n * 4))
     engs = []
     for _ in range(3):
         e = SpectrumEngine(n, max_frames=F)
@@ -43,7 +39,7 @@ def main():
         for e in use:
             e.set_overlap(1)
         for i in range(steps):
-            use[i % k].process_device(nat.IN_I8, ins[i % ring], ns, hop, F, outs[i % ring])
+            use[i % k].process_device(nat.IN_I8, ins[i % ring].ptr, ns, hop, F, outs[i % ring].ptr)
         for e in use:
             e.synchronize()
 
@@ -51,7 +47,7 @@ def main():
         e = engs[0]
         e.set_overlap(k)
         for i in range(steps):
-            e.process_device(nat.IN_I8, ins[i % ring], ns, hop, F, outs[i % ring])
+            e.process_device(nat.IN_I8, ins[i % ring].ptr, ns, hop, F, outs[i % ring].ptr)
         e.synchronize()
 
     if os.environ.get("AVG"):
@@ -72,6 +68,8 @@ def main():
         v = np.array(acc[name]) * 1e6
         print(f"{name:24s}: median {np.median(v):6.1f} us per step (min {v.min():.1f}, max {v.max():.1f}) -> "
               f"{F/np.median(v):.2f} Mframes/s")
+    for h in engs + ins + outs:                 # the plans first: nothing is queued on a buffer that goes
+        h.close()
 
 
 if __name__ == "__main__":

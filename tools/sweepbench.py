@@ -25,8 +25,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import SpectrumEngine, SweepAssembler, _native as nat, plan_steps  # noqa: E402
-from topdogspectrumanalyser_amd._native import _dev_alloc  # noqa: E402
+from topdogspectrumanalyser_amd import (DeviceBuffer, SpectrumEngine, SweepAssembler, _native as nat,  # noqa: E402
+                                        plan_steps)
 from topdogspectrumanalyser_amd.sweep import frequency_grid  # noqa: E402
 from topdogspectrumanalyser_amd.zoom import zoom_window  # noqa: E402
 
@@ -66,8 +66,8 @@ def main():
     rng = np.random.default_rng(1)
     raw = rng.integers(-128, 128, (S, 2 * n_per)).astype(np.int8)
     row_bytes, det_bytes = 4 * S * F * N, 4 * S * F * K
-    d_iq, d_rows, d_copy = _dev_alloc(0, raw.nbytes), _dev_alloc(0, row_bytes), _dev_alloc(0, det_bytes)
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_iq, raw.ctypes.data_as(C.c_void_p), raw.nbytes))
+    d_iq, d_rows, d_copy = DeviceBuffer(raw.nbytes), DeviceBuffer(row_bytes), DeviceBuffer(det_bytes)
+    d_iq.put(raw)
     say(f"sweep {START / 1e9:.0f} .. {STOP / 1e9:.0f} GHz: fs {FS / 1e6:.0f} MHz, N {N}, kept bins [{k0}, {k1}) of {bin_hz:.3f} Hz, "
         f"{S} steps x {F} frames at hop {N}, int8 IQ in HBM ({raw.nbytes / 1e6:.1f} MB), rows {row_bytes / 1e6:.1f} MB, "
         f"kept part of the rows {det_bytes / 1e6:.1f} MB")
@@ -78,24 +78,24 @@ def main():
             eng.configure(db_mode="mag", log_floor=1e-12, dc_alpha=-1.0)
 
             def batch():
-                eng.process_device_batch(nat.IN_I8, d_iq.value, 2 * n_per, S, n_per, N, F, d_rows.value)
+                eng.process_device_batch(nat.IN_I8, d_iq.ptr, 2 * n_per, S, n_per, N, F, d_rows.ptr)
 
             us_a = timed(eng, batch, args.warm, args.reps)
             say(f"(a) tdsa_process_dev_batch, rows alone: {us_a:9.1f} us")
-            us_d = timed(eng, lambda: nat.check(nat.lib.tdsa_plan_copy(eng._h, d_copy, d_rows, det_bytes, 0)),
+            us_d = timed(eng, lambda: nat.check(nat.lib.tdsa_plan_copy(eng._h, d_copy.ptr, d_rows.ptr, det_bytes, 0)),
                               args.warm, args.reps)
             say(f"(d) device-to-device copy of {det_bytes / 1e6:.1f} MB: {us_d:9.1f} us "
                 f"({det_bytes / us_d / 1e3:.0f} GB/s read, as much written)")
             for n_grid, bin_size in GRIDS:
                 grid = frequency_grid(START, STOP, bin_size)
                 assert grid.size == n_grid
-                d_out = _dev_alloc(0, 8 * n_grid)
+                d_out = DeviceBuffer(8 * n_grid)
                 try:
                     with SweepAssembler(N, centres, (k0, k1), bin_hz, grid) as asm:
                         say(f"--- grid of {n_grid} points ({bin_size / 1e3:.0f} kHz cells, {bin_size / bin_hz:.1f} bins each)")
                         batch()
                         for det in DETECTORS:
-                            us = timed(eng, lambda: asm.update_device(eng, 0, S, d_rows.value, F, det),
+                            us = timed(eng, lambda: asm.update_device(eng, 0, S, d_rows.ptr, F, det),
                                             args.warm, args.reps)
                             rd = 4 * S * K if det == "sample" else det_bytes
                             say(f"(c) detector {det:>6s} alone: {us:9.1f} us, reads {rd / 1e6:7.1f} MB, {rd / us / 1e3:6.0f} GB/s"
@@ -103,17 +103,17 @@ def main():
                                    if det != "sample" else ""))
                         eng.synchronize()
                         for mode in ("interp", "peak"):
-                            us = timed(asm, lambda: asm.read(mode, out_dev=d_out.value, to_host=False),
+                            us = timed(asm, lambda: asm.read(mode, out_dev=d_out.ptr, to_host=False),
                                              args.warm, args.reps)
                             rd = 8 * n_grid + 4 * S * K
                             say(f"(c) stitch {mode:>6s} alone: {us:9.1f} us, reads <= {rd / 1e6:6.1f} MB "
                                 f"(grid + T), writes {8 * n_grid / 1e6:.2f} MB, {(rd + 8 * n_grid) / us / 1e3:6.0f} GB/s")
                         for det in DETECTORS:
                             def run():
-                                asm.run_device(eng, nat.IN_I8, d_iq.value, 2 * n_per, 0, S, n_per, N, F, det)
+                                asm.run_device(eng, nat.IN_I8, d_iq.ptr, 2 * n_per, 0, S, n_per, N, F, det)
                             us_run = timed(eng, run, args.warm, args.reps)
                             for mode in ("interp", "peak"):
-                                us_read = timed(asm, lambda: asm.read(mode, out_dev=d_out.value, to_host=False),
+                                us_read = timed(asm, lambda: asm.read(mode, out_dev=d_out.ptr, to_host=False),
                                                       1, args.reps)
                                 run()
                                 asm.read(mode)
@@ -127,20 +127,20 @@ def main():
                         if n_grid == GRIDS[0][0]:
                             for mib in (8, 16, 32, 64, 128, 256):
                                 asm.set_chunk_bytes(mib << 20)
-                                us = timed(eng, lambda: asm.run_device(eng, nat.IN_I8, d_iq.value, 2 * n_per, 0, S,
+                                us = timed(eng, lambda: asm.run_device(eng, nat.IN_I8, d_iq.ptr, 2 * n_per, 0, S,
                                                                             n_per, N, F, "avg"), args.warm, args.reps)
                                 steps = max(1, min(S, (mib << 20) // (4 * F * N)))
                                 say(f"    run_dev avg, row scratch bound {mib:4d} MiB ({steps:3d} steps per chunk): {us:9.1f} us")
                             asm.set_chunk_bytes(256 << 20)
                 finally:
-                    nat.lib.tdsa_dev_free(0, d_out)
+                    d_out.close()
             # (e) without the assembler: rows to the host, numpy
             import sweep_contract as sc
             batch()
             rows = np.empty((S, F, N), dtype=np.float32)
             t0 = time.perf_counter()
             batch()
-            nat.check(nat.lib.tdsa_plan_copy(eng._h, rows.ctypes.data_as(C.c_void_p), d_rows, rows.nbytes, 1))
+            nat.check(nat.lib.tdsa_plan_copy(eng._h, rows.ctypes.data_as(C.c_void_p), d_rows.ptr, rows.nbytes, 1))
             t1 = time.perf_counter()
             T = np.stack([sc.detector(rows[s], k0, k1, "avg") for s in range(S)])
             t2 = time.perf_counter()
@@ -151,7 +151,7 @@ def main():
                 f"{1e3 * (t2 - t1):.1f} ms, np.interp onto {grid.size} points {1e3 * (t3 - t2):.1f} ms")
     finally:
         for p in (d_iq, d_rows, d_copy):
-            nat.lib.tdsa_dev_free(0, p)
+            p.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

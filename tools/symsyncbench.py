@@ -16,7 +16,6 @@ stream; a call ends when the segments' records are in host memory, so the figure
     python tools/symsyncbench.py [--out profiles/symsyncbench.txt] [--reps 20]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -79,42 +78,42 @@ def step_copy(args):
 
 
 def step_tick(args):
-    from topdogspectrumanalyser_amd import SymbolSync, _native as nat
+    from topdogspectrumanalyser_amd import DeviceBuffer, SymbolSync
     x = signal(TICK, SPS)
     with SymbolSync(SPS, "qpsk") as s:
         K = s.symbols_per_segment(TICK)
-        d_x, d_s = nat._dev_alloc(0, x.nbytes), nat._dev_alloc(0, 8 * K)
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_x, x.ctypes.data_as(C.c_void_p), x.nbytes))
-        us, lo, hi = median_us(s, lambda: s.process_device(None, d_x.value, TICK, TICK, 1, d_s.value, K), args.warm, args.reps)
+        d_x, d_s = DeviceBuffer(x.nbytes), DeviceBuffer(8 * K)
+        d_x.put(x)
+        us, lo, hi = median_us(s, lambda: s.process_device(None, d_x.ptr, TICK, TICK, 1, d_s.ptr, K), args.warm, args.reps)
         t0 = time.perf_counter()
         for _ in range(args.reps):
             s.process(x, TICK)
         host_us = (time.perf_counter() - t0) / args.reps * 1e6
         for p in (d_x, d_s):
-            nat.lib.tdsa_dev_free(0, p)
+            p.close()
     return dict(text=[
         f"tick: {TICK} samples at {SPS} samples per symbol, one segment, K = {K}, qpsk: {us:8.1f} us (min {lo:.1f}, max {hi:.1f}) "
         f"in device memory; from and to host memory (SymbolSync.process, wall clock, mean of {args.reps}) {host_us:8.1f} us"])
 
 
 def step_second(args):
-    from topdogspectrumanalyser_amd import DownConverter, SpectrumEngine, SymbolSync, _native as nat
+    from topdogspectrumanalyser_amd import DeviceBuffer, DownConverter, SpectrumEngine, SymbolSync, _native as nat
     from topdogspectrumanalyser_amd.symbols import rrc_taps
     x = signal(N_SEC, SPS * D)
     ny = N_SEC // D
     n_seg = ny // SEG
-    d_x, d_y = nat._dev_alloc(0, x.nbytes), nat._dev_alloc(0, 8 * (ny + 8))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_x, x.ctypes.data_as(C.c_void_p), x.nbytes))
+    d_x, d_y = DeviceBuffer(x.nbytes), DeviceBuffer(8 * (ny + 8))
+    d_x.put(x)
     with SpectrumEngine(64) as eng, DownConverter(D, 20e6, taps=rrc_taps(SPS * D, 0.35, 4)) as ddc, SymbolSync(SPS, "qpsk") as s:
         K = s.symbols_per_segment(SEG)
-        d_s = nat._dev_alloc(0, 8 * K * n_seg)
-        assert ddc.process_device(eng, nat.IN_C64, d_x.value, N_SEC, d_y.value) == ny
+        d_s = DeviceBuffer(8 * K * n_seg)
+        assert ddc.process_device(eng, nat.IN_C64, d_x.ptr, N_SEC, d_y.ptr) == ny
         eng.synchronize()
-        us, lo, hi = median_us(s, lambda: s.process_device(None, d_y.value, SEG, SEG, n_seg, d_s.value, K), args.warm, args.reps)
-        r = s.process_device(None, d_y.value, SEG, SEG, n_seg, d_s.value, K)
+        us, lo, hi = median_us(s, lambda: s.process_device(None, d_y.ptr, SEG, SEG, n_seg, d_s.ptr, K), args.warm, args.reps)
+        r = s.process_device(None, d_y.ptr, SEG, SEG, n_seg, d_s.ptr, K)
     floor = (8.0 * n_seg * SEG + 8.0 * K * n_seg) / args.copy_bps * 1e6 if args.copy_bps else float("nan")
     for p in (d_x, d_y, d_s):
-        nat.lib.tdsa_dev_free(0, p)
+        p.close()
     return dict(text=[
         f"second: {N_SEC} samples through DownConverter(D = {D}, RRC) -> {ny} in HBM, {n_seg} segments of {SEG}, K = {K}: "
         f"{us:9.1f} us (min {lo:.1f}, max {hi:.1f}); memory floor {floor:8.1f} us (8 bytes read per sample, 8 K written per "

@@ -14,7 +14,6 @@
     python tools/zerospanbench.py [--out profiles/zerospanbench.txt] [--reps 10] [--pairs 12]
 """
 import argparse
-import ctypes as C
 import os
 import sys
 import time
@@ -23,8 +22,7 @@ import types
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import DataProcessor, ZeroSpan, _native as nat  # noqa: E402
-from topdogspectrumanalyser_amd._native import _dev_alloc  # noqa: E402
+from topdogspectrumanalyser_amd import DataProcessor, DeviceBuffer, ZeroSpan, _native as nat  # noqa: E402
 
 FS = 20e6
 N_IN = 20_000_000
@@ -74,11 +72,11 @@ def main():
 
     rng = np.random.default_rng(1)
     raw = pulse_train(rng, 2 * N_IN)                       # two seconds: fills the ring
-    d_i8, d_c64 = _dev_alloc(0, raw.nbytes // 2), _dev_alloc(0, 8 * N_IN)
+    d_i8, d_c64 = DeviceBuffer(raw.nbytes // 2), DeviceBuffer(8 * N_IN)
     try:
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_i8, raw.ctypes.data_as(C.c_void_p), raw.nbytes // 2))
+        d_i8.put(raw[:raw.size // 2])
         cplx = to_c64(raw[:2 * N_IN])
-        nat.check(nat.lib.tdsa_memcpy_h2d(0, d_c64, cplx.ctypes.data_as(C.c_void_p), cplx.nbytes))
+        d_c64.put(cplx)
         del cplx
         say(f"zero span at {FS / 1e6:.0f} Msps: ring of {int(2 * FS)} float32 in HBM; device events around {args.reps} "
             f"calls after {args.warm} warm-up calls; memory floors at {HBM_BPS / 1e12:.2f} TB/s")
@@ -88,7 +86,7 @@ def main():
         for det in ("real", "mag", "db"):
             with ZeroSpan(FS, detector=det) as zs:
                 for name, fmt, ptr, bps in (("i8", nat.IN_I8, d_i8, 2), ("c64", nat.IN_C64, d_c64, 8)):
-                    us = timed(zs, lambda: zs.push_device(None, fmt, ptr.value, N_IN), args.warm, args.reps)
+                    us = timed(zs, lambda: zs.push_device(None, fmt, ptr.ptr, N_IN), args.warm, args.reps)
                     nbytes = N_IN * (bps + 4)
                     floor = nbytes / HBM_BPS * 1e6
                     say(f"{name:>5s} {det:>8s} {us:9.1f} {floor:9.1f} {100 * floor / us:9.1f}% {nbytes / us / 1e3:8.0f}")
@@ -97,7 +95,7 @@ def main():
         say(f"{'window':>7s} {'output':>12s} {'device us':>10s} {'wall us':>9s} {'searched':>10s} {'shown':>9s} "
             f"{'MB read':>8s} {'floor us':>9s} {'to host B':>10s} {'triggered':>9s}")
         with ZeroSpan(FS) as zs:
-            zs.push_device(None, nat.IN_I8, d_i8.value, N_IN)
+            zs.push_device(None, nat.IN_I8, d_i8.ptr, N_IN)
             zs.push(raw[2 * N_IN:])
             for window in (0.01, 0.1, 1.0):
                 nd = int(window * FS)
@@ -157,7 +155,7 @@ def main():
         say(f"  ratio of the medians: {np.median(t_host) / np.median(t_dev):.1f} x")
     finally:
         for p in (d_i8, d_c64):
-            nat.lib.tdsa_dev_free(0, p)
+            p.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

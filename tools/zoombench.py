@@ -11,15 +11,13 @@ Floors, from the shapes: compute = n_in (4 T / D + 8) FLOPs at the 157.3 TFLOPS 
     python tools/zoombench.py [--out profiles/zoombench.txt] [--reps 10]
 """
 import argparse
-import ctypes as C
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from topdogspectrumanalyser_amd import SpectrumEngine, _native as nat  # noqa: E402
-from topdogspectrumanalyser_amd._native import _dev_alloc  # noqa: E402
+from topdogspectrumanalyser_amd import DeviceBuffer, SpectrumEngine, _native as nat  # noqa: E402
 from topdogspectrumanalyser_amd.zoom import DownConverter, ZoomSpectrum  # noqa: E402
 
 FS = 20e6
@@ -53,10 +51,8 @@ def main():
     rng = np.random.default_rng(1)
     raw = rng.integers(-128, 128, 2 * N_IN).astype(np.int8)
     cplx = (raw[0::2].astype(np.float32) / 128 + 1j * raw[1::2].astype(np.float32) / 128).astype(np.complex64)
-    d_i8, d_c64 = _dev_alloc(0, raw.nbytes), _dev_alloc(0, cplx.nbytes)
-    d_out = _dev_alloc(0, 8 * (N_IN // 2 + 8))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_i8, raw.ctypes.data_as(C.c_void_p), raw.nbytes))
-    nat.check(nat.lib.tdsa_memcpy_h2d(0, d_c64, cplx.ctypes.data_as(C.c_void_p), cplx.nbytes))
+    d_i8, d_c64 = DeviceBuffer.of(raw), DeviceBuffer.of(cplx)
+    d_out = DeviceBuffer(8 * (N_IN // 2 + 8))
     del cplx
     say(f"one C3 second: {N_IN} IQ samples in HBM, one call; device events around {args.reps} calls after "
         f"{args.warm} warm-up calls; offset 0.1 fs; default filter (T = 34 D)")
@@ -70,7 +66,7 @@ def main():
                 with DownConverter(D, FS, 0.1 * FS) as ddc:
                     T = ddc.taps.size
                     for name, fmt, ptr, bps in (("i8", nat.IN_I8, d_i8, 2), ("c64", nat.IN_C64, d_c64, 8)):
-                        us = timed(eng, lambda: ddc.process_device(eng, fmt, ptr.value, N_IN, d_out.value),
+                        us = timed(eng, lambda: ddc.process_device(eng, fmt, ptr.ptr, N_IN, d_out.ptr),
                                    args.warm, args.reps)
                         flop = N_IN * (4.0 * T / D + 8)
                         n_out = N_IN // D
@@ -81,17 +77,17 @@ def main():
         with ZoomSpectrum(FS, D, N, offset_hz=0.1 * FS, hop=hop) as z:
             z.engine.configure(hold_max=True)
             frames = z.frames_completed_by(N_IN) + 4
-            d_rows = _dev_alloc(0, 4 * frames * N)
+            d_rows = DeviceBuffer(4 * frames * N)
             try:
-                us = timed(z.engine, lambda: z.process_device(nat.IN_I8, d_i8.value, N_IN, d_rows.value),
+                us = timed(z.engine, lambda: z.process_device(nat.IN_I8, d_i8.ptr, N_IN, d_rows.ptr),
                            args.warm, args.reps)
             finally:
-                nat.lib.tdsa_dev_free(0, d_rows)
+                d_rows.close()
             say(f"ZoomSpectrum end to end, D = {D}, nfft = {N}, hop = {hop}, max hold, int8: {us:.1f} us per C3 second "
                 f"({frames - 4} frames, rbw {FS / D / N:.1f} Hz)")
     finally:
         for p in (d_i8, d_c64, d_out):
-            nat.lib.tdsa_dev_free(0, p)
+            p.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

@@ -4,6 +4,7 @@ Hand-written HIP (gfx950) kernels behind a ctypes C-ABI (include/tdsa_hip.h), ke
 reference's own SampleDataSource / DataProcessor Python API.  Importing the package requires
 libtdsa_hip.so (built by __graft_entry__.build()); there is no CPU fallback.
 """
+from .devmem import DeviceBuffer  # noqa: F401
 from .engine import HostPipe, SpectrumEngine, TraceState  # noqa: F401
 from .utils.signal_processing import TraceAverager  # noqa: F401
 from .datasources import (SOURCE_CLASSES, HackrfSamplesDataSource, MicrophoneSamplesDataSource,  # noqa: F401
@@ -20,7 +21,7 @@ from .zerospan import ZeroSpan, view_plan  # noqa: F401
 from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401
 
-__all__ = ["SpectrumEngine", "HostPipe", "TraceState", "TraceAverager", "SampleDataSource", "SweepDataSource",
+__all__ = ["DeviceBuffer", "SpectrumEngine", "HostPipe", "TraceState", "TraceAverager", "SampleDataSource", "SweepDataSource",
            "HackrfSamplesDataSource", "RtlSamplesDataSource", "MicrophoneSamplesDataSource",
            "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView",
            "DownConverter", "ZoomSpectrum", "design_decimator", "ZeroSpan", "view_plan", "IqSweepDataSource", "SweepAssembler", "plan_steps",

@@ -268,12 +268,6 @@ def check(rc: int) -> None:
         raise TdsaError(f"tdsa error {rc}: {lib.tdsa_last_error_string().decode()}")
 
 
-def _dev_alloc(device: int, nbytes: int) -> C.c_void_p:
-    p = C.c_void_p()
-    check(lib.tdsa_dev_alloc(device, max(int(nbytes), 8), C.byref(p)))
-    return p
-
-
 class _Handle:
     """Lifetime of an object that owns device resources: close() once, from __del__ and on leaving a `with` block.  The
     plain case is one library handle in self._h, which close() hands to the library function _destroy names; a class that
@@ -296,6 +290,20 @@ class _Handle:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def _close_all(obj, *names, wait=None) -> None:
+    """The close() of a handle made of handles: waits for the stream of the engine in attribute `wait`, if it is still
+    open, then closes the attributes `names` (a handle, or a list of them) that exist, in the order given.  Attributes
+    a constructor did not reach are skipped, and close() of a closed handle does nothing."""
+    eng = getattr(obj, wait, None) if wait else None
+    if eng is not None and eng._h:
+        eng.synchronize()
+    for name in names:
+        held = getattr(obj, name, None)
+        for h in held if isinstance(held, list) else [held]:
+            if h is not None:
+                h.close()
 
 
 class _Timer:

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as nat
-from ._native import _dev_alloc
+from .devmem import DeviceBuffer
 from .analytics import _iq_input
 from .engine import SpectrumEngine
 from .utils.constants import DSPConstants
@@ -180,23 +180,13 @@ class ChannelSpectra(nat._Handle):
         self.engine = SpectrumEngine(self.nfft, max_frames=self.channels * self.max_frames, device=self.device)
         self.engine.set_window(zoom_window(self.nfft) if window is None else window)
         self.engine.configure(db_mode="mag", log_floor=DSPConstants.LOG_FLOOR, dc_alpha=-1.0)
-        self._d_in = _dev_alloc(self.device, 8 * self._max_in)
-        self._d_y = _dev_alloc(self.device, 8 * self.channels * self.max_frames * self.nfft)
-        self._d_rows = _dev_alloc(self.device, 4 * self.channels * self.max_frames * self.nfft)
+        self._d_in = DeviceBuffer(8 * self._max_in, self.device)
+        self._d_y = DeviceBuffer(8 * self.channels * self.max_frames * self.nfft, self.device)
+        self._d_rows = DeviceBuffer(4 * self.channels * self.max_frames * self.nfft, self.device)
 
     # ------------------------------------------------------------------ lifetime
     def close(self) -> None:
-        eng = getattr(self, "engine", None)
-        if eng is not None and eng._h:
-            eng.synchronize()
-        for p in (getattr(self, "_d_in", None), getattr(self, "_d_y", None), getattr(self, "_d_rows", None)):
-            if p is not None and p.value:
-                nat.lib.tdsa_dev_free(self.device, p)
-                p.value = None
-        if getattr(self, "bank", None) is not None:
-            self.bank.close()
-        if eng is not None:
-            eng.close()
+        nat._close_all(self, "_d_in", "_d_y", "_d_rows", "bank", "engine", wait="engine")
 
     # ------------------------------------------------------------------ axis
     @property
@@ -254,10 +244,10 @@ class ChannelSpectra(nat._Handle):
         F = self.frames_of(n_in)
         if F == 0:
             return 0
-        n_out = self.bank.process_device(self.engine, fmt, ptr, n_in, self._d_y.value, F * self.nfft)
+        d_y = self._d_y.at(0, 8 * self.channels * F * self.nfft)
+        n_out = self.bank.process_device(self.engine, fmt, ptr, n_in, d_y, F * self.nfft)
         assert n_out == F * self.nfft
-        self.engine.process_device(nat.IN_C64, self._d_y.value, self.channels * F * self.nfft, self.nfft,
-                                   self.channels * F, rows_ptr)
+        self.engine.process_device(nat.IN_C64, d_y, self.channels * F * self.nfft, self.nfft, self.channels * F, rows_ptr)
         return F
 
     def process(self, iq) -> np.ndarray:
@@ -268,9 +258,11 @@ class ChannelSpectra(nat._Handle):
         if F == 0:
             return out
         bps = 8 if fmt == nat.IN_C64 else 2
-        nat.check(nat.lib.tdsa_plan_copy(self.engine._h, self._d_in, a.ctypes.data_as(C.c_void_p), bps * n, 0))
-        self._run(fmt, self._d_in.value, n, self._d_rows.value)
-        nat.check(nat.lib.tdsa_plan_copy(self.engine._h, out.ctypes.data_as(C.c_void_p), self._d_rows, out.nbytes, 1))
+        nat.check(nat.lib.tdsa_plan_copy(self.engine._h, self._d_in.at(0, bps * n), a.ctypes.data_as(C.c_void_p),
+                                         bps * n, 0))
+        self._run(fmt, self._d_in.ptr, n, self._d_rows.ptr)
+        nat.check(nat.lib.tdsa_plan_copy(self.engine._h, out.ctypes.data_as(C.c_void_p), self._d_rows.at(0, out.nbytes),
+                                         out.nbytes, 1))
         return out
 
     def process_device(self, fmt: int, ptr: int, n_in: int, out_db_dev: int) -> int:

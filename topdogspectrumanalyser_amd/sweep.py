@@ -21,9 +21,9 @@ import numpy as np
 
 from . import _native as nat
 from .datasources.base import SweepDataSource
+from .devmem import DeviceBuffer
 from .engine import SpectrumEngine
 from .utils.constants import DSPConstants
-from ._native import _dev_alloc
 from .zoom import zoom_window
 
 MAX_STEPS = 4096
@@ -227,16 +227,13 @@ class IqSweepDataSource(nat._Handle, SweepDataSource):
         else:
             self._stage = np.zeros((S, 2 * self.n_samples_per_step),
                                    dtype=np.int8 if self.in_format == nat.IN_I8 else np.uint8)
-        self._d_in = _dev_alloc(self.device, self._stage.nbytes)
+        self._d_in = DeviceBuffer(self._stage.nbytes, self.device)
 
     def _release(self) -> None:
         if self.assembler is not None:
             self.engine.synchronize()
-            self.assembler.close()
-            self.assembler = None
-        if self._d_in is not None and self._d_in.value:
-            nat.lib.tdsa_dev_free(self.device, self._d_in)
-            self._d_in = None
+        nat._close_all(self, "assembler", "_d_in")
+        self.assembler = self._d_in = None
 
     # ------------------------------------------------------------------ SweepDataSource
     def start(self, frequency=None):
@@ -279,8 +276,9 @@ class IqSweepDataSource(nat._Handle, SweepDataSource):
                 raise ValueError(f"capture returned {block.size} values for step {s}, {self._stage.shape[1]} expected")
             self._stage[s] = block
         eng, asm = self.engine, self.assembler
-        nat.check(nat.lib.tdsa_plan_copy(eng._h, self._d_in, self._stage.ctypes.data_as(C.c_void_p), self._stage.nbytes, 0))
-        asm.run_device(eng, self.in_format, self._d_in.value, self._stage.strides[0], 0, self.centres.size,
+        nat.check(nat.lib.tdsa_plan_copy(eng._h, self._d_in.at(0, self._stage.nbytes),
+                                         self._stage.ctypes.data_as(C.c_void_p), self._stage.nbytes, 0))
+        asm.run_device(eng, self.in_format, self._d_in.ptr, self._stage.strides[0], 0, self.centres.size,
                        self.n_samples_per_step, self.hop, self.frames_per_step, self.detector)
         trace = asm.read(self.mode)
         dt = time.monotonic() - t0

@@ -18,8 +18,8 @@ from typing import Optional
 import numpy as np
 
 from . import _native as nat
+from .devmem import DeviceBuffer
 from .engine import SpectrumEngine
-from ._native import _dev_alloc
 from .zoom import DownConverter
 
 BUFFER_SECONDS = 2.0            # the reference's _ZS_BUFFER_SECONDS
@@ -103,6 +103,7 @@ def _zs_input(samples):
 
 class ZeroSpan(nat._Handle, nat._Timer):
     """Detector ring of the last `buffer_s` seconds on the device, and views of it."""
+    _destroy = "tdsa_zspan_destroy"
     _timer = ("tdsa_zspan_timer_begin", "tdsa_zspan_timer_end")
 
     def __init__(self, sample_rate: float, window_s: float = 0.01, detector: str = "real",
@@ -134,26 +135,15 @@ class ZeroSpan(nat._Handle, nat._Timer):
             # the tuned channel: converter, scratch and ring share one stream (a small plan lends it)
             self.ddc = DownConverter(self.decimation, self.sample_rate, offset_hz, taps, self.device, self.max_host_samples)
             self._engine = SpectrumEngine(64, max_frames=1, device=self.device)
-            self._d_in = _dev_alloc(self.device, 8 * self.max_host_samples)
+            self._d_in = DeviceBuffer(8 * self.max_host_samples, self.device)
             self._y_cap = self.max_host_samples // self.decimation + 1
-            self._d_y = _dev_alloc(self.device, 8 * self._y_cap)
+            self._d_y = DeviceBuffer(8 * self._y_cap, self.device)
 
     # ------------------------------------------------------------------ lifetime
     def close(self) -> None:
-        eng = getattr(self, "_engine", None)
-        if eng is not None and eng._h:
-            eng.synchronize()
-        if getattr(self, "_h", None) is not None and self._h:
-            nat.lib.tdsa_zspan_destroy(self._h)
-            self._h = C.c_void_p()
-        for p in (getattr(self, "_d_in", None), getattr(self, "_d_y", None)):
-            if p is not None and p.value:
-                nat.lib.tdsa_dev_free(self.device, p)
-                p.value = None
-        if getattr(self, "ddc", None) is not None:
-            self.ddc.close()
-        if eng is not None:
-            eng.close()
+        nat._close_all(self, wait="_engine")
+        super().close()                       # the ring: after the wait, before the scratch it was fed from
+        nat._close_all(self, "_d_in", "_d_y", "ddc", "_engine")
 
     # ------------------------------------------------------------------ configuration
     @property
@@ -200,8 +190,9 @@ class ZeroSpan(nat._Handle, nat._Timer):
         for s in range(0, n, self.max_host_samples):
             k = min(self.max_host_samples, n - s)
             part = np.ascontiguousarray(a[s:s + k] if fmt == nat.IN_C64 else a[2 * s:2 * (s + k)])
-            nat.check(nat.lib.tdsa_plan_copy(self._engine._h, self._d_in, part.ctypes.data_as(C.c_void_p), bps * k, 0))
-            pushed += self._convert(self._engine, fmt, self._d_in.value, k)
+            nat.check(nat.lib.tdsa_plan_copy(self._engine._h, self._d_in.at(0, bps * k), part.ctypes.data_as(C.c_void_p),
+                                             bps * k, 0))
+            pushed += self._convert(self._engine, fmt, self._d_in.ptr, k)
         return pushed
 
     def _convert(self, engine, fmt: int, ptr: int, n: int) -> int:
@@ -209,9 +200,9 @@ class ZeroSpan(nat._Handle, nat._Timer):
         for s in range(0, n, self.max_host_samples):       # the scratch holds one block's outputs
             k = min(self.max_host_samples, n - s)
             bps = 8 if fmt == nat.IN_C64 else 2
-            n_out = self.ddc.process_device(engine, fmt, ptr + bps * s, k, self._d_y.value)
+            n_out = self.ddc.process_device(engine, fmt, ptr + bps * s, k, self._d_y.ptr)
             if n_out:
-                nat.check(nat.lib.tdsa_zspan_push_dev(self._h, engine._h, nat.IN_C64, self._d_y, n_out))
+                nat.check(nat.lib.tdsa_zspan_push_dev(self._h, engine._h, nat.IN_C64, self._d_y.at(0, 8 * n_out), n_out))
             done += n_out
         return done
 

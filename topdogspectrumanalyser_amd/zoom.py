@@ -19,8 +19,8 @@ from typing import Optional
 import numpy as np
 
 from . import _native as nat
-from ._native import _dev_alloc
 from .analytics import _iq_input
+from .devmem import DeviceBuffer
 from .engine import SpectrumEngine
 from .utils.constants import DSPConstants
 
@@ -191,25 +191,15 @@ class ZoomSpectrum(nat._Handle):
         self.engine.set_window(zoom_window(self.nfft) if window is None else window)
         self.engine.configure(db_mode="mag", log_floor=DSPConstants.LOG_FLOOR, dc_alpha=-1.0)
         self._y_cap = 0
-        self._y = [C.c_void_p(), C.c_void_p()]
+        self._y = []
         self._restart()
         self._grow(self.nfft + max_out)
-        self._d_in = _dev_alloc(self.device, 8 * self.max_host_samples)
-        self._d_rows = _dev_alloc(self.device, 4 * self._rows_cap * self.nfft)
+        self._d_in = DeviceBuffer(8 * self.max_host_samples, self.device)
+        self._d_rows = DeviceBuffer(4 * self._rows_cap * self.nfft, self.device)
 
     # ------------------------------------------------------------------ lifetime
     def close(self) -> None:
-        eng = getattr(self, "engine", None)
-        if eng is not None and eng._h:
-            eng.synchronize()
-        for p in list(getattr(self, "_y", [])) + [getattr(self, "_d_in", None), getattr(self, "_d_rows", None)]:
-            if p is not None and p.value:
-                nat.lib.tdsa_dev_free(self.device, p)
-                p.value = None
-        if getattr(self, "ddc", None) is not None:
-            self.ddc.close()
-        if eng is not None:
-            eng.close()
+        nat._close_all(self, "_y", "_d_in", "_d_rows", "ddc", "engine", wait="engine")
 
     # ------------------------------------------------------------------ axis
     @property
@@ -272,14 +262,14 @@ class ZoomSpectrum(nat._Handle):
         if need <= self._y_cap:
             return
         cap = max(need, 2 * self._y_cap)
-        new = [_dev_alloc(self.device, 8 * cap), _dev_alloc(self.device, 8 * cap)]
+        new = [DeviceBuffer(8 * cap, self.device), DeviceBuffer(8 * cap, self.device)]
         if self._y_cap:
             if self._pending:
-                nat.check(nat.lib.tdsa_plan_copy(self.engine._h, new[self._cur], self._y[self._cur],
-                                                 8 * self._pending, 0))
+                nat.check(nat.lib.tdsa_plan_copy(self.engine._h, new[self._cur].ptr,
+                                                 self._y[self._cur].at(0, 8 * self._pending), 8 * self._pending, 0))
             self.engine.synchronize()
-            for p in self._y:
-                nat.lib.tdsa_dev_free(self.device, p)
+            for old in self._y:
+                old.close()
         self._y, self._y_cap = new, cap
 
     def _run(self, fmt: int, ptr: int, n_in: int, rows_ptr: int) -> int:
@@ -289,7 +279,7 @@ class ZoomSpectrum(nat._Handle):
         n_new = outputs_completed(self._inputs, n_in, D)
         self._grow(self._pending + n_new)
         y = self._y[self._cur]
-        n_out = self.ddc.process_device(self.engine, fmt, ptr, n_in, y.value + 8 * self._pending)
+        n_out = self.ddc.process_device(self.engine, fmt, ptr, n_in, y.at(8 * self._pending, 8 * n_new))
         self._inputs = total
         end = self._base + self._pending + n_out
         nf = 0 if end - self._next < self.nfft else (end - self._next - self.nfft) // self.hop + 1
@@ -297,7 +287,8 @@ class ZoomSpectrum(nat._Handle):
         while done < nf:
             k = min(self.engine.max_frames, nf - done)
             start = self._next + done * self.hop
-            self.engine.process_device(nat.IN_C64, y.value + 8 * (start - self._base), (k - 1) * self.hop + self.nfft,
+            n_frame = (k - 1) * self.hop + self.nfft
+            self.engine.process_device(nat.IN_C64, y.at(8 * (start - self._base), 8 * n_frame), n_frame,
                                        self.hop, k, rows_ptr + 4 * done * self.nfft if rows_ptr else None)
             done += k
         self._next += nf * self.hop
@@ -305,8 +296,8 @@ class ZoomSpectrum(nat._Handle):
         keep = end - keep_from
         other = self._y[self._cur ^ 1]
         if keep:
-            nat.check(nat.lib.tdsa_plan_copy(self.engine._h, other, C.c_void_p(y.value + 8 * (keep_from - self._base)),
-                                             8 * keep, 0))
+            nat.check(nat.lib.tdsa_plan_copy(self.engine._h, other.at(0, 8 * keep),
+                                             y.at(8 * (keep_from - self._base), 8 * keep), 8 * keep, 0))
         self._cur ^= 1
         self._base, self._pending = keep_from, keep
         return nf
@@ -320,11 +311,12 @@ class ZoomSpectrum(nat._Handle):
         for s in range(0, n, self.max_host_samples):
             k = min(self.max_host_samples, n - s)
             part = np.ascontiguousarray(a[s:s + k] if fmt == nat.IN_C64 else a[2 * s:2 * (s + k)])
-            nat.check(nat.lib.tdsa_plan_copy(self.engine._h, self._d_in, part.ctypes.data_as(C.c_void_p), bps * k, 0))
-            nf = self._run(fmt, self._d_in.value, k, self._d_rows.value)
+            nat.check(nat.lib.tdsa_plan_copy(self.engine._h, self._d_in.at(0, bps * k), part.ctypes.data_as(C.c_void_p),
+                                             bps * k, 0))
+            nf = self._run(fmt, self._d_in.ptr, k, self._d_rows.ptr)
             out = np.empty((nf, self.nfft), dtype=np.float32)
-            nat.check(nat.lib.tdsa_plan_copy(self.engine._h, out.ctypes.data_as(C.c_void_p), self._d_rows,
-                                             out.nbytes, 1))
+            nat.check(nat.lib.tdsa_plan_copy(self.engine._h, out.ctypes.data_as(C.c_void_p),
+                                             self._d_rows.at(0, out.nbytes), out.nbytes, 1))
             rows.append(out)
         if not rows:
             return np.empty((0, self.nfft), dtype=np.float32)
