@@ -578,6 +578,65 @@ int tdsa_detect_reset(tdsa_detect h);
 int tdsa_detect_timer_begin(tdsa_detect h);
 int tdsa_detect_timer_end(tdsa_detect h, float* elapsed_ms);
 
+/* -------- channel measurements: power, ACPR, occupied bandwidth, x-dB width, limit mask ----
+ * Rows are [n_rows][n_bins] float32 dB rows, 1 <= n_bins <= 16384, the input of tdsa_detect_*.  Throughout, p_i =
+ * 10^(row[i] / 10) in float32 (tdsa_rows_stats' expression) widened to float64; a NaN bin contributes 0.  Per row:
+ *   channels   C inclusive bin ranges lo_c <= hi_c (1 <= C <= 16, they may overlap; channel 0 is the main channel).  Per
+ *              channel: power = sum p_i over the range in float64, by the tree of tdsa_detect_signal.power - a channel
+ *              set to a detector record's [start, stop] has that record's power bits; peak_bin = the first bin holding
+ *              the range's largest non-NaN value and peak_db that value (-1 and NaN if there is none); n_nan.
+ *   obw        over [obw_lo, obw_hi]: S[k] = the inclusive prefix sum of p, T = its last value (obw_total), t_lo =
+ *              T (1 - f) / 2, t_hi = T (1 + f) / 2; k_lo / k_hi = the first k with S[k] >= t_lo / t_hi; with a bin
+ *              spanning [k - 1/2, k + 1/2], x = k - 1/2 + (t - S[k - 1]) / p_k, S[obw_lo - 1] = 0.  T not > 0 sets
+ *              TDSA_MEAS_EMPTY, T = +inf TDSA_MEAS_INF: then k = -1 and x = NaN.  The order of the sums behind S depends
+ *              on the bins and the configuration alone.  n_nan counts the range's NaNs.
+ *   x-dB       peak_db / peak_bin of the same range as above; xdb_lo / xdb_hi = the first / last bin of the range with
+ *              row[i] >= peak_db - xdb (float32); -1 where there is no peak.
+ *   limit      with a limit line (tdsa_meas_set_limit; float32 [n_bins], a NaN entry = bin not tested): lim_i =
+ *              limit[i] (absolute) or limit[i] + ref in float32 (relative; ref = channel 0's peak_db, a NaN ref tests
+ *              nothing).  A bin fails when row[i] > lim_i (a NaN never does): n_fail, first_fail, last_fail.  margin_i
+ *              = row[i] - lim_i in float32, NaN margins skipped: worst_margin = the largest, worst_bin = its first
+ *              bin.  Nothing tested: the bins are -1, worst_margin NaN.  n_fail > 0 sets TDSA_MEAS_MASK_FAIL.
+ * A row's records are the same bits whatever n_rows is, wherever the row sits, and whichever entry point or load path
+ * ran it.  _configure fixes the parameters (a live handle may be configured again): 1 <= n_channels <= 16, every range
+ * inside the row, 0 < fraction < 1, xdb finite and >= 0.  _set_limit uploads n = n_bins values (NULL removes the line)
+ * and returns when limit_host may be released.  _process: host rows through pinned staging, n_rows <= max_host_rows.
+ * _process_dev: rows in device memory (aligned to 4 bytes; 16-byte loads where n_bins % 4 == 0 and rows_dev is 16-byte
+ * aligned, float loads otherwise, with the same results), on plan p's stream (ordered after its work, and its later
+ * work after this) or on the handle's own for p = NULL.  Both write n_rows row records and n_rows * n_channels channel
+ * records and return when they are in host memory; n_rows = 0 returns TDSA_OK and writes nothing.  The handle counts
+ * the rows of all calls and those with TDSA_MEAS_MASK_FAIL since the last _reset (or create): _read_totals, either
+ * destination may be NULL, not both.  Argument errors are reported before any HIP call. */
+#define TDSA_MEAS_EMPTY 1
+#define TDSA_MEAS_INF 2
+#define TDSA_MEAS_MASK_FAIL 4
+#define TDSA_MEAS_MAX_CHANNELS 16
+typedef struct tdsa_meas_row {
+  double obw_total, x_lo, x_hi;                 /* linear power; positions in bins */
+  int32_t k_lo, k_hi, xdb_lo, xdb_hi, peak_bin, n_nan, n_fail, worst_bin, first_fail, last_fail, flags;
+  float peak_db, worst_margin;
+  int32_t reserved;
+} tdsa_meas_row;
+typedef struct tdsa_meas_channel {
+  double power;                                 /* linear */
+  float peak_db;
+  int32_t peak_bin, n_nan, reserved;
+} tdsa_meas_channel;
+typedef struct tdsa_meas_s* tdsa_meas;
+int tdsa_meas_create(int device_id, int n_bins, size_t max_host_rows, tdsa_meas* out);
+int tdsa_meas_destroy(tdsa_meas h);
+int tdsa_meas_configure(tdsa_meas h, int n_channels, const int* lo, const int* hi, int obw_lo, int obw_hi,
+                        double fraction, float xdb);
+int tdsa_meas_set_limit(tdsa_meas h, const float* limit_host, int n, int relative);
+int tdsa_meas_process(tdsa_meas h, const float* rows_host, size_t n_rows, tdsa_meas_row* row_records_host,
+                      tdsa_meas_channel* channel_records_host);
+int tdsa_meas_process_dev(tdsa_meas h, tdsa_plan p, const float* rows_dev, size_t n_rows,
+                          tdsa_meas_row* row_records_host, tdsa_meas_channel* channel_records_host);
+int tdsa_meas_read_totals(tdsa_meas h, uint64_t* rows_seen, uint64_t* rows_failed);
+int tdsa_meas_reset(tdsa_meas h);
+int tdsa_meas_timer_begin(tdsa_meas h);
+int tdsa_meas_timer_end(tdsa_meas h, float* elapsed_ms);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

@@ -17,6 +17,7 @@ from .channelizer import Channelizer, ChannelSpectra  # noqa: F401
 from .demod import Demodulator, deemphasis_pole, design_audio_filter  # noqa: F401
 from .symbols import SymbolSync, rrc_taps  # noqa: F401
 from .detect import Detections, SignalDetector  # noqa: F401
+from .measure import ChannelMeasure, Measurements, channel_plan, channels_from_emission, limit_line  # noqa: F401
 from .zerospan import ZeroSpan, view_plan  # noqa: F401
 from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401
@@ -26,4 +27,5 @@ __all__ = ["DeviceBuffer", "SpectrumEngine", "HostPipe", "TraceState", "TraceAve
            "SOURCE_CLASSES", "DataProcessor", "TareState", "Constellation", "ConstellationView",
            "DownConverter", "ZoomSpectrum", "design_decimator", "ZeroSpan", "view_plan", "IqSweepDataSource", "SweepAssembler", "plan_steps",
            "TraceHistory", "RibbonView", "ThreeDView", "SurfaceView", "Channelizer", "ChannelSpectra",
-           "Demodulator", "design_audio_filter", "deemphasis_pole", "SignalDetector", "Detections"]
+           "Demodulator", "design_audio_filter", "deemphasis_pole", "SignalDetector", "Detections", "ChannelMeasure", "Measurements",
+           "channel_plan", "limit_line", "channels_from_emission"]

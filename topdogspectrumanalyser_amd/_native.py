@@ -26,6 +26,7 @@ DEMOD_POLE_OFF, DEMOD_POLE_LOWPASS, DEMOD_POLE_HIGHPASS = 0, 1, 2
 SYMSYNC_AUTO, SYMSYNC_FIXED = 0, 1
 SYMSYNC_NONFINITE, SYMSYNC_NO_CARRIER = 1, 2
 DETECT_NAN_FLOOR = 1
+MEAS_EMPTY, MEAS_INF, MEAS_MASK_FAIL = 1, 2, 4
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
 ZS_FREE_RUN, ZS_RISE, ZS_FALL = 0, 1, 2
 ZS_COL_MINMAX, ZS_COL_SAMPLE, ZS_COL_MEAN = 0, 1, 2
@@ -168,6 +169,16 @@ _SIGNATURES = {
     "tdsa_detect_reset": (C.c_int, [_P]),
     "tdsa_detect_timer_begin": (C.c_int, [_P]),
     "tdsa_detect_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_meas_create": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_meas_destroy": (C.c_int, [_P]),
+    "tdsa_meas_configure": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_double, C.c_float]),
+    "tdsa_meas_set_limit": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "tdsa_meas_process": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "tdsa_meas_process_dev": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
+    "tdsa_meas_read_totals": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "tdsa_meas_reset": (C.c_int, [_P]),
+    "tdsa_meas_timer_begin": (C.c_int, [_P]),
+    "tdsa_meas_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),

@@ -1,6 +1,6 @@
 // tdsa_wave.hpp - the lane-level idioms of the kernels, once (device only): the xor butterfly across a wave64 or a
-// segment of it, the DPP controls and the reduction ladders built from them, and float max / min through integer
-// atomics.  What a kernel's bit-for-bit tests pin about a reduction - the order in which the operands are combined,
+// segment of it, the scan from lane 0 up, the DPP controls and the reduction ladders built from them, and float max /
+// min through integer atomics.  What a kernel's bit-for-bit tests pin about a reduction - the order in which the operands are combined,
 // the lanes that hold the result, whether a NaN is dropped - is stated here and nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,6 +48,26 @@ __device__ __forceinline__ PeakPair wave_best(PeakPair p, Better better) {
 // A kernel that folds several values side by side in ONE butterfly (min, max and a NaN flag; the I and the Q of a
 // frame) keeps its own loop: taken apart into calls of the above, one value's steps come behind the other's and the
 // kernel's instruction stream changes.  tests/test_isa_frozen.py lists those loops.
+
+// ---- scan --------------------------------------------------------------------------------------------------------
+// Inclusive scan from lane 0 up: lane l ends with the op over lanes 0 .. l.  Steps at distance 1, 2 .. 32, own value
+// first: the order a float scan rounds by.  wave_lane_below hands every lane the value of the lane below it (lane 0:
+// `first`), which turns the inclusive scan into the exclusive one.
+template <class T, class Op>
+__device__ __forceinline__ T wave_scan_inclusive(T v, Op op) {
+  const int lane = __lane_id();
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = __shfl_up(v, d);
+    if (lane >= d) v = op(v, o);
+  }
+  return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_lane_below(T v, T first) {
+  const T o = __shfl_up(v, 1);
+  return __lane_id() == 0 ? first : o;
+}
 
 // ---- DPP ---------------------------------------------------------------------------------------------------------
 // One type per control: the dpp_ctrl operand and the row mask it is used with.  A row is 16 lanes; the two
