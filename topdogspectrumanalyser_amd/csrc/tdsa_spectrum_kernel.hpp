@@ -253,6 +253,10 @@ template <int LOG2N, bool IN_C64, int HOLDX, int CHIRP = 0>   // HOLD: bit0 = ma
 __global__ void __launch_bounds__(Cfg<LOG2N>::WGT, 4) spectrum_kernel(const SpecParams p) {
   constexpr int HOLD = HOLDX & 7;
   constexpr bool STATS = (HOLDX & 8) != 0;
+  // SLIDE (HOLDX bit 4; 16384 points, bytes, dB rows, hop = N/2: tdsa_spectrum_c3_inst.hip): the upper half of a frame's raw
+  // rows IS the lower half of the next frame's - kept in registers, XOR-ed, with its DC partial sums, instead of being
+  // loaded, XOR-ed and summed again.  Integer sums: the rows are bit for bit those of the plain instantiation.
+  constexpr bool SLIDE = (HOLDX & 16) != 0;
   using C = Cfg<LOG2N>;
   constexpr int N = C::N, SG = C::SG, A = C::A, M = C::M, H = C::H, FPW = C::FPW, NPAD = C::NPAD;
   constexpr int LH = ilog2(H);
@@ -487,6 +491,14 @@ __global__ void __launch_bounds__(Cfg<LOG2N>::WGT, 4) spectrum_kernel(const Spec
     }
   };
   if (u0 < u1) load_frame_raw(frame_of(u0));
+  // SLIDE: raw[0 .. NRAW/2) hold the previous frame's upper rows (XOR-ed), slide_sum their per-thread I / Q sums -
+  // unless the frame at hand has no contiguous predecessor in this workgroup (slide_full, wave-uniform): the first of
+  // the workgroup's range, the first of a capture in a batch
+  bool slide_full = true;
+  unsigned slide_sum = 0;
+  typedef unsigned short slide_u16x2 __attribute__((ext_vector_type(2)));
+  static_assert(!SLIDE || (LOG2N == 14 && !IN_C64 && HOLD < 2 && !STATS && CHIRP == 0 && FPW == 1 && !INL && M == 2 && NRAW == 8),
+                "sliding front end: the 16384-point byte-format dB-row instantiations, hold off / max hold");
   // order of the cold fetches: the first frame's bytes (the DC sums need them first), the twiddles (the
   // middle-pass table goes through registers into LDS, which waits for everything issued before it), the
   // window slice last (64 KiB per workgroup, not needed before the first barrier has been passed)
@@ -575,7 +587,7 @@ __global__ void __launch_bounds__(Cfg<LOG2N>::WGT, 4) spectrum_kernel(const Spec
         }
       });
       }
-    } else {
+    } else if constexpr (!SLIDE) {   // (SLIDE: only the rows that are new, with the DC sums)
       static_for<0, NRAW>([&](auto ic) { raw[decltype(ic)::value] ^= xm_v; });   // int8 -> offset binary
     }
     // One transform (DC, window, three radix passes: v[] in sample order -> v[] in bin order) - or, CHIRP == 3, the whole
@@ -1142,6 +1154,17 @@ inline hipError_t launch_one(const SpecParams& p, const LaunchGeom& g, hipStream
   return hipGetLastError();
 }
 
+// The 16384-point frames of a byte-format capture at hop N/2 (dB rows, frame-mean DC, hold off / max hold, nothing else
+// riding the epilogue) have instantiations of their own with the sliding front end (SLIDE), in a translation unit of their
+// own (tdsa_spectrum_c3_inst.hip).  A property of the launch's parameters alone: single and batched launches of one plan
+// pick alike, and their rows stay bit-identical.
+inline bool c3_slide_applies(int in_c64, const SpecParams& p) {
+  return !in_c64 && p.dc_mode == DC_FRAME_MEAN && p.out_db != nullptr && p.out_lin == nullptr &&
+         p.out_cplx == nullptr && (p.hold_flags & 2) == 0 && p.stats_part == nullptr && p.tare == nullptr &&
+         p.pre_raw == nullptr && p.post_n == 0 && p.rows_twice == 0 && p.frame_stride == (long long)Cfg<14>::N;
+}
+hipError_t launch_c3_slide(const SpecParams& p, const LaunchGeom& g, hipStream_t s);
+
 template <int LOG2N>
 hipError_t launch_n(int in_c64, const SpecParams& p, const LaunchGeom& g, hipStream_t s) {
   const int hold = p.out_lin == nullptr ? (p.hold_flags & 3) : 0;
@@ -1166,6 +1189,9 @@ hipError_t launch_n(int in_c64, const SpecParams& p, const LaunchGeom& g, hipStr
     } else {
       return hipErrorInvalidValue;
     }
+  }
+  if constexpr (LOG2N == 14) {
+    if (c3_slide_applies(in_c64, p)) return launch_c3_slide(p, g, s);
   }
   if (in_c64) {
     switch (hold) {

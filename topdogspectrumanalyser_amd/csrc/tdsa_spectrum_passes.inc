@@ -6,8 +6,36 @@
     if constexpr (!IN_C64 && SG >= 32) {
       // byte formats, whole waves per frame: exact integer sums, DPP wave reduce, one int2 per wave
       int* redi = reinterpret_cast<int*>(red);
+      unsigned slide_ti = 0, slide_tq = 0;                   // SLIDE: this thread's share of the frame's I / Q sums
+      if constexpr (SLIDE) {
+        // the lower rows and their sums (I | Q << 16: at most 8 x 255 each) are the previous frame's upper ones, unless
+        // this frame came in whole
+        if (slide_full) {
+          unsigned li = 0, lq = 0;
+          static_for<0, NRAW / 2>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            raw[i] ^= xm_v;
+            li = __builtin_amdgcn_udot4(raw[i], 0x00010001u, li, false);
+            lq = __builtin_amdgcn_udot4(raw[i], 0x01000100u, lq, false);
+          });
+          slide_sum = li | (lq << 16);
+        }
+        static_for<NRAW / 2, NRAW>([&](auto ic) {
+          constexpr int i = decltype(ic)::value;
+          raw[i] ^= xm_v;
+          slide_ti = __builtin_amdgcn_udot4(raw[i], 0x00010001u, slide_ti, false);
+          slide_tq = __builtin_amdgcn_udot4(raw[i], 0x01000100u, slide_tq, false);
+        });
+        const unsigned up = slide_ti | (slide_tq << 16);    // the upper rows' sums: the next frame's lower ones
+        slide_ti = __builtin_amdgcn_udot2(__builtin_bit_cast(slide_u16x2, slide_sum), __builtin_bit_cast(slide_u16x2, 0x00000001u), slide_ti, false);
+        slide_tq = __builtin_amdgcn_udot2(__builtin_bit_cast(slide_u16x2, slide_sum), __builtin_bit_cast(slide_u16x2, 0x00010000u), slide_tq, false);
+        slide_sum = up;
+      }
       if (p.dc_mode == DC_FRAME_MEAN) {
         unsigned si = 0, sq = 0;
+        if constexpr (SLIDE) {
+          si = slide_ti; sq = slide_tq;
+        } else
         static_for<0, NRAW>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
           si = __builtin_amdgcn_udot4(raw[i], 0x00010001u, si, false);
@@ -196,6 +224,23 @@
     }
     TDSA_STAMP(3);
     // raw registers are free again: start the next frame's HBM read now, it lands during the FFT
+    if constexpr (SLIDE) {
+      if (unit + 1 < u1) {
+        const int nf = frame_of(unit + 1);
+        // frame 0 of a capture of a batch does not continue the one before it
+        slide_full = p.seg_magic != 0u && unsigned(nf) - __umulhi(unsigned(nf), p.seg_magic) * p.seg_frames == 0u;
+        if (slide_full) {
+          load_frame_raw(nf);
+        } else {
+          const rsrc_t r = make_rsrc(static_cast<const unsigned char*>(p.in) + in_byte_off(nf), N * 2u);
+          static_for<0, NRAW / 2>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            raw[i] = raw[i + NRAW / 2];
+            raw[i + NRAW / 2] = __builtin_amdgcn_raw_buffer_load_b32(r, lane_in_off, RSTEP * (i + NRAW / 2) * ROWB, 0);
+          });
+        }
+      }
+    } else
     if (unit + 1 < u1) load_frame_raw(frame_of(unit + 1));
     TDSA_PRIO(2);
 
