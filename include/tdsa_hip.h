@@ -637,6 +637,59 @@ int tdsa_meas_reset(tdsa_meas h);
 int tdsa_meas_timer_begin(tdsa_meas h);
 int tdsa_meas_timer_end(tdsa_meas h, float* elapsed_ms);
 
+/* -------- power statistics of IQ streams: CCDF, PAPR, APD ---------------------------------
+ * The statistics of the INSTANTANEOUS power of the samples, which no averaged or held trace carries.  A handle has C
+ * streams, 1 <= C <= 256; stream c's samples of a call lie at in + c * in_stride, counted in samples of the call's
+ * format (TDSA_IN_I8 / _U8 / _C64, unpacked as the down-converter does: I8 (I + jQ) / 128, U8 by the float32 of
+ * float64(u) / 127.5 - 1).  Per sample p = fl(fl(re re) + fl(im im)) in float32: two products and one sum, each rounded
+ * once, no fused multiply-add, denormals kept.  u = the 32 bits of p, E = u >> 23, F = u & 0x7fffff.
+ * _configure(exp_lo, gate): -126 <= exp_lo <= 64 (default -40), gate a finite float32 >= 0 (0 = off, default).
+ * Per stream, accumulated over all calls since the last _reset / _configure / _create, integers only.  A sample falls in
+ * exactly one class, tested in this order:
+ *   1  p is NaN                         n_nan
+ *   2  p < gate (float32 compare)       n_gated   (a zero sample is gated whenever gate > 0)
+ *   3  p = +inf                         n_inf     (also finite samples whose square overflows)
+ *   4  p = 0                            n_zero
+ *   5  b = (u >> 18) - ((exp_lo + 127) << 5):  b < 0 n_under, b >= 2048 n_over, else hist[b] += 1
+ * hist: 2048 uint64 bins, 64 octaves of 32; bin b covers [edge_b, edge_(b+1)), edge_b = 2^(exp_lo + b / 32) * (1 +
+ * (b % 32) / 32), every edge an exact float32, widths 0.068 .. 0.134 dB.  n_total = the samples seen = the sum of the six
+ * counts and of hist.  msum: 256 uint64 words; every sample of class 5, inside the window or not, adds its mantissa (F |
+ * 2^23 for E >= 1, F for E = 0) to msum[E], so the total power of the finite samples is exactly (msum[0] + sum over E >=
+ * 1 of msum[E] 2^(E - 1)) 2^-149; a word holds 2^40 samples of one octave.  max_bits: the largest u among the samples of
+ * classes 4 and 5 (finite, not gated), 0 if none; min_bits: the smallest u of class 5, 0xffffffff if none.  Integer adds,
+ * max and min commute: the state is the same bits for any split of the input into calls, either entry point, any load
+ * path.
+ * _process: host samples through pinned staging, C * n_in <= max_host_samples; returns when they are consumed.
+ * _process_dev: samples in device memory (aligned to one sample; a stream whose first sample lies on 16 bytes is read
+ * with 16-byte loads, any other by elements), on plan p's stream (ordered after its work, and its later work after this)
+ * or on the handle's own for p = NULL; it does NOT wait - the state stays on the device.  in_stride >= n_in when C > 1
+ * (ignored for C = 1); n_in = 0 returns TDSA_OK and does nothing.  _read goes behind the last launch, waits, and copies
+ * n_streams records from first_stream on, and where the pointers are not NULL their msum ([n_streams][256]) and hist
+ * ([n_streams][2048]).  _reset zeroes the state and returns when earlier calls have finished; _configure does the same
+ * and sets the parameters.  Argument errors are reported before any HIP call. */
+#define TDSA_PSTAT_MAX_STREAMS 256
+#define TDSA_PSTAT_BINS 2048
+#define TDSA_PSTAT_BINS_PER_OCTAVE 32
+#define TDSA_PSTAT_EXPONENTS 256
+#define TDSA_PSTAT_EXP_LO_MIN (-126)
+#define TDSA_PSTAT_EXP_LO_MAX 64
+typedef struct tdsa_pstat_record {
+  uint64_t n_total, n_nan, n_gated, n_inf, n_zero, n_under, n_over;
+  uint32_t max_bits, min_bits;                  /* float32 bits */
+  uint32_t reserved[2];
+} tdsa_pstat_record;                            /* 72 bytes */
+typedef struct tdsa_pstat_s* tdsa_pstat;
+int tdsa_pstat_create(int device_id, int streams, size_t max_host_samples, tdsa_pstat* out);
+int tdsa_pstat_destroy(tdsa_pstat h);
+int tdsa_pstat_configure(tdsa_pstat h, int exp_lo, float gate);
+int tdsa_pstat_reset(tdsa_pstat h);
+int tdsa_pstat_process(tdsa_pstat h, int in_format, const void* in_host, size_t n_in, size_t in_stride);
+int tdsa_pstat_process_dev(tdsa_pstat h, tdsa_plan p, int in_format, const void* in_dev, size_t n_in, size_t in_stride);
+int tdsa_pstat_read(tdsa_pstat h, int first_stream, int n_streams, tdsa_pstat_record* records_host, uint64_t* msum_host,
+                    uint64_t* hist_host);
+int tdsa_pstat_timer_begin(tdsa_pstat h);
+int tdsa_pstat_timer_end(tdsa_pstat h, float* elapsed_ms);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

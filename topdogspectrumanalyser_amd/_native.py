@@ -67,6 +67,12 @@ class HistoryOut(C.Structure):
                 ("min_bins", C.c_void_p)]
 
 
+class PstatRecord(C.Structure):
+    _fields_ = [("n_total", C.c_uint64), ("n_nan", C.c_uint64), ("n_gated", C.c_uint64), ("n_inf", C.c_uint64),
+                ("n_zero", C.c_uint64), ("n_under", C.c_uint64), ("n_over", C.c_uint64), ("max_bits", C.c_uint32),
+                ("min_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 # every symbol include/tdsa_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -179,6 +185,15 @@ _SIGNATURES = {
     "tdsa_meas_reset": (C.c_int, [_P]),
     "tdsa_meas_timer_begin": (C.c_int, [_P]),
     "tdsa_meas_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_pstat_create": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_pstat_destroy": (C.c_int, [_P]),
+    "tdsa_pstat_configure": (C.c_int, [_P, C.c_int, C.c_float]),
+    "tdsa_pstat_reset": (C.c_int, [_P]),
+    "tdsa_pstat_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_size_t]),
+    "tdsa_pstat_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.c_size_t]),
+    "tdsa_pstat_read": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "tdsa_pstat_timer_begin": (C.c_int, [_P]),
+    "tdsa_pstat_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),
