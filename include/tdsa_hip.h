@@ -690,6 +690,78 @@ int tdsa_pstat_read(tdsa_pstat h, int first_stream, int n_streams, tdsa_pstat_re
 int tdsa_pstat_timer_begin(tdsa_pstat h);
 int tdsa_pstat_timer_end(tdsa_pstat h, float* elapsed_ms);
 
+/* -------- pulse analysis of IQ streams: one descriptor per pulse -----------------------------
+ * The time-domain measurement of pulsed signals: per pulse its time of arrival, width, peak, energy and the lag-one
+ * product that gives the carrier inside it; PRI / PRF, duty cycle and the rest follow on the host from the records.
+ * Streams and samples.  A handle has C streams, 1 <= C <= 256; stream c's samples of a call lie at in + c * in_stride,
+ *   counted in samples of the call's format (TDSA_IN_I8 / _U8 / _C64, unpacked as the power statistics do).  The
+ *   samples of a stream count from the last _reset / _configure / _create across calls: n = 0, 1, ... (int64).
+ * Power.  p = fl(fl(re re) + fl(im im)) in float32, no fused multiply-add, denormals kept: the power statistics' value
+ *   bit for bit.
+ * Class.  With float32 levels 0 < off_level <= on_level < inf:  A: p >= on_level.  B: p < off_level, or p is NaN.
+ *   C: anything else.  A NaN also counts in n_nan.
+ * State.  A stream is off after a reset.  A sets it on, B sets it off, C leaves it as it is: the state at n is the class
+ *   of the last sample <= n that is not C.  The state survives between calls.
+ * Pulse.  A maximal run of on samples: toa is its first index, width its length.  It is complete when a B sample
+ *   follows it; a pulse still on at the end of a call stays open in the handle and completes in a later call.
+ * Fields.  peak_bits: the largest float32 bits of p in the run (p >= off_level > 0 there, so bits order as values).
+ *   peak_index: the first n that attains it.  energy: the float64 sum of p, each converted to float64 first.  acc_re,
+ *   acc_im: the float64 sum over n = toa + 1 .. toa + width - 1 of x[n] conj(x[n-1]), per term re = fl64(re_n re_(n-1) +
+ *   im_n im_(n-1)), im = fl64(im_n re_(n-1) - re_n im_(n-1)) with the products formed in float64, where they are exact;
+ *   the pair (n-1, n) crosses tiles and calls like any other - the handle keeps each stream's last sample.  flags bit 0:
+ *   the run holds a sample with p = +inf; then energy is +inf and acc_* is unspecified.
+ * Filter and storage.  A complete pulse with width < min_width is dropped and counted in n_short.  Kept pulses get
+ *   ordinals 0, 1, ... per stream in time order; ordinal k < capacity is stored at slot k, later ones are counted in
+ *   n_lost; nothing is overwritten.
+ * Summary, per stream: n_total; n_on, the samples in the on state before the width filter (duty cycle = n_on /
+ *   n_total); n_pulses, the kept pulses, the lost ones included; n_short; n_lost; n_nan; open, open_toa, open_width of the
+ *   pulse not yet complete (0 when the stream is off).
+ * Split invariance.  toa, width, peak_index, peak_bits, flags, the summary and which pulses are stored are the same
+ *   bits for any split of a stream into calls, any grid and any load path.  energy, acc_re and acc_im are float64 sums
+ *   whose order of addition follows the split and the tiles (TDSA_PULSE_TILE samples, TDSA_PULSE_SAMPLES_PER_THREAD per
+ *   thread): they agree with any other order within the rounding of width additions - |d energy| <= width 2^-52
+ *   energy, |d acc| <= width 2^-50 energy - and no closer.
+ * _create: 1 <= capacity, streams * capacity <= 2^22 records.  _configure(on_level, off_level, min_width), 1 <= min_width
+ * < 2^31 (after _create: 1.0, 1.0, 1), zeroes the state and returns when earlier calls have finished, as _reset does.
+ * _process: host samples through pinned staging, C * n_in <= max_host_samples; returns when they are consumed.
+ * _process_dev: samples in device memory (aligned to one sample; a stream whose first sample lies on 16 bytes is read
+ * with 16-byte loads, any other by elements), on plan p's stream (ordered after its work, and its later work after this)
+ * or on the handle's own for p = NULL; it does NOT wait.  in_stride >= n_in when C > 1 (ignored for C = 1); n_in = 0
+ * returns TDSA_OK and does nothing; a call of any length is cut into launches.  _read and _read_pulses go behind the
+ * last launch and wait: _read copies n_streams summaries from first_stream on; _read_pulses copies the stored records
+ * first .. first + count - 1 of one stream, as many as there are (*n_out).  _debug_limits is for the tests and
+ * tools/pulsebench.py: fewer tiles (one workgroup each) per launch, so that small inputs take several, and a mask
+ * of the three kernels to launch (7 = all; anything else leaves the state meaningless until the next _reset).
+ * Argument errors are reported before any HIP call. */
+#define TDSA_PULSE_MAX_STREAMS 256
+#define TDSA_PULSE_MAX_RECORDS 4194304
+#define TDSA_PULSE_TILE 4096
+#define TDSA_PULSE_SAMPLES_PER_THREAD 16
+#define TDSA_PULSE_FLAG_INF 1u
+typedef struct tdsa_pulse_record {
+  int64_t toa, width, peak_index;
+  uint32_t peak_bits, flags;                    /* float32 bits; TDSA_PULSE_FLAG_* */
+  double energy, acc_re, acc_im;
+  uint64_t reserved;
+} tdsa_pulse_record;                            /* 64 bytes */
+typedef struct tdsa_pulse_summary {
+  uint64_t n_total, n_on, n_pulses, n_short, n_lost, n_nan;
+  int64_t open_toa, open_width;
+  int32_t open, reserved;
+} tdsa_pulse_summary;                           /* 72 bytes */
+typedef struct tdsa_pulse_s* tdsa_pulse;
+int tdsa_pulse_create(int device_id, int streams, int capacity, size_t max_host_samples, tdsa_pulse* out);
+int tdsa_pulse_destroy(tdsa_pulse h);
+int tdsa_pulse_configure(tdsa_pulse h, float on_level, float off_level, int64_t min_width);
+int tdsa_pulse_reset(tdsa_pulse h);
+int tdsa_pulse_process(tdsa_pulse h, int in_format, const void* in_host, size_t n_in, size_t in_stride);
+int tdsa_pulse_process_dev(tdsa_pulse h, tdsa_plan p, int in_format, const void* in_dev, size_t n_in, size_t in_stride);
+int tdsa_pulse_read(tdsa_pulse h, int first_stream, int n_streams, tdsa_pulse_summary* summaries_host);
+int tdsa_pulse_read_pulses(tdsa_pulse h, int stream, int first, int count, tdsa_pulse_record* records_host, int* n_out);
+int tdsa_pulse_debug_limits(tdsa_pulse h, int max_launch_tiles, int passes);
+int tdsa_pulse_timer_begin(tdsa_pulse h);
+int tdsa_pulse_timer_end(tdsa_pulse h, float* elapsed_ms);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

@@ -19,6 +19,7 @@ from .symbols import SymbolSync, rrc_taps  # noqa: F401
 from .detect import Detections, SignalDetector  # noqa: F401
 from .measure import ChannelMeasure, Measurements, channel_plan, channels_from_emission, limit_line  # noqa: F401
 from .powerstats import PowerStatistics, PowerStats, gaussian_ccdf  # noqa: F401
+from .pulses import PulseAnalyzer, PulseTrain, levels_from_db  # noqa: F401
 from .zerospan import ZeroSpan, view_plan  # noqa: F401
 from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401
@@ -29,4 +30,5 @@ __all__ = ["DeviceBuffer", "SpectrumEngine", "HostPipe", "TraceState", "TraceAve
            "DownConverter", "ZoomSpectrum", "design_decimator", "ZeroSpan", "view_plan", "IqSweepDataSource", "SweepAssembler", "plan_steps",
            "TraceHistory", "RibbonView", "ThreeDView", "SurfaceView", "Channelizer", "ChannelSpectra",
            "Demodulator", "design_audio_filter", "deemphasis_pole", "SignalDetector", "Detections", "ChannelMeasure", "Measurements",
-           "channel_plan", "limit_line", "channels_from_emission", "PowerStats", "PowerStatistics", "gaussian_ccdf"]
+           "channel_plan", "limit_line", "channels_from_emission", "PowerStats", "PowerStatistics", "gaussian_ccdf",
+           "PulseAnalyzer", "PulseTrain", "levels_from_db"]

@@ -73,6 +73,18 @@ class PstatRecord(C.Structure):
                 ("min_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class PulseRecord(C.Structure):
+    _fields_ = [("toa", C.c_int64), ("width", C.c_int64), ("peak_index", C.c_int64), ("peak_bits", C.c_uint32),
+                ("flags", C.c_uint32), ("energy", C.c_double), ("acc_re", C.c_double), ("acc_im", C.c_double),
+                ("reserved", C.c_uint64)]
+
+
+class PulseSummary(C.Structure):
+    _fields_ = [("n_total", C.c_uint64), ("n_on", C.c_uint64), ("n_pulses", C.c_uint64), ("n_short", C.c_uint64),
+                ("n_lost", C.c_uint64), ("n_nan", C.c_uint64), ("open_toa", C.c_int64), ("open_width", C.c_int64),
+                ("open", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/tdsa_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -194,6 +206,17 @@ _SIGNATURES = {
     "tdsa_pstat_read": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "tdsa_pstat_timer_begin": (C.c_int, [_P]),
     "tdsa_pstat_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_pulse_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_pulse_destroy": (C.c_int, [_P]),
+    "tdsa_pulse_configure": (C.c_int, [_P, C.c_float, C.c_float, C.c_int64]),
+    "tdsa_pulse_reset": (C.c_int, [_P]),
+    "tdsa_pulse_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_size_t]),
+    "tdsa_pulse_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.c_size_t]),
+    "tdsa_pulse_read": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "tdsa_pulse_read_pulses": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
+    "tdsa_pulse_debug_limits": (C.c_int, [_P, C.c_int, C.c_int]),
+    "tdsa_pulse_timer_begin": (C.c_int, [_P]),
+    "tdsa_pulse_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),
