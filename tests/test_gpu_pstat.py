@@ -191,6 +191,26 @@ def test_any_split_into_calls_through_either_entry_point_gives_the_same_bits():
         _same(p.read(), want, "six calls")
 
 
+@pytest.mark.parametrize("fmt", (pc.I8, pc.C64))
+def test_a_host_block_of_three_streams_above_the_staging_goes_in_pieces(fmt, monkeypatch):
+    """max_host_samples = 3 * 7 + 2: process() cuts 20 samples per stream into library calls of 7, 7 and 6, each an offset
+    into rows 20 samples apart.  The state is that of one device call over the same samples, and the contract's."""
+    calls, entry = [], nat.lib.tdsa_pstat_process
+    monkeypatch.setattr(nat.lib, "tdsa_pstat_process", lambda h, f, ptr, n, stride: calls.append((n, stride)) or entry(h, f, ptr, n, stride))
+    x = _noise(fmt, 3, 20, 77)
+    want = _want(x, fmt)
+    with PowerStats(3, max_host_samples=3 * 7 + 2) as p:
+        p.process(x)
+        host = p.read()
+        assert calls == [(7, 20), (7, 20), (6, 20)]
+        _same(host, want, "host")
+        p.reset()
+        dev = _feed_device(p, x, fmt)
+        _same(dev, want, "device")
+        for a, b in ((host.records, dev.records), (host.msum, dev.msum), (host.hist, dev.hist)):
+            assert np.array_equal(a, b)                        # integers all: no NaN to mind
+
+
 def test_read_of_sub_ranges_reset_reconfiguration_gate_and_window():
     x = _noise(pc.C64, 5, 1000, 3)
     x[:, ::50] = 0

@@ -250,6 +250,47 @@ def test_one_call_against_six_pieces_through_both_entry_points():
                 assert np.array_equal(six[f], one[c][f]), (c, f)
 
 
+def _seam_train(fmt, C_, n):
+    """[C][n] samples, stream c on where (k + 3 + c) % 8 < 5: with 7 samples a piece every stream has a pulse over the
+    seams at 7 and at 14.  int8 pairs, or complex64 in multiples of 1 / 8: every float64 sum of a pulse is exact in any
+    order, so the records have one right answer, bit for bit."""
+    k = np.arange(n)
+    on = (k[None, :] + 3 + np.arange(C_)[:, None]) % 8 < 5
+    if fmt == pc.C64:
+        return (np.where(on, 1.0 + 0.25 * (k % 4), 0.125 * (k % 2)) + 1j * np.where(on, 0.5 * (k % 3 - 1.0), 0.0)).astype(np.complex64)
+    iq = np.stack([np.where(on, 80 + 7 * k % 40, 3), np.where(on, -(85 + k % 30), -2)], axis=-1)
+    return iq.reshape(C_, 2 * n).astype(np.int8)
+
+
+@pytest.mark.parametrize("fmt", (pc.I8, pc.C64))
+def test_a_host_block_of_three_streams_above_the_staging_goes_in_pieces(fmt, monkeypatch):
+    """max_host_samples = 3 * 7 + 2: process() cuts 20 samples per stream into library calls of 7, 7 and 6, each an offset
+    into rows 20 samples apart; the open pulse, the last sample and the parity cross both seams in every stream.  The
+    state is that of one device call over the same samples, and the contract's."""
+    calls, entry = [], nat.lib.tdsa_pulse_process
+    monkeypatch.setattr(nat.lib, "tdsa_pulse_process", lambda h, f, ptr, n, stride: calls.append((n, stride)) or entry(h, f, ptr, n, stride))
+    x = _seam_train(fmt, 3, 20)
+    want = _want(x, fmt)
+    assert all(w.summary()["n_pulses"] >= 2 for w in want)
+
+    def state(p):
+        return p.read_summaries(), [p.read(c).records for c in range(3)]
+
+    with _analyzer(3, max_host_samples=3 * 7 + 2) as p:
+        p.process(x)
+        host = state(p)
+        assert calls == [(7, 20), (7, 20), (6, 20)]
+        p.reset()
+        _feed_device(p, x, fmt)
+        dev = state(p)
+    for tag, (sums, recs) in (("host", host), ("device", dev)):
+        for c, w in enumerate(want):
+            for f in pc.SUMMARY.names:
+                assert np.array_equal(sums[c][f], w.summary()[f]), (tag, c, f)
+            for f in pc.RECORD.names:
+                assert np.array_equal(recs[c][f], w.records()[f]), (tag, c, f)
+
+
 def test_overflow_min_width_across_a_tile_seam_and_non_finite_samples():
     rng = np.random.default_rng(3)
     code = _random_code(3 * T + 1, rng)

@@ -247,13 +247,6 @@ int tdsa_demod_reset_meas(tdsa_demod d) {
   return demod_clear_meas(d);
 }
 
-int tdsa_demod_timer_begin(tdsa_demod d) {
-  if (!d) return fail(TDSA_ERR_ARG, "null demodulator");
-  return d->timer_begin();
-}
+int tdsa_demod_timer_begin(tdsa_demod d) { return Lane::timer_begin(d, "demodulator"); }
 
-int tdsa_demod_timer_end(tdsa_demod d, float* elapsed_ms) {
-  if (!d) return fail(TDSA_ERR_ARG, "null demodulator");
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return d->timer_end(elapsed_ms);
-}
+int tdsa_demod_timer_end(tdsa_demod d, float* elapsed_ms) { return Lane::timer_end(d, "demodulator", elapsed_ms); }

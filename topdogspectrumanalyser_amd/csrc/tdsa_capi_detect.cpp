@@ -8,64 +8,38 @@ static_assert(sizeof(tdsa_detect_row) == sizeof(DetRow), "the public row record 
 static_assert(sizeof(tdsa_detect_signal) == sizeof(DetSignal), "the public signal record is the kernel's");
 
 // ---- signal detection (tdsa_detect.hip) --------------------------------------------------------------------------
-struct tdsa_detect_s : Lane {
-  int n_bins = 0;
-  size_t max_host = 0;             // rows one host call stages
-  void* h_in = nullptr;            // pinned staging of a host block ...
-  float* d_in = nullptr;
-  DetRow* d_row = nullptr;         // ... and the records of either entry point, grown on demand
-  DetSignal* d_sig = nullptr;
-  size_t row_cap = 0, sig_cap = 0;
+struct tdsa_detect_s : RowAnalyser {   // the second records: sub_per_row signals per row (max_signals)
   unsigned* d_occ = nullptr;       // [n_bins] rows in which the bin was above the threshold
-  uint64_t rows_seen = 0, rows_flagged = 0;
-  bool configured = false;
-  int lo = 0, hi = 0, rank = 0, min_width = 1, max_gap = 0, S = 1;
+  uint64_t rows_flagged = 0;
+  int lo = 0, hi = 0, rank = 0, min_width = 1, max_gap = 0;
   float margin = 0.0f, xdb = 0.0f;
+
+  hipError_t launch(hipStream_t s, const float* rows, size_t n_rows) {
+    DetLaunch a;
+    a.rows = rows;
+    a.n_rows = n_rows;
+    a.n = n_bins;
+    a.lo = lo;
+    a.hi = hi;
+    a.rank = rank;
+    a.margin = margin;
+    a.xdb = xdb;
+    a.min_width = min_width;
+    a.max_gap = max_gap;
+    a.S = int(sub_per_row);
+    a.row_rec = static_cast<DetRow*>(d_row);
+    a.sig_rec = static_cast<DetSignal*>(d_sub);
+    a.occ = d_occ;
+    return launch_detect(a, s);
+  }
+  void tally(const tdsa_detect_row* row_host, size_t n_rows) {
+    for (size_t r = 0; r < n_rows; ++r) rows_flagged += row_host[r].flags != 0;
+  }
 };
 
 namespace {
-
-// the checks both entry points share, before any HIP call
-int det_check(const tdsa_detect_s* h, const void* rows, const void* row_rec, const void* sig_rec) {
-  if (!h) return fail(TDSA_ERR_ARG, "null detector");
-  if (!h->configured) return fail(TDSA_ERR_ARG, "not configured: call tdsa_detect_configure first");
-  if (!rows) return fail(TDSA_ERR_ARG, "null rows");
-  if (!row_rec) return fail(TDSA_ERR_ARG, "null row records");
-  if (!sig_rec) return fail(TDSA_ERR_ARG, "null signal records");
-  return TDSA_OK;
+constexpr RowNames kNames = {"detector", "detect", "signal"};
 }
-
-// one call on stream s over device rows; returns when the records are in the caller's memory
-int det_run(tdsa_detect_s* h, hipStream_t s, const float* rows, size_t n_rows, tdsa_detect_row* row_host,
-            tdsa_detect_signal* sig_host) {
-  TRY(grow_device(&h->d_row, &h->row_cap, n_rows, h->last, sizeof(DetRow)));
-  TRY(grow_device(&h->d_sig, &h->sig_cap, n_rows * size_t(h->S), h->last, sizeof(DetSignal)));
-  DetLaunch a;
-  a.rows = rows;
-  a.n_rows = n_rows;
-  a.n = h->n_bins;
-  a.lo = h->lo;
-  a.hi = h->hi;
-  a.rank = h->rank;
-  a.margin = h->margin;
-  a.xdb = h->xdb;
-  a.min_width = h->min_width;
-  a.max_gap = h->max_gap;
-  a.S = h->S;
-  a.row_rec = h->d_row;
-  a.sig_rec = h->d_sig;
-  a.occ = h->d_occ;
-  HIPCHK(launch_detect(a, s));
-  HIPCHK(hipMemcpyAsync(row_host, h->d_row, n_rows * sizeof(DetRow), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(sig_host, h->d_sig, n_rows * size_t(h->S) * sizeof(DetSignal), hipMemcpyDeviceToHost, s));
-  TRY(h->done(s));
-  HIPCHK(hipStreamSynchronize(s));   // the records are the call's result: they are in the caller's memory on return
-  h->rows_seen += n_rows;
-  for (size_t r = 0; r < n_rows; ++r) h->rows_flagged += row_host[r].flags != 0;
-  return TDSA_OK;
-}
-
-}  // namespace
 
 int tdsa_detect_create(int device_id, int n_bins, size_t max_host_rows, tdsa_detect* out) {
   if (!out) return fail(TDSA_ERR_ARG, "null out");
@@ -84,10 +58,10 @@ int tdsa_detect_create(int device_id, int n_bins, size_t max_host_rows, tdsa_det
   h->device = device_id;
   h->n_bins = n_bins;
   h->max_host = max_host_rows;
-  const size_t in_bytes = max_host_rows * size_t(n_bins) * sizeof(float);
+  h->row_unit = sizeof(DetRow);
+  h->sub_unit = sizeof(DetSignal);
   hipError_t e = h->open(true);
-  if (e == hipSuccess) e = hipHostMalloc(&h->h_in, in_bytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_in), in_bytes);
+  if (e == hipSuccess) e = h->alloc();
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_occ), size_t(n_bins) * sizeof(unsigned));
   if (e == hipSuccess) e = hipMemsetAsync(h->d_occ, 0, size_t(n_bins) * sizeof(unsigned), h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -102,8 +76,8 @@ int tdsa_detect_create(int device_id, int n_bins, size_t max_host_rows, tdsa_det
 int tdsa_detect_destroy(tdsa_detect h) {
   if (!h) return TDSA_OK;
   h->drain();
-  free_all({h->d_in, h->d_row, h->d_sig, h->d_occ});
-  if (h->h_in) (void)hipHostFree(h->h_in);
+  h->release();
+  free_all({h->d_occ});
   h->close();
   delete h;
   return TDSA_OK;
@@ -133,35 +107,19 @@ int tdsa_detect_configure(tdsa_detect h, int bin_lo, int bin_hi, int rank, float
   h->min_width = min_width;
   h->max_gap = max_gap;
   h->xdb = xdb;
-  h->S = max_signals;
+  h->sub_per_row = size_t(max_signals);
   h->configured = true;
   return TDSA_OK;
 }
 
 int tdsa_detect_process(tdsa_detect h, const float* rows_host, size_t n_rows, tdsa_detect_row* row_records_host,
                         tdsa_detect_signal* signal_records_host) {
-  TRY(det_check(h, rows_host, row_records_host, signal_records_host));
-  if (n_rows > h->max_host)
-    return fail(TDSA_ERR_ARG, "block of %zu rows, the handle stages at most %zu (max_host_rows)", n_rows, h->max_host);
-  if (n_rows == 0) return TDSA_OK;
-  TRY(h->own_stream());
-  const size_t bytes = n_rows * size_t(h->n_bins) * sizeof(float);
-  std::memcpy(h->h_in, rows_host, bytes);   // the previous host call has waited: the staging is free
-  HIPCHK(hipMemcpyAsync(h->d_in, h->h_in, bytes, hipMemcpyHostToDevice, h->stream));
-  return det_run(h, h->stream, h->d_in, n_rows, row_records_host, signal_records_host);
+  return RowAnalyser::host(h, kNames, rows_host, n_rows, row_records_host, signal_records_host);
 }
 
 int tdsa_detect_process_dev(tdsa_detect h, tdsa_plan p, const float* rows_dev, size_t n_rows,
                             tdsa_detect_row* row_records_host, tdsa_detect_signal* signal_records_host) {
-  TRY(det_check(h, rows_dev, row_records_host, signal_records_host));
-  if (reinterpret_cast<uintptr_t>(rows_dev) % 4 != 0)
-    return fail(TDSA_ERR_ARG, "rows_dev must be aligned to one float32 (4 bytes)");
-  if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and detector live on different devices");
-  if (n_rows == 0) return TDSA_OK;
-  hipStream_t s;
-  TRY(h->producer_stream(p, &s));
-  TRY(h->order(s));
-  return det_run(h, s, rows_dev, n_rows, row_records_host, signal_records_host);
+  return RowAnalyser::dev(h, kNames, p, rows_dev, n_rows, row_records_host, signal_records_host);
 }
 
 int tdsa_detect_read_occupancy(tdsa_detect h, uint32_t* counts_host, uint64_t* rows_seen, uint64_t* rows_flagged) {
@@ -187,13 +145,6 @@ int tdsa_detect_reset(tdsa_detect h) {
   return TDSA_OK;
 }
 
-int tdsa_detect_timer_begin(tdsa_detect h) {
-  if (!h) return fail(TDSA_ERR_ARG, "null detector");
-  return h->timer_begin();
-}
+int tdsa_detect_timer_begin(tdsa_detect h) { return Lane::timer_begin(h, kNames.handle); }
 
-int tdsa_detect_timer_end(tdsa_detect h, float* elapsed_ms) {
-  if (!h) return fail(TDSA_ERR_ARG, "null detector");
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return h->timer_end(elapsed_ms);
-}
+int tdsa_detect_timer_end(tdsa_detect h, float* elapsed_ms) { return Lane::timer_end(h, kNames.handle, elapsed_ms); }

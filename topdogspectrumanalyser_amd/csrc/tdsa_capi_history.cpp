@@ -437,11 +437,10 @@ int tdsa_history_surface(tdsa_history h, int columns, const tdsa_history_out* ou
 
 int tdsa_history_timer_begin(tdsa_history h) {
   TRY(hist_check(h));
-  return h->timer_begin();
+  return Lane::timer_begin(h, "history");
 }
 
 int tdsa_history_timer_end(tdsa_history h, float* elapsed_ms) {
   TRY(hist_check(h));
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return h->timer_end(elapsed_ms);
+  return Lane::timer_end(h, "history", elapsed_ms);
 }

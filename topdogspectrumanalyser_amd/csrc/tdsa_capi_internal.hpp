@@ -1,10 +1,12 @@
 // tdsa_capi_internal.hpp - what the translation units of the C-ABI layer (tdsa_capi_*.cpp, one per handle type or
 // concern) share: error reporting, the status macros, the host idioms they all use, the few functions that cross files,
 // the plan itself, and - at the end, because they need the plan - Lane, the base of the handle types: their stream,
-// their lifetime, and the one rule that orders a handle's launches whichever stream each goes on; and over it Feed, the
-// base of the streaming filters (down-converter, channelizer, demodulator): taps, history, input count, the bracket and
-// the checks of a call, and both entry points with the host one's staging.  The public face of the library is
-// include/tdsa_hip.h.
+// their lifetime, the timer entry points, and the one rule that orders a handle's launches whichever stream each goes
+// on.  Over Lane stand three bases, each with the checks of a call and both entry points: Feed for the streaming filters
+// (down-converter, channelizer, demodulator: taps, history, input count), IqAccum for the accumulators over IQ streams
+// (power statistics, pulse analysis) and RowAnalyser for the analysers of dB rows (signal detection, channel
+// measurements: the records grown on demand and the tail of a call).  All three stage a host block through Staging.  The
+// public face of the library is include/tdsa_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -343,18 +345,49 @@ struct Lane {
     return TDSA_OK;
   }
 
-  // device time on the handle's stream between the two calls; both first put it behind the last launch, so work that
-  // went on a plan's stream in between is inside the interval
-  int timer_begin() {
-    TRY(own_stream());
-    HIPCHK(hipEventRecord(ev_t0, stream));
+  // tdsa_<x>_timer_begin / _timer_end of a handle type that `who` names ("null <who>"): device time on the handle's
+  // stream between the two calls; both first put it behind the last launch, so work that went on a plan's stream in
+  // between is inside the interval
+  static int timer_begin(Lane* h, const char* who) {
+    if (!h) return fail(TDSA_ERR_ARG, "null %s", who);
+    TRY(h->own_stream());
+    HIPCHK(hipEventRecord(h->ev_t0, h->stream));
     return TDSA_OK;
   }
-  int timer_end(float* elapsed_ms) {
-    TRY(own_stream());
-    HIPCHK(hipEventRecord(ev_t1, stream));
-    HIPCHK(hipEventSynchronize(ev_t1));
-    HIPCHK(hipEventElapsedTime(elapsed_ms, ev_t0, ev_t1));
+  static int timer_end(Lane* h, const char* who, float* elapsed_ms) {
+    if (!h) return fail(TDSA_ERR_ARG, "null %s", who);
+    if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
+    TRY(h->own_stream());
+    HIPCHK(hipEventRecord(h->ev_t1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev_t1));
+    HIPCHK(hipEventElapsedTime(elapsed_ms, h->ev_t0, h->ev_t1));
+    return TDSA_OK;
+  }
+};
+
+// The staging of a synchronous host entry point: a pinned block and the device block it is copied to.  The host call
+// that filled it has waited for its stream before it returned, so the next one finds it free.
+struct Staging {
+  void* h_in = nullptr;
+  void* d_in = nullptr;
+
+  // create, inside the chain that began with open()
+  hipError_t alloc(size_t bytes) {
+    const hipError_t e = hipHostMalloc(&h_in, bytes, hipHostMallocDefault);
+    return e == hipSuccess ? hipMalloc(&d_in, bytes) : e;
+  }
+  // destroy: whichever of the two exist
+  void release() {
+    if (d_in) (void)hipFree(d_in);
+    if (h_in) (void)hipHostFree(h_in);
+  }
+  // `rows` rows of n units of `unit` bytes, row r at in + r * stride units, back to back into h_in; then one copy to
+  // d_in, enqueued on s
+  int fill(hipStream_t s, const void* in, size_t rows, size_t n, size_t stride, size_t unit) {
+    const size_t row = n * unit;
+    for (size_t r = 0; r < rows; ++r)
+      std::memcpy(static_cast<char*>(h_in) + r * row, static_cast<const char*>(in) + r * stride * unit, row);
+    HIPCHK(hipMemcpyAsync(d_in, h_in, rows * row, hipMemcpyHostToDevice, s));
     return TDSA_OK;
   }
 };
@@ -400,8 +433,7 @@ struct Feed : Lane {
   int cur = 0;
   long long n_total = 0;              // inputs (per row) since the last reset
   size_t max_host = 0;                // samples, all rows together, one host call stages
-  void* h_in = nullptr;               // pinned staging of a host block, rows back to back ...
-  void* d_in = nullptr;
+  Staging in;                         // of a host block, rows back to back ...
   void* d_out = nullptr;              // ... and of its outputs
   void* h_out = nullptr;
 
@@ -415,8 +447,7 @@ struct Feed : Lane {
     hipError_t e = hipMalloc(&d_taps, taps_len * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&d_hist[0], hist_bytes);
     if (e == hipSuccess) e = hipMalloc(&d_hist[1], hist_bytes);
-    if (e == hipSuccess) e = hipHostMalloc(&h_in, max_host * 8, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&d_in, max_host * 8);
+    if (e == hipSuccess) e = in.alloc(max_host * 8);
     if (e == hipSuccess) e = hipMalloc(&d_out, ob);
     if (e == hipSuccess) e = hipHostMalloc(&h_out, ob, hipHostMallocDefault);
     if (e == hipSuccess) e = hipMemsetAsync(d_taps, 0, taps_len * sizeof(float), stream);
@@ -424,8 +455,8 @@ struct Feed : Lane {
   }
   // destroy, between drain() and close(): whichever of them exist
   void release() {
-    free_all({d_taps, d_hist[0], d_hist[1], d_in, d_out});
-    if (h_in) (void)hipHostFree(h_in);
+    free_all({d_taps, d_hist[0], d_hist[1], d_out});
+    in.release();
     if (h_out) (void)hipHostFree(h_out);
   }
 
@@ -508,12 +539,9 @@ struct Feed : Lane {
     *c.n_out = 0;
     if (c.n_in == 0) return TDSA_OK;
     HIPCHK(hipSetDevice(f->device));
-    const size_t irow = c.n_in * c.in_unit;
-    for (size_t r = 0; r < c.in_rows; ++r)   // the previous host call has waited: the staging is free
-      std::memcpy(static_cast<char*>(f->h_in) + r * irow, static_cast<const char*>(c.in) + r * c.in_stride * c.in_unit, irow);
-    HIPCHK(hipMemcpyAsync(f->d_in, f->h_in, c.in_rows * irow, hipMemcpyHostToDevice, f->stream));
+    TRY(f->in.fill(f->stream, c.in, c.in_rows, c.n_in, c.in_stride, c.in_unit));
     size_t n = 0;
-    TRY(run(f->stream, static_cast<const void*>(f->d_in), c.n_in, f->d_out, f->outputs(c.n_in), &n));
+    TRY(run(f->stream, static_cast<const void*>(f->in.d_in), c.n_in, f->d_out, f->outputs(c.n_in), &n));
     const size_t orow = n * c.out_unit;
     if (n) HIPCHK(hipMemcpyAsync(f->h_out, f->d_out, c.out_rows * orow, hipMemcpyDeviceToHost, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
@@ -532,6 +560,154 @@ struct Feed : Lane {
     hipStream_t s;
     TRY(f->producer_stream(p, &s));
     return run(s, c.in, c.in_stride, c.out, c.out_stride, c.n_out);
+  }
+};
+
+// What the messages of an accumulator over IQ streams call it: "null <handle>", "the <takes> complex IQ".
+struct IqNames {
+  const char *handle, *takes;
+};
+
+// The base of the accumulators over IQ streams (power statistics, pulse analysis) over Lane: C streams of n_in samples
+// each in I8, U8 or C64, stream c at in + c * in_stride samples.  Neither entry point leaves anything in the caller's
+// memory: the state stays on the device until the handle's _read, and the device entry point does not wait.  A handle
+// type H supplies its state and H::run(s, fmt, in, n_in, in_stride), its launches on stream s between order(s) and
+// done(s).
+//
+// The checks of a call come in ONE order (check): format, alignment to one sample of a pointer that is read in place,
+// null handle, null samples, in_stride; host() adds the block size after them, dev() the plan's device.
+struct IqAccum : Lane {
+  int C = 1;
+  size_t max_host = 0;             // samples, all streams together, one host call stages
+  Staging in;                      // of a host block, streams back to back
+
+  static int check(const IqAccum* h, const IqNames& who, int fmt, const void* in, size_t n_in, size_t in_stride, bool dev) {
+    if (fmt != TDSA_IN_I8 && fmt != TDSA_IN_U8 && fmt != TDSA_IN_C64)
+      return fail(TDSA_ERR_ARG, "in_format=%d: the %s complex IQ (TDSA_IN_I8 / _U8 / _C64)", fmt, who.takes);
+    if (dev && reinterpret_cast<uintptr_t>(in) % unsigned(bytes_per_sample(fmt)) != 0)
+      return fail(TDSA_ERR_ARG, "input pointer must be aligned to one sample (%d bytes)", bytes_per_sample(fmt));
+    if (!h) return fail(TDSA_ERR_ARG, "null %s", who.handle);
+    if (n_in > 0 && !in) return fail(TDSA_ERR_ARG, "null samples");
+    if (h->C > 1 && in_stride < n_in)
+      return fail(TDSA_ERR_ARG, "in_stride=%zu: below the call's %zu samples per stream", in_stride, n_in);
+    return TDSA_OK;
+  }
+
+  // host: through the staging on the handle's own stream; returns when the staging is free for the next host call
+  template <class H>
+  static int host(H* h, const IqNames& who, int fmt, const void* in, size_t n_in, size_t in_stride) {
+    TRY(check(h, who, fmt, in, n_in, in_stride, false));
+    const size_t most = h->max_host / size_t(h->C);
+    if (n_in > most)
+      return h->C == 1
+                 ? fail(TDSA_ERR_ARG, "block of %zu samples, the handle stages at most %zu (max_host_samples)", n_in, most)
+                 : fail(TDSA_ERR_ARG, "block of %zu samples per stream, the handle stages at most %zu (max_host_samples / "
+                        "streams)", n_in, most);
+    if (n_in == 0) return TDSA_OK;
+    TRY(h->own_stream());
+    TRY(h->in.fill(h->stream, in, size_t(h->C), n_in, in_stride, size_t(bytes_per_sample(fmt))));
+    TRY(h->run(h->stream, fmt, static_cast<const void*>(h->in.d_in), n_in, n_in));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return TDSA_OK;
+  }
+  // dev: in place, on plan p's stream (null: the handle's own), no host wait
+  template <class H>
+  static int dev(H* h, const IqNames& who, tdsa_plan p, int fmt, const void* in, size_t n_in, size_t in_stride) {
+    TRY(check(h, who, fmt, in, n_in, in_stride, true));
+    if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and %s live on different devices", who.handle);
+    if (n_in == 0) return TDSA_OK;
+    hipStream_t s;
+    TRY(h->producer_stream(p, &s));
+    return h->run(s, fmt, in, n_in, in_stride);
+  }
+
+  // the streams a _read names
+  int stream_range(int first_stream, int n_streams) const {
+    if (first_stream < 0 || n_streams < 1 || first_stream > C - n_streams)
+      return fail(TDSA_ERR_ARG, "streams %d .. %d: inside the handle's %d", first_stream, first_stream + n_streams - 1, C);
+    return TDSA_OK;
+  }
+};
+
+// What the messages of an analyser of dB rows call it: "null <handle>", "tdsa_<prefix>_configure", "null <sub> records".
+struct RowNames {
+  const char *handle, *prefix, *sub;
+};
+
+// The base of the analysers of dB rows (signal detection, channel measurements) over Lane: n_rows rows of n_bins
+// float32 back to back, and per call two kinds of records in the caller's memory, one per row and sub_per_row per row,
+// through device buffers that grow on demand.  Both entry points return when the records have arrived.  A handle type H
+// supplies H::launch(s, rows, n_rows), which enqueues its kernel on s and returns a hipError_t, and H::tally(row_host,
+// n_rows), which reads the call's row records for the handle's second total.
+//
+// The checks of a call come in ONE order (check): null handle, not configured, null rows, the two null record pointers;
+// host() adds the block size after them, dev() the alignment of the rows and the plan's device.
+struct RowAnalyser : Lane {
+  int n_bins = 0;
+  size_t max_host = 0;             // rows one host call stages
+  Staging in;
+  void* d_row = nullptr;           // the records of either entry point ...
+  void* d_sub = nullptr;
+  size_t row_cap = 0, sub_cap = 0;                     // ... in records ...
+  size_t row_unit = 0, sub_unit = 0, sub_per_row = 1;  // ... of so many bytes; d_sub holds sub_per_row per row
+  uint64_t rows_seen = 0;
+  bool configured = false;
+
+  // create, inside the chain that began with open(); n_bins and max_host are set
+  hipError_t alloc() { return in.alloc(max_host * size_t(n_bins) * sizeof(float)); }
+  // destroy, between drain() and close()
+  void release() {
+    in.release();
+    free_all({d_row, d_sub});
+  }
+
+  static int check(const RowAnalyser* h, const RowNames& who, const void* rows, const void* row_rec, const void* sub_rec) {
+    if (!h) return fail(TDSA_ERR_ARG, "null %s", who.handle);
+    if (!h->configured) return fail(TDSA_ERR_ARG, "not configured: call tdsa_%s_configure first", who.prefix);
+    if (!rows) return fail(TDSA_ERR_ARG, "null rows");
+    if (!row_rec) return fail(TDSA_ERR_ARG, "null row records");
+    if (!sub_rec) return fail(TDSA_ERR_ARG, "null %s records", who.sub);
+    return TDSA_OK;
+  }
+
+  // one call on stream s, which the caller has put behind the last launch, over device rows
+  template <class H, class R>
+  static int run(H* h, hipStream_t s, const float* rows, size_t n_rows, R* row_host, void* sub_host) {
+    TRY(grow_device(&h->d_row, &h->row_cap, n_rows, h->last, h->row_unit));
+    TRY(grow_device(&h->d_sub, &h->sub_cap, n_rows * h->sub_per_row, h->last, h->sub_unit));
+    HIPCHK(h->launch(s, rows, n_rows));
+    HIPCHK(hipMemcpyAsync(row_host, h->d_row, n_rows * h->row_unit, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sub_host, h->d_sub, n_rows * h->sub_per_row * h->sub_unit, hipMemcpyDeviceToHost, s));
+    TRY(h->done(s));
+    HIPCHK(hipStreamSynchronize(s));   // the records are the call's result: they are in the caller's memory on return
+    h->rows_seen += n_rows;
+    h->tally(row_host, n_rows);
+    return TDSA_OK;
+  }
+
+  // host: through the staging, on the handle's own stream
+  template <class H, class R>
+  static int host(H* h, const RowNames& who, const float* rows, size_t n_rows, R* row_host, void* sub_host) {
+    TRY(check(h, who, rows, row_host, sub_host));
+    if (n_rows > h->max_host)
+      return fail(TDSA_ERR_ARG, "block of %zu rows, the handle stages at most %zu (max_host_rows)", n_rows, h->max_host);
+    if (n_rows == 0) return TDSA_OK;
+    TRY(h->own_stream());
+    TRY(h->in.fill(h->stream, rows, 1, n_rows * size_t(h->n_bins), 0, sizeof(float)));
+    return run(h, h->stream, static_cast<const float*>(h->in.d_in), n_rows, row_host, sub_host);
+  }
+  // dev: in place, on plan p's stream (null: the handle's own)
+  template <class H, class R>
+  static int dev(H* h, const RowNames& who, tdsa_plan p, const float* rows, size_t n_rows, R* row_host, void* sub_host) {
+    TRY(check(h, who, rows, row_host, sub_host));
+    if (reinterpret_cast<uintptr_t>(rows) % 4 != 0)
+      return fail(TDSA_ERR_ARG, "rows_dev must be aligned to one float32 (4 bytes)");
+    if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and %s live on different devices", who.handle);
+    if (n_rows == 0) return TDSA_OK;
+    hipStream_t s;
+    TRY(h->producer_stream(p, &s));
+    TRY(h->order(s));
+    return run(h, s, rows, n_rows, row_host, sub_host);
   }
 };
 

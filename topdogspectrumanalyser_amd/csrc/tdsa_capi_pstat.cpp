@@ -12,20 +12,37 @@ static_assert(TDSA_PSTAT_MAX_STREAMS == kPstatMaxStreams && TDSA_PSTAT_BINS == k
               "the public constants are the kernel's");
 
 // ---- power statistics (tdsa_pstat.hip) ---------------------------------------------------------------------------
-struct tdsa_pstat_s : Lane {
-  int C = 1;
-  size_t max_host = 0;             // samples, all streams together, one host call stages
-  void* h_in = nullptr;            // pinned staging of a host block, streams back to back ...
-  void* d_in = nullptr;
-  PstatRecord* d_rec = nullptr;    // ... and the state: [C] records, [C][256] mantissa sums, [C][2048] counts
+struct tdsa_pstat_s : IqAccum {
+  PstatRecord* d_rec = nullptr;    // the state: [C] records, [C][256] mantissa sums, [C][2048] counts
   unsigned long long* d_msum = nullptr;
   unsigned long long* d_hist = nullptr;
   std::vector<PstatRecord> fresh;  // [C] what a reset writes: zeros, min_bits all ones
   int exp_lo = -40;
   float gate = 0.0f;
+
+  // one launch on stream s over device samples; does not wait
+  int run(hipStream_t s, int fmt, const void* in, size_t n_in, size_t in_stride) {
+    PstatLaunch a;
+    a.in = in;
+    a.fmt = fmt;
+    a.C = C;
+    a.n = n_in;
+    a.in_stride = in_stride;
+    a.bin_base = (exp_lo + 127) << 5;
+    a.gate = gate;
+    a.rec = d_rec;
+    a.msum = d_msum;
+    a.hist = d_hist;
+    TRY(order(s));
+    HIPCHK(launch_pstat(a, s));
+    TRY(done(s));
+    return TDSA_OK;
+  }
 };
 
 namespace {
+
+constexpr IqNames kNames = {"power statistics handle", "power statistics take"};
 
 // the state as no sample has touched it, enqueued on the handle's own stream behind the last launch
 int pstat_clear(tdsa_pstat_s* h) {
@@ -35,38 +52,6 @@ int pstat_clear(tdsa_pstat_s* h) {
   HIPCHK(hipMemcpyAsync(h->d_rec, h->fresh.data(), size_t(h->C) * sizeof(PstatRecord), hipMemcpyHostToDevice, h->stream));
   TRY(h->done(h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // earlier calls have finished; `fresh` is read
-  return TDSA_OK;
-}
-
-// the checks both entry points share, before any HIP call; dev: the pointer is read in place, so one sample aligns it
-int pstat_check(const tdsa_pstat_s* h, int fmt, const void* in, size_t n_in, size_t in_stride, bool dev) {
-  if (fmt != TDSA_IN_I8 && fmt != TDSA_IN_U8 && fmt != TDSA_IN_C64)
-    return fail(TDSA_ERR_ARG, "in_format=%d: the power statistics take complex IQ (TDSA_IN_I8 / _U8 / _C64)", fmt);
-  if (dev && reinterpret_cast<uintptr_t>(in) % unsigned(bytes_per_sample(fmt)) != 0)
-    return fail(TDSA_ERR_ARG, "input pointer must be aligned to one sample (%d bytes)", bytes_per_sample(fmt));
-  if (!h) return fail(TDSA_ERR_ARG, "null power statistics handle");
-  if (n_in > 0 && !in) return fail(TDSA_ERR_ARG, "null samples");
-  if (h->C > 1 && in_stride < n_in)
-    return fail(TDSA_ERR_ARG, "in_stride=%zu: below the call's %zu samples per stream", in_stride, n_in);
-  return TDSA_OK;
-}
-
-// one launch on stream s over device samples; does not wait
-int pstat_run(tdsa_pstat_s* h, hipStream_t s, int fmt, const void* in, size_t n_in, size_t in_stride) {
-  PstatLaunch a;
-  a.in = in;
-  a.fmt = fmt;
-  a.C = h->C;
-  a.n = n_in;
-  a.in_stride = in_stride;
-  a.bin_base = (h->exp_lo + 127) << 5;
-  a.gate = h->gate;
-  a.rec = h->d_rec;
-  a.msum = h->d_msum;
-  a.hist = h->d_hist;
-  TRY(h->order(s));
-  HIPCHK(launch_pstat(a, s));
-  TRY(h->done(s));
   return TDSA_OK;
 }
 
@@ -88,8 +73,7 @@ int tdsa_pstat_create(int device_id, int streams, size_t max_host_samples, tdsa_
   zero.min_bits = 0xffffffffu;
   h->fresh.assign(size_t(streams), zero);
   hipError_t e = h->open(true);
-  if (e == hipSuccess) e = hipHostMalloc(&h->h_in, max_host_samples * 8, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&h->d_in, max_host_samples * 8);
+  if (e == hipSuccess) e = h->in.alloc(max_host_samples * 8);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_rec), size_t(streams) * sizeof(PstatRecord));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_msum), size_t(streams) * kPstatExponents * 8);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_hist), size_t(streams) * kPstatBins * 8);
@@ -109,8 +93,8 @@ int tdsa_pstat_create(int device_id, int streams, size_t max_host_samples, tdsa_
 int tdsa_pstat_destroy(tdsa_pstat h) {
   if (!h) return TDSA_OK;
   h->drain();
-  free_all({h->d_in, h->d_rec, h->d_msum, h->d_hist});
-  if (h->h_in) (void)hipHostFree(h->h_in);
+  h->in.release();
+  free_all({h->d_rec, h->d_msum, h->d_hist});
   h->close();
   delete h;
   return TDSA_OK;
@@ -133,39 +117,18 @@ int tdsa_pstat_reset(tdsa_pstat h) {
 }
 
 int tdsa_pstat_process(tdsa_pstat h, int in_format, const void* in_host, size_t n_in, size_t in_stride) {
-  TRY(pstat_check(h, in_format, in_host, n_in, in_stride, false));
-  const size_t most = h->max_host / size_t(h->C);
-  if (n_in > most)
-    return h->C == 1
-               ? fail(TDSA_ERR_ARG, "block of %zu samples, the handle stages at most %zu (max_host_samples)", n_in, most)
-               : fail(TDSA_ERR_ARG, "block of %zu samples per stream, the handle stages at most %zu (max_host_samples / "
-                      "streams)", n_in, most);
-  if (n_in == 0) return TDSA_OK;
-  TRY(h->own_stream());
-  const size_t unit = size_t(bytes_per_sample(in_format)), row = n_in * unit;
-  for (int c = 0; c < h->C; ++c)   // the previous host call has waited: the staging is free
-    std::memcpy(static_cast<char*>(h->h_in) + size_t(c) * row, static_cast<const char*>(in_host) + size_t(c) * in_stride * unit, row);
-  HIPCHK(hipMemcpyAsync(h->d_in, h->h_in, size_t(h->C) * row, hipMemcpyHostToDevice, h->stream));
-  TRY(pstat_run(h, h->stream, in_format, h->d_in, n_in, n_in));
-  HIPCHK(hipStreamSynchronize(h->stream));   // the staging is free for the next host call
-  return TDSA_OK;
+  return IqAccum::host(h, kNames, in_format, in_host, n_in, in_stride);
 }
 
 int tdsa_pstat_process_dev(tdsa_pstat h, tdsa_plan p, int in_format, const void* in_dev, size_t n_in, size_t in_stride) {
-  TRY(pstat_check(h, in_format, in_dev, n_in, in_stride, true));
-  if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and power statistics handle live on different devices");
-  if (n_in == 0) return TDSA_OK;
-  hipStream_t s;
-  TRY(h->producer_stream(p, &s));
-  return pstat_run(h, s, in_format, in_dev, n_in, in_stride);   // no wait: the state stays on the device until _read
+  return IqAccum::dev(h, kNames, p, in_format, in_dev, n_in, in_stride);   // no wait: the state stays on the device until _read
 }
 
 int tdsa_pstat_read(tdsa_pstat h, int first_stream, int n_streams, tdsa_pstat_record* records_host, uint64_t* msum_host,
                     uint64_t* hist_host) {
   if (!records_host) return fail(TDSA_ERR_ARG, "null records");
   if (!h) return fail(TDSA_ERR_ARG, "null power statistics handle");
-  if (first_stream < 0 || n_streams < 1 || first_stream > h->C - n_streams)
-    return fail(TDSA_ERR_ARG, "streams %d .. %d: inside the handle's %d", first_stream, first_stream + n_streams - 1, h->C);
+  TRY(h->stream_range(first_stream, n_streams));
   TRY(h->own_stream());            // behind the last launch, whichever stream it went on
   const size_t a = size_t(first_stream), n = size_t(n_streams);
   HIPCHK(hipMemcpyAsync(records_host, h->d_rec + a, n * sizeof(PstatRecord), hipMemcpyDeviceToHost, h->stream));
@@ -178,13 +141,6 @@ int tdsa_pstat_read(tdsa_pstat h, int first_stream, int n_streams, tdsa_pstat_re
   return TDSA_OK;
 }
 
-int tdsa_pstat_timer_begin(tdsa_pstat h) {
-  if (!h) return fail(TDSA_ERR_ARG, "null power statistics handle");
-  return h->timer_begin();
-}
+int tdsa_pstat_timer_begin(tdsa_pstat h) { return Lane::timer_begin(h, kNames.handle); }
 
-int tdsa_pstat_timer_end(tdsa_pstat h, float* elapsed_ms) {
-  if (!h) return fail(TDSA_ERR_ARG, "null power statistics handle");
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return h->timer_end(elapsed_ms);
-}
+int tdsa_pstat_timer_end(tdsa_pstat h, float* elapsed_ms) { return Lane::timer_end(h, kNames.handle, elapsed_ms); }

@@ -17,13 +17,9 @@ static_assert(TDSA_PULSE_MAX_STREAMS == kPulseMaxStreams && TDSA_PULSE_MAX_RECOR
               "the public constants are the kernel's");
 
 // ---- pulse analysis (tdsa_pulse.hip) -----------------------------------------------------------------------------
-struct tdsa_pulse_s : Lane {
-  int C = 1;
+struct tdsa_pulse_s : IqAccum {
   int capacity = 1;
-  size_t max_host = 0;             // samples, all streams together, one host call stages
-  void* h_in = nullptr;            // pinned staging of a host block, streams back to back ...
-  void* d_in = nullptr;
-  PulseTileInfo* d_tiles = nullptr;   // ... the tile summaries of one launch ...
+  PulseTileInfo* d_tiles = nullptr;   // the tile summaries of one launch ...
   PulseSummary* d_sum = nullptr;   // ... and the state: [C] summaries, [C] open pulses, [C][2] last samples, [C][capacity] records
   PulseRecord* d_open = nullptr;
   float2* d_prev = nullptr;
@@ -33,9 +29,41 @@ struct tdsa_pulse_s : Lane {
   long long seen = 0;              // samples per stream since the last reset: the index of the next call's first
   int parity = 0;
   int max_launch_tiles = kPulseMaxLaunchTiles, passes = 7;
+
+  // the launches of one call on stream s over device samples; does not wait
+  int run(hipStream_t s, int fmt, const void* in, size_t n_in, size_t in_stride) {
+    PulseLaunch a;
+    a.in = in;
+    a.fmt = fmt;
+    a.C = C;
+    a.n = n_in;
+    a.in_stride = in_stride;
+    a.base = seen;
+    a.on_level = on_level;
+    a.off_level = off_level;
+    a.min_width = int(min_width);
+    a.capacity = capacity;
+    a.parity = parity;
+    a.max_launch_tiles = max_launch_tiles;
+    a.passes = passes;
+    a.tiles = d_tiles;
+    a.sum = d_sum;
+    a.open = d_open;
+    a.prev = d_prev;
+    a.records = d_rec;
+    TRY(order(s));
+    int launches = 0;
+    HIPCHK(launch_pulse(a, s, &launches));
+    TRY(done(s));
+    seen += (long long)n_in;
+    parity ^= launches & 1;
+    return TDSA_OK;
+  }
 };
 
 namespace {
+
+constexpr IqNames kNames = {"pulse handle", "pulse analysis takes"};
 
 // the state as no sample has touched it, enqueued on the handle's own stream behind the last launch.  The records are
 // left: n_pulses says how many of them count
@@ -51,55 +79,12 @@ int pulse_clear(tdsa_pulse_s* h) {
   return TDSA_OK;
 }
 
-// the checks both entry points share, before any HIP call; dev: the pointer is read in place, so one sample aligns it
-int pulse_check(const tdsa_pulse_s* h, int fmt, const void* in, size_t n_in, size_t in_stride, bool dev) {
-  if (fmt != TDSA_IN_I8 && fmt != TDSA_IN_U8 && fmt != TDSA_IN_C64)
-    return fail(TDSA_ERR_ARG, "in_format=%d: the pulse analysis takes complex IQ (TDSA_IN_I8 / _U8 / _C64)", fmt);
-  if (dev && reinterpret_cast<uintptr_t>(in) % unsigned(bytes_per_sample(fmt)) != 0)
-    return fail(TDSA_ERR_ARG, "input pointer must be aligned to one sample (%d bytes)", bytes_per_sample(fmt));
-  if (!h) return fail(TDSA_ERR_ARG, "null pulse handle");
-  if (n_in > 0 && !in) return fail(TDSA_ERR_ARG, "null samples");
-  if (h->C > 1 && in_stride < n_in)
-    return fail(TDSA_ERR_ARG, "in_stride=%zu: below the call's %zu samples per stream", in_stride, n_in);
-  return TDSA_OK;
-}
-
 int levels_check(float on_level, float off_level, long long min_width) {
   if (!(std::isfinite(on_level) && on_level > 0.0f))
     return fail(TDSA_ERR_ARG, "on_level=%g: a finite float32 above 0", double(on_level));
   if (!(off_level > 0.0f && off_level <= on_level))
     return fail(TDSA_ERR_ARG, "off_level=%g: above 0 and at most on_level=%g", double(off_level), double(on_level));
   if (min_width < 1 || min_width >= (1ll << 31)) return fail(TDSA_ERR_ARG, "min_width=%lld: 1 .. 2^31 - 1", min_width);
-  return TDSA_OK;
-}
-
-// the launches of one call on stream s over device samples; does not wait
-int pulse_run(tdsa_pulse_s* h, hipStream_t s, int fmt, const void* in, size_t n_in, size_t in_stride) {
-  PulseLaunch a;
-  a.in = in;
-  a.fmt = fmt;
-  a.C = h->C;
-  a.n = n_in;
-  a.in_stride = in_stride;
-  a.base = h->seen;
-  a.on_level = h->on_level;
-  a.off_level = h->off_level;
-  a.min_width = int(h->min_width);
-  a.capacity = h->capacity;
-  a.parity = h->parity;
-  a.max_launch_tiles = h->max_launch_tiles;
-  a.passes = h->passes;
-  a.tiles = h->d_tiles;
-  a.sum = h->d_sum;
-  a.open = h->d_open;
-  a.prev = h->d_prev;
-  a.records = h->d_rec;
-  TRY(h->order(s));
-  int launches = 0;
-  HIPCHK(launch_pulse(a, s, &launches));
-  TRY(h->done(s));
-  h->seen += (long long)n_in;
-  h->parity ^= launches & 1;
   return TDSA_OK;
 }
 
@@ -121,8 +106,7 @@ int tdsa_pulse_create(int device_id, int streams, int capacity, size_t max_host_
   h->capacity = capacity;
   h->max_host = max_host_samples;
   hipError_t e = h->open(true);
-  if (e == hipSuccess) e = hipHostMalloc(&h->h_in, max_host_samples * 8, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&h->d_in, max_host_samples * 8);
+  if (e == hipSuccess) e = h->in.alloc(max_host_samples * 8);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_tiles), size_t(kPulseMaxLaunchTiles) * sizeof(PulseTileInfo));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_sum), size_t(streams) * sizeof(PulseSummary));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_open), size_t(streams) * sizeof(PulseRecord));
@@ -144,8 +128,8 @@ int tdsa_pulse_create(int device_id, int streams, int capacity, size_t max_host_
 int tdsa_pulse_destroy(tdsa_pulse h) {
   if (!h) return TDSA_OK;
   h->drain();
-  free_all({h->d_in, h->d_tiles, h->d_sum, h->d_open, h->d_prev, h->d_rec});
-  if (h->h_in) (void)hipHostFree(h->h_in);
+  h->in.release();
+  free_all({h->d_tiles, h->d_sum, h->d_open, h->d_prev, h->d_rec});
   h->close();
   delete h;
   return TDSA_OK;
@@ -167,38 +151,17 @@ int tdsa_pulse_reset(tdsa_pulse h) {
 }
 
 int tdsa_pulse_process(tdsa_pulse h, int in_format, const void* in_host, size_t n_in, size_t in_stride) {
-  TRY(pulse_check(h, in_format, in_host, n_in, in_stride, false));
-  const size_t most = h->max_host / size_t(h->C);
-  if (n_in > most)
-    return h->C == 1
-               ? fail(TDSA_ERR_ARG, "block of %zu samples, the handle stages at most %zu (max_host_samples)", n_in, most)
-               : fail(TDSA_ERR_ARG, "block of %zu samples per stream, the handle stages at most %zu (max_host_samples / "
-                      "streams)", n_in, most);
-  if (n_in == 0) return TDSA_OK;
-  TRY(h->own_stream());
-  const size_t unit = size_t(bytes_per_sample(in_format)), row = n_in * unit;
-  for (int c = 0; c < h->C; ++c)   // the previous host call has waited: the staging is free
-    std::memcpy(static_cast<char*>(h->h_in) + size_t(c) * row, static_cast<const char*>(in_host) + size_t(c) * in_stride * unit, row);
-  HIPCHK(hipMemcpyAsync(h->d_in, h->h_in, size_t(h->C) * row, hipMemcpyHostToDevice, h->stream));
-  TRY(pulse_run(h, h->stream, in_format, h->d_in, n_in, n_in));
-  HIPCHK(hipStreamSynchronize(h->stream));   // the staging is free for the next host call
-  return TDSA_OK;
+  return IqAccum::host(h, kNames, in_format, in_host, n_in, in_stride);
 }
 
 int tdsa_pulse_process_dev(tdsa_pulse h, tdsa_plan p, int in_format, const void* in_dev, size_t n_in, size_t in_stride) {
-  TRY(pulse_check(h, in_format, in_dev, n_in, in_stride, true));
-  if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and pulse handle live on different devices");
-  if (n_in == 0) return TDSA_OK;
-  hipStream_t s;
-  TRY(h->producer_stream(p, &s));
-  return pulse_run(h, s, in_format, in_dev, n_in, in_stride);   // no wait: the state stays on the device until _read
+  return IqAccum::dev(h, kNames, p, in_format, in_dev, n_in, in_stride);   // no wait: the state stays on the device until _read
 }
 
 int tdsa_pulse_read(tdsa_pulse h, int first_stream, int n_streams, tdsa_pulse_summary* summaries_host) {
   if (!summaries_host) return fail(TDSA_ERR_ARG, "null summaries");
   if (!h) return fail(TDSA_ERR_ARG, "null pulse handle");
-  if (first_stream < 0 || n_streams < 1 || first_stream > h->C - n_streams)
-    return fail(TDSA_ERR_ARG, "streams %d .. %d: inside the handle's %d", first_stream, first_stream + n_streams - 1, h->C);
+  TRY(h->stream_range(first_stream, n_streams));
   TRY(h->own_stream());            // behind the last launch, whichever stream it went on
   HIPCHK(hipMemcpyAsync(summaries_host, h->d_sum + first_stream, size_t(n_streams) * sizeof(PulseSummary), hipMemcpyDeviceToHost,
                         h->stream));
@@ -239,13 +202,6 @@ int tdsa_pulse_debug_limits(tdsa_pulse h, int max_launch_tiles, int passes) {
   return TDSA_OK;
 }
 
-int tdsa_pulse_timer_begin(tdsa_pulse h) {
-  if (!h) return fail(TDSA_ERR_ARG, "null pulse handle");
-  return h->timer_begin();
-}
+int tdsa_pulse_timer_begin(tdsa_pulse h) { return Lane::timer_begin(h, kNames.handle); }
 
-int tdsa_pulse_timer_end(tdsa_pulse h, float* elapsed_ms) {
-  if (!h) return fail(TDSA_ERR_ARG, "null pulse handle");
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return h->timer_end(elapsed_ms);
-}
+int tdsa_pulse_timer_end(tdsa_pulse h, float* elapsed_ms) { return Lane::timer_end(h, kNames.handle, elapsed_ms); }

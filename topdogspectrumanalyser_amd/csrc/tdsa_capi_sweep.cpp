@@ -270,13 +270,6 @@ int tdsa_sweep_get_steps(tdsa_sweep w, float* T_host, unsigned char* valid_host)
   return TDSA_OK;
 }
 
-int tdsa_sweep_timer_begin(tdsa_sweep w) {
-  if (!w) return fail(TDSA_ERR_ARG, "null sweep");
-  return w->timer_begin();
-}
+int tdsa_sweep_timer_begin(tdsa_sweep w) { return Lane::timer_begin(w, "sweep"); }
 
-int tdsa_sweep_timer_end(tdsa_sweep w, float* elapsed_ms) {
-  if (!w) return fail(TDSA_ERR_ARG, "null sweep");
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return w->timer_end(elapsed_ms);
-}
+int tdsa_sweep_timer_end(tdsa_sweep w, float* elapsed_ms) { return Lane::timer_end(w, "sweep", elapsed_ms); }

@@ -210,13 +210,6 @@ int tdsa_symsync_process_dev(tdsa_symsync h, tdsa_plan p, const void* in_dev, si
   return TDSA_OK;
 }
 
-int tdsa_symsync_timer_begin(tdsa_symsync h) {
-  if (!h) return fail(TDSA_ERR_ARG, "null symbol synchroniser");
-  return h->timer_begin();
-}
+int tdsa_symsync_timer_begin(tdsa_symsync h) { return Lane::timer_begin(h, "symbol synchroniser"); }
 
-int tdsa_symsync_timer_end(tdsa_symsync h, float* elapsed_ms) {
-  if (!h) return fail(TDSA_ERR_ARG, "null symbol synchroniser");
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return h->timer_end(elapsed_ms);
-}
+int tdsa_symsync_timer_end(tdsa_symsync h, float* elapsed_ms) { return Lane::timer_end(h, "symbol synchroniser", elapsed_ms); }

@@ -262,13 +262,6 @@ int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int 
   return TDSA_OK;
 }
 
-int tdsa_zspan_timer_begin(tdsa_zspan z) {
-  if (!z) return fail(TDSA_ERR_ARG, "null zero span");
-  return z->timer_begin();
-}
+int tdsa_zspan_timer_begin(tdsa_zspan z) { return Lane::timer_begin(z, "zero span"); }
 
-int tdsa_zspan_timer_end(tdsa_zspan z, float* elapsed_ms) {
-  if (!z) return fail(TDSA_ERR_ARG, "null zero span");
-  if (!elapsed_ms) return fail(TDSA_ERR_ARG, "null elapsed_ms");
-  return z->timer_end(elapsed_ms);
-}
+int tdsa_zspan_timer_end(tdsa_zspan z, float* elapsed_ms) { return Lane::timer_end(z, "zero span", elapsed_ms); }

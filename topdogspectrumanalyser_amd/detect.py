@@ -18,8 +18,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import SpectrumEngine
-from .zoom import check_same_device
+from ._inputs import _DbRows
 
 MAX_BINS = 16384
 MAX_SIGNALS = 64
@@ -91,7 +90,7 @@ def detections_from(rows: np.ndarray, signals: np.ndarray) -> Detections:
                       rows["flags"].copy(), signals, rows)
 
 
-class SignalDetector(nat._Handle, nat._Timer):
+class SignalDetector(_DbRows, nat._Handle, nat._Timer):
     """Emissions of [n_rows][n_bins] float32 dB rows, 1 <= n_bins <= 16384.
 
     floor_quantile: which order statistic of the search range is the noise floor (0.5: the median); rank= names it
@@ -100,6 +99,8 @@ class SignalDetector(nat._Handle, nat._Timer):
     x-dB width; max_signals records per row (1 .. 64)."""
     _destroy = "tdsa_detect_destroy"
     _timer = ("tdsa_detect_timer_begin", "tdsa_detect_timer_end")
+    _process = ("tdsa_detect_process", "tdsa_detect_process_dev")
+    _result = staticmethod(detections_from)
 
     def __init__(self, n_bins: int, *, floor_quantile: float = 0.5, margin_db: float = 10.0, min_width: int = 1,
                  max_gap: int = 0, xdb: float = 3.0, max_signals: int = 16, bins: Optional[Tuple[int, int]] = None,
@@ -108,11 +109,7 @@ class SignalDetector(nat._Handle, nat._Timer):
         if not 1 <= self.n_bins <= MAX_BINS:
             raise ValueError(f"n_bins={n_bins}: 1 .. {MAX_BINS}")
         cfg = self._checked(floor_quantile, margin_db, min_width, max_gap, xdb, max_signals, bins, rank)
-        if max_host_rows is None:
-            max_host_rows = max(1, min(4096, (16 << 20) // (4 * self.n_bins)))     # 16 MiB of pinned staging
-        self.max_host_rows = int(max_host_rows)
-        if self.max_host_rows < 1:
-            raise ValueError(f"max_host_rows={max_host_rows}: at least 1")
+        self._stage(max_host_rows)
         self.device = int(device)
         self._h = C.c_void_p()
         nat.check(nat.lib.tdsa_detect_create(self.device, self.n_bins, self.max_host_rows, C.byref(self._h)))
@@ -162,39 +159,6 @@ class SignalDetector(nat._Handle, nat._Timer):
 
     def _records(self, n_rows: int):
         return np.zeros(n_rows, dtype=ROW_RECORD), np.zeros((n_rows, self.max_signals), dtype=SIGNAL_RECORD)
-
-    def process(self, rows) -> Detections:
-        """Rows in host memory, [n_rows][n_bins] (or one row), float32."""
-        a = np.asarray(rows)
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim != 2 or a.shape[1] != self.n_bins or a.dtype.kind not in "fiu":
-            raise ValueError(f"rows of dtype {a.dtype} and shape {a.shape}: [n_rows][{self.n_bins}] real values")
-        if a.shape[0] > self.max_host_rows:
-            raise ValueError(f"{a.shape[0]} rows: the handle stages at most {self.max_host_rows} (max_host_rows)")
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        rr, sig = self._records(a.shape[0])
-        nat.check(nat.lib.tdsa_detect_process(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0],
-                                              rr.ctypes.data_as(C.c_void_p), sig.ctypes.data_as(C.c_void_p)))
-        return detections_from(rr, sig)
-
-    def process_device(self, engine: Optional[SpectrumEngine], rows_dev: int, n_rows: int) -> Detections:
-        """Rows already in device memory, n_rows of n_bins float32 back to back at rows_dev, on `engine`'s stream behind
-        its work (None: the handle's own).  Returns when the records have arrived; no row leaves the device."""
-        n_rows = int(n_rows)
-        if n_rows < 0:
-            raise ValueError(f"n_rows={n_rows}")
-        if not rows_dev:
-            raise ValueError("null pointer")
-        if int(rows_dev) % 4:
-            raise ValueError("rows pointer must be aligned to one float32 (4 bytes)")
-        if engine is not None:
-            check_same_device(engine.device, self.device)
-        rr, sig = self._records(n_rows)
-        nat.check(nat.lib.tdsa_detect_process_dev(self._h, engine._h if engine is not None else None,
-                                                  C.c_void_p(int(rows_dev)), n_rows, rr.ctypes.data_as(C.c_void_p),
-                                                  sig.ctypes.data_as(C.c_void_p)))
-        return detections_from(rr, sig)
 
     def occupancy(self) -> Tuple[np.ndarray, int, int]:
         """(counts uint32 [n_bins], rows seen, rows flagged) since the last reset: counts[i] rows had bin i above their

@@ -18,8 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import SpectrumEngine
-from .zoom import check_same_device
+from ._inputs import _DbRows
 
 MAX_BINS = 16384
 MAX_CHANNELS = 16
@@ -170,7 +169,7 @@ def measurements_from(rows: np.ndarray, channels: np.ndarray) -> Measurements:
     return Measurements(*(rows[f].copy() for f in ROW_FIELDS), channels, rows)
 
 
-class ChannelMeasure(nat._Handle, nat._Timer):
+class ChannelMeasure(_DbRows, nat._Handle, nat._Timer):
     """Channel power, occupied bandwidth, x-dB width and limit mask of [n_rows][n_bins] float32 dB rows, 1 <= n_bins <=
     16384.
 
@@ -180,6 +179,8 @@ class ChannelMeasure(nat._Handle, nat._Timer):
     None, NaN = bin not tested; limit_relative: the line is relative to channel 0's peak."""
     _destroy = "tdsa_meas_destroy"
     _timer = ("tdsa_meas_timer_begin", "tdsa_meas_timer_end")
+    _process = ("tdsa_meas_process", "tdsa_meas_process_dev")
+    _result = staticmethod(measurements_from)
 
     def __init__(self, n_bins: int, channels, obw: Optional[Tuple[int, int]] = None, fraction: float = 0.99,
                  xdb: float = 26.0, limit=None, limit_relative: bool = False, device: int = 0,
@@ -189,11 +190,7 @@ class ChannelMeasure(nat._Handle, nat._Timer):
             raise ValueError(f"n_bins={n_bins}: 1 .. {MAX_BINS}")
         cfg = self._checked(channels, obw, fraction, xdb)
         lim = self._checked_limit(limit)
-        if max_host_rows is None:
-            max_host_rows = max(1, min(4096, (16 << 20) // (4 * self.n_bins)))     # 16 MiB of pinned staging
-        self.max_host_rows = int(max_host_rows)
-        if self.max_host_rows < 1:
-            raise ValueError(f"max_host_rows={max_host_rows}: at least 1")
+        self._stage(max_host_rows)
         self.device = int(device)
         self.limit, self.limit_relative = None, False
         self._h = C.c_void_p()
@@ -260,39 +257,6 @@ class ChannelMeasure(nat._Handle, nat._Timer):
 
     def _records(self, n_rows: int):
         return np.zeros(n_rows, dtype=ROW_RECORD), np.zeros((n_rows, len(self.channels)), dtype=CHANNEL_RECORD)
-
-    def process(self, rows) -> Measurements:
-        """Rows in host memory, [n_rows][n_bins] (or one row), float32."""
-        a = np.asarray(rows)
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim != 2 or a.shape[1] != self.n_bins or a.dtype.kind not in "fiu":
-            raise ValueError(f"rows of dtype {a.dtype} and shape {a.shape}: [n_rows][{self.n_bins}] real values")
-        if a.shape[0] > self.max_host_rows:
-            raise ValueError(f"{a.shape[0]} rows: the handle stages at most {self.max_host_rows} (max_host_rows)")
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        rr, ch = self._records(a.shape[0])
-        nat.check(nat.lib.tdsa_meas_process(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0],
-                                            rr.ctypes.data_as(C.c_void_p), ch.ctypes.data_as(C.c_void_p)))
-        return measurements_from(rr, ch)
-
-    def process_device(self, engine: Optional[SpectrumEngine], rows_dev: int, n_rows: int) -> Measurements:
-        """Rows already in device memory, n_rows of n_bins float32 back to back at rows_dev, on `engine`'s stream behind
-        its work (None: the handle's own).  Returns when the records have arrived; no row leaves the device."""
-        n_rows = int(n_rows)
-        if n_rows < 0:
-            raise ValueError(f"n_rows={n_rows}")
-        if not rows_dev:
-            raise ValueError("null pointer")
-        if int(rows_dev) % 4:
-            raise ValueError("rows pointer must be aligned to one float32 (4 bytes)")
-        if engine is not None:
-            check_same_device(engine.device, self.device)
-        rr, ch = self._records(n_rows)
-        nat.check(nat.lib.tdsa_meas_process_dev(self._h, engine._h if engine is not None else None,
-                                                C.c_void_p(int(rows_dev)), n_rows, rr.ctypes.data_as(C.c_void_p),
-                                                ch.ctypes.data_as(C.c_void_p)))
-        return measurements_from(rr, ch)
 
     def totals(self) -> Tuple[int, int]:
         """(rows seen, rows whose mask test failed) since the last reset."""

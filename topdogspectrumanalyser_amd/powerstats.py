@@ -19,8 +19,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import SpectrumEngine
-from .zoom import check_same_device
+from ._inputs import _IqStreams
 
 MAX_STREAMS = 256
 BINS, BINS_PER_OCTAVE, OCTAVES, EXPONENTS = 2048, 32, 64, 256
@@ -29,7 +28,6 @@ COUNTS = ("n_total", "n_nan", "n_gated", "n_inf", "n_zero", "n_under", "n_over")
 RECORD = np.dtype([(f, np.uint64) for f in COUNTS] + [("max_bits", np.uint32), ("min_bits", np.uint32),
                                                        ("reserved", np.uint32, (2,))])
 assert RECORD.itemsize == 72 == C.sizeof(nat.PstatRecord)
-_FORMATS = {np.dtype(np.int8): nat.IN_I8, np.dtype(np.uint8): nat.IN_U8, np.dtype(np.complex64): nat.IN_C64}
 
 
 def gaussian_ccdf(db):
@@ -167,7 +165,7 @@ class PowerStatistics:
         return np.interp(np.asarray(prob, dtype=np.float64), p[::-1], x[::-1], left=np.nan, right=np.nan)
 
 
-class PowerStats(nat._Handle, nat._Timer):
+class PowerStats(_IqStreams, nat._Handle, nat._Timer):
     """Statistics of the instantaneous power of `streams` IQ streams (1 .. 256).
 
     exp_lo: the histogram covers the powers [2^exp_lo, 2^(exp_lo + 64)), 32 bins per octave; -126 .. 64.  gate: samples
@@ -175,6 +173,7 @@ class PowerStats(nat._Handle, nat._Timer):
     a burst's on-time; 0 = off.  The state accumulates over all calls until reset() or configure()."""
     _destroy = "tdsa_pstat_destroy"
     _timer = ("tdsa_pstat_timer_begin", "tdsa_pstat_timer_end")
+    _process = ("tdsa_pstat_process", "tdsa_pstat_process_dev")
 
     def __init__(self, streams: int = 1, exp_lo: int = EXP_LO_DEFAULT, gate: float = 0.0, device: int = 0,
                  max_host_samples: Optional[int] = None):
@@ -182,11 +181,7 @@ class PowerStats(nat._Handle, nat._Timer):
         if not 1 <= self.streams <= MAX_STREAMS:
             raise ValueError(f"streams={streams}: 1 .. {MAX_STREAMS}")
         cfg = _checked(exp_lo, gate)
-        if max_host_samples is None:
-            max_host_samples = max(1 << 21, self.streams)      # 16 MiB of pinned staging
-        self.max_host_samples = int(max_host_samples)
-        if self.max_host_samples < self.streams:
-            raise ValueError(f"max_host_samples={max_host_samples}: at least one sample per stream ({self.streams})")
+        self._stage(max_host_samples)
         self.device = int(device)
         self.exp_lo, self.gate = EXP_LO_DEFAULT, 0.0
         self._h = C.c_void_p()
@@ -203,51 +198,6 @@ class PowerStats(nat._Handle, nat._Timer):
 
     def reset(self) -> None:
         nat.check(nat.lib.tdsa_pstat_reset(self._h))
-
-    def process(self, iq) -> None:
-        """Samples in host memory.  The dtype names the format: int8 or uint8 (interleaved I, Q: a last axis of even
-        length) or complex64.  One stream: a 1-D array; more: [streams][...].  A block above the staging goes in pieces,
-        which changes nothing."""
-        a = np.asarray(iq)
-        if a.dtype.kind == "c":
-            a = a.astype(np.complex64, copy=False)
-        fmt = _FORMATS.get(a.dtype)
-        if fmt is None:
-            raise ValueError(f"samples of dtype {a.dtype}: int8 or uint8 (interleaved I, Q) or complex64")
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim != 2 or a.shape[0] != self.streams:
-            raise ValueError(f"samples of shape {np.shape(iq)}: [{self.streams}][n], or [n] for one stream")
-        per = 1 if fmt == nat.IN_C64 else 2
-        if a.shape[1] % per:
-            raise ValueError(f"{a.shape[1]} bytes per stream: interleaved I, Q pairs")
-        a = np.ascontiguousarray(a)
-        n, most = a.shape[1] // per, self.max_host_samples // self.streams
-        for k in range(0, n, most):
-            m = min(most, n - k)
-            nat.check(nat.lib.tdsa_pstat_process(self._h, fmt, C.c_void_p(a.ctypes.data + k * per * a.itemsize), m, n))
-
-    def process_device(self, engine: Optional[SpectrumEngine], ptr: int, n: int, stride: Optional[int] = None,
-                       in_format: int = nat.IN_C64) -> None:
-        """n samples per stream already in device memory, stream c at ptr + c * stride samples (default: n), on
-        `engine`'s stream behind its work (None: the handle's own).  Does not wait: read() does."""
-        n = int(n)
-        stride = n if stride is None else int(stride)
-        if in_format not in (nat.IN_I8, nat.IN_U8, nat.IN_C64):
-            raise ValueError(f"in_format={in_format}: IN_I8, IN_U8 or IN_C64")
-        if n < 0:
-            raise ValueError(f"n={n}")
-        if not ptr:
-            raise ValueError("null pointer")
-        unit = 8 if in_format == nat.IN_C64 else 2
-        if int(ptr) % unit:
-            raise ValueError(f"samples pointer must be aligned to one sample ({unit} bytes)")
-        if self.streams > 1 and stride < n:
-            raise ValueError(f"stride={stride}: below the call's {n} samples per stream")
-        if engine is not None:
-            check_same_device(engine.device, self.device)
-        nat.check(nat.lib.tdsa_pstat_process_dev(self._h, engine._h if engine is not None else None, in_format,
-                                                 C.c_void_p(int(ptr)), n, stride))
 
     def read(self, streams=None) -> PowerStatistics:
         """Waits for the calls so far and reads the state of all streams (None), of one (an int) or of a range."""

@@ -17,8 +17,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import SpectrumEngine
-from .zoom import check_same_device
+from ._inputs import _IqStreams
 
 MAX_STREAMS = 256
 MAX_RECORDS = 1 << 22
@@ -31,7 +30,6 @@ COUNTS = ("n_total", "n_on", "n_pulses", "n_short", "n_lost", "n_nan")
 SUMMARY = np.dtype([(f, np.uint64) for f in COUNTS] + [("open_toa", np.int64), ("open_width", np.int64),
                                                         ("open", np.int32), ("reserved", np.int32)])
 assert RECORD.itemsize == 64 == C.sizeof(nat.PulseRecord) and SUMMARY.itemsize == 72 == C.sizeof(nat.PulseSummary)
-_FORMATS = {np.dtype(np.int8): nat.IN_I8, np.dtype(np.uint8): nat.IN_U8, np.dtype(np.complex64): nat.IN_C64}
 
 
 def levels_from_db(on_db: float, hysteresis_db: float = 0.0) -> Tuple[float, float]:
@@ -125,7 +123,7 @@ class PulseTrain:
         return int(self.summary["open_toa"]), int(self.summary["open_width"])
 
 
-class PulseAnalyzer(nat._Handle, nat._Timer):
+class PulseAnalyzer(_IqStreams, nat._Handle, nat._Timer):
     """Pulse descriptors of `streams` IQ streams (1 .. 256), up to `capacity` stored pulses each (streams * capacity
     <= 2^22).
 
@@ -135,6 +133,7 @@ class PulseAnalyzer(nat._Handle, nat._Timer):
     until reset() or configure()."""
     _destroy = "tdsa_pulse_destroy"
     _timer = ("tdsa_pulse_timer_begin", "tdsa_pulse_timer_end")
+    _process = ("tdsa_pulse_process", "tdsa_pulse_process_dev")
 
     def __init__(self, streams: int = 1, capacity: int = 4096, device: int = 0, max_host_samples: Optional[int] = None):
         self.streams, self.capacity = int(streams), int(capacity)
@@ -142,11 +141,7 @@ class PulseAnalyzer(nat._Handle, nat._Timer):
             raise ValueError(f"streams={streams}: 1 .. {MAX_STREAMS}")
         if self.capacity < 1 or self.streams * self.capacity > MAX_RECORDS:
             raise ValueError(f"capacity={capacity}: at least 1, streams * capacity at most {MAX_RECORDS}")
-        if max_host_samples is None:
-            max_host_samples = max(1 << 21, self.streams)      # 16 MiB of pinned staging
-        self.max_host_samples = int(max_host_samples)
-        if self.max_host_samples < self.streams:
-            raise ValueError(f"max_host_samples={max_host_samples}: at least one sample per stream ({self.streams})")
+        self._stage(max_host_samples)
         self.device = int(device)
         self.on_level, self.off_level, self.min_width = 1.0, 1.0, 1
         self._h = C.c_void_p()
@@ -161,51 +156,6 @@ class PulseAnalyzer(nat._Handle, nat._Timer):
 
     def reset(self) -> None:
         nat.check(nat.lib.tdsa_pulse_reset(self._h))
-
-    def process(self, iq) -> None:
-        """Samples in host memory.  The dtype names the format: int8 or uint8 (interleaved I, Q: a last axis of even
-        length) or complex64.  One stream: a 1-D array; more: [streams][...].  A block above the staging goes in pieces,
-        which changes no integer of the result."""
-        a = np.asarray(iq)
-        if a.dtype.kind == "c":
-            a = a.astype(np.complex64, copy=False)
-        fmt = _FORMATS.get(a.dtype)
-        if fmt is None:
-            raise ValueError(f"samples of dtype {a.dtype}: int8 or uint8 (interleaved I, Q) or complex64")
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim != 2 or a.shape[0] != self.streams:
-            raise ValueError(f"samples of shape {np.shape(iq)}: [{self.streams}][n], or [n] for one stream")
-        per = 1 if fmt == nat.IN_C64 else 2
-        if a.shape[1] % per:
-            raise ValueError(f"{a.shape[1]} bytes per stream: interleaved I, Q pairs")
-        a = np.ascontiguousarray(a)
-        n, most = a.shape[1] // per, self.max_host_samples // self.streams
-        for k in range(0, n, most):
-            m = min(most, n - k)
-            nat.check(nat.lib.tdsa_pulse_process(self._h, fmt, C.c_void_p(a.ctypes.data + k * per * a.itemsize), m, n))
-
-    def process_device(self, engine: Optional[SpectrumEngine], ptr: int, n: int, stride: Optional[int] = None,
-                       in_format: int = nat.IN_C64) -> None:
-        """n samples per stream already in device memory, stream c at ptr + c * stride samples (default: n), on
-        `engine`'s stream behind its work (None: the handle's own).  Does not wait: read() does."""
-        n = int(n)
-        stride = n if stride is None else int(stride)
-        if in_format not in (nat.IN_I8, nat.IN_U8, nat.IN_C64):
-            raise ValueError(f"in_format={in_format}: IN_I8, IN_U8 or IN_C64")
-        if n < 0:
-            raise ValueError(f"n={n}")
-        if not ptr:
-            raise ValueError("null pointer")
-        unit = 8 if in_format == nat.IN_C64 else 2
-        if int(ptr) % unit:
-            raise ValueError(f"samples pointer must be aligned to one sample ({unit} bytes)")
-        if self.streams > 1 and stride < n:
-            raise ValueError(f"stride={stride}: below the call's {n} samples per stream")
-        if engine is not None:
-            check_same_device(engine.device, self.device)
-        nat.check(nat.lib.tdsa_pulse_process_dev(self._h, engine._h if engine is not None else None, in_format,
-                                                 C.c_void_p(int(ptr)), n, stride))
 
     def read_summaries(self) -> np.ndarray:
         """Waits for the calls so far; [streams] of SUMMARY."""
