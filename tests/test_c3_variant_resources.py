@@ -9,7 +9,7 @@ import shutil
 
 import pytest
 
-from kernel_build import CSRC, FRAME_SOURCE, HIPCC, ROOT, compile_kernels, flags, makefile
+from kernel_build import CSRC, FRAME_SOURCE, HIPCC, ROOT, compile_kernels, cross_compiled, flags, makefile, no_scratch_no_spills
 
 VARIANT_SOURCE = "tdsa_spectrum_c3_inst.hip"
 VARIANTS = {hold: f"_ZN4tdsa15spectrum_kernelILi14ELb0ELi{16 | hold}ELi0EEEvNS_10SpecParamsE" for hold in (0, 1)}
@@ -17,10 +17,7 @@ VARIANTS = {hold: f"_ZN4tdsa15spectrum_kernelILi14ELb0ELi{16 | hold}ELi0EEEvNS_1
 
 @pytest.fixture(scope="module")
 def variant(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("c3") / "c3.s")
-    return compile_kernels(VARIANT_SOURCE, out), open(out).read()
+    return cross_compiled(tmp_path_factory, VARIANT_SOURCE, listing=True)
 
 
 @pytest.mark.parametrize("hold", [0, 1])
@@ -29,8 +26,7 @@ def test_variant_fits_four_waves_without_scratch(variant, hold):
     reports, _ = variant
     assert sorted(reports) == sorted(VARIANTS.values()), sorted(reports)
     k = reports[VARIANTS[hold]]
-    assert int(k["ScratchSize [bytes/lane]"]) == 0, k
-    assert int(k["VGPRs Spill"]) == 0 and int(k["SGPRs Spill"]) == 0, k
+    no_scratch_no_spills(k)
     assert int(k["VGPRs"]) <= 128, k
     assert int(k["Occupancy [waves/SIMD]"]) == 4, k
 

@@ -1,31 +1,23 @@
 """tdsa_chan.hip cross-compiled for gfx950 (no GPU): every kernel of the channelizer is free of scratch and of spilled
 registers, its static LDS is what the launcher budgets for, and the dynamic LDS the launcher asks for stays within a
 CU's 160 KiB for every shape the library accepts."""
+import functools
 import os
-import re
-import shutil
 
 import pytest
 
-from kernel_build import CSRC, HIPCC, compile_kernels, makefile
+from kernel_build import CSRC, cross_compiled, header_const, in_makefile, no_scratch_no_spills
 
 KERNELS = {"chan_bank_kernel": 2, "chan_history_kernel": 1}      # name -> instantiations (oversampling 1 and 2)
 
 
-def _const(name):
-    m = re.search(r"constexpr int %s = ([^;]+);" % name, open(os.path.join(CSRC, "tdsa_chan.hpp")).read())
-    return int(eval(m.group(1)))
+_const = functools.partial(header_const, "tdsa_chan.hpp")
 
 
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    mk = makefile()
-    assert "$(B)/tdsa_chan.o" in mk and re.search(r"^CAPI\s*=.*\bchan\b", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_chan\.hpp\b", mk, re.M)
-    asm = str(tmp_path_factory.mktemp("chan") / "tdsa_chan.s")
-    return compile_kernels("tdsa_chan.hip", asm), open(asm).read()
+    in_makefile("chan", ["tdsa_chan.hpp"])
+    return cross_compiled(tmp_path_factory, "tdsa_chan.hip", listing=True)
 
 
 def test_chan_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(compiled):
@@ -36,9 +28,7 @@ def test_chan_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(comp
         assert len(found) == count, (name, sorted(kernels))
         for k in found:
             print(k, kernels[k])
-            assert kernels[k]["ScratchSize [bytes/lane]"] == "0", (k, kernels[k])
-            assert kernels[k].get("VGPRs Spill", "0") == "0", (k, kernels[k])
-            assert kernels[k].get("SGPRs Spill", "0") == "0", (k, kernels[k])
+            no_scratch_no_spills(kernels[k])
             assert int(kernels[k]["LDS Size [bytes/block]"]) <= _const("kChanStaticLdsBytes"), (k, kernels[k])
             assert int(kernels[k]["VGPRs"]) <= 128, (k, kernels[k])      # 256 threads: four workgroups fit a CU's registers
 

@@ -2,30 +2,23 @@
 kernel instantiations exist, none uses scratch or spills a register, VGPRs stay within 128, the static LDS is what the
 header budgets for, and the dynamic LDS the launcher asks for stays within a CU's 160 KiB for every (R, T) the library
 accepts."""
+import functools
 import os
-import re
-import shutil
 
 import pytest
 
-from kernel_build import CSRC, HIPCC, compile_kernels, makefile
+from kernel_build import CSRC, cross_compiled, header_const, in_makefile, no_scratch_no_spills
 
 KERNELS = {"demod_audio_kernel": 2, "demod_history_kernel": 2, "demod_post_kernel": 1}     # name -> instantiations (FM, AM)
 
 
-def _const(name):
-    m = re.search(r"constexpr int %s = ([^;]+);" % name, open(os.path.join(CSRC, "tdsa_demod.hpp")).read())
-    return int(eval(m.group(1)))
+_const = functools.partial(header_const, "tdsa_demod.hpp")
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    mk = makefile()
-    assert "$(B)/tdsa_demod.o" in mk and re.search(r"^CAPI\s*=.*\bdemod\b", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_demod\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_demod_math\.hpp\b", mk, re.M)
-    return compile_kernels("tdsa_demod.hip", str(tmp_path_factory.mktemp("demod") / "tdsa_demod.o"))
+    in_makefile("demod", ["tdsa_demod.hpp", "tdsa_demod_math.hpp"])
+    return cross_compiled(tmp_path_factory, "tdsa_demod.hip")
 
 
 def test_demod_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(kernels):
@@ -35,9 +28,7 @@ def test_demod_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(ker
         assert len(found) == count, (name, sorted(kernels))
         for k in found:
             print(k, kernels[k])
-            assert kernels[k]["ScratchSize [bytes/lane]"] == "0", (k, kernels[k])
-            assert kernels[k].get("VGPRs Spill", "0") == "0", (k, kernels[k])
-            assert kernels[k].get("SGPRs Spill", "0") == "0", (k, kernels[k])
+            no_scratch_no_spills(kernels[k])
             assert int(kernels[k]["LDS Size [bytes/block]"]) <= _const("kDemodStaticLdsBytes"), (k, kernels[k])
             assert int(kernels[k]["VGPRs"]) <= 128, (k, kernels[k])      # 256 threads: four workgroups fit a CU's registers
 

@@ -1,12 +1,9 @@
 """tdsa_history.hip cross-compiled for gfx950 (no GPU): every kernel of the 3-D history views is free of scratch and of
 spilled registers, the translation unit is built with -ffp-contract=off, its divisions are the IEEE sequences, and its
 wide stores are the global stores the compiler pads on gfx950, not buffer stores with a register offset."""
-import re
-import shutil
-
 import pytest
 
-from kernel_build import HIPCC, compile_kernels, flags, makefile
+from kernel_build import cross_compiled, in_makefile, no_scratch_no_spills
 
 KERNELS = {"hist_push_kernel": 2, "hist_reduce_kernel": 1, "hist_ribbon_kernel": 2, "hist_lines_kernel": 2,
            "hist_surface_kernel": 2}      # name -> instantiations (16-byte and one-bin lanes)
@@ -14,16 +11,9 @@ KERNELS = {"hist_push_kernel": 2, "hist_reduce_kernel": 1, "hist_ribbon_kernel":
 
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    mk = makefile()
-    assert "$(B)/tdsa_history.o" in mk and re.search(r"^CAPI\s*=.*\bhistory\b", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_history\.hpp\b", mk, re.M)
-    assert re.search(r"^\$\(B\)/tdsa_history\.o:\s*EXTRA\s*\+=\s*-ffp-contract=off\s*$", mk, re.M), \
-        "the history views restate numpy operation by operation: no contraction into FMA"
-    assert "-ffp-contract=off" in flags("tdsa_history.hip")
-    asm = str(tmp_path_factory.mktemp("history") / "tdsa_history.s")
-    return compile_kernels("tdsa_history.hip", asm), open(asm).read()
+    # the history views restate numpy operation by operation: no contraction into FMA
+    in_makefile("history", ["tdsa_history.hpp"], own_flags="-ffp-contract=off")
+    return cross_compiled(tmp_path_factory, "tdsa_history.hip", listing=True)
 
 
 def test_history_kernels_have_no_scratch_and_no_spills(compiled):
@@ -33,9 +23,7 @@ def test_history_kernels_have_no_scratch_and_no_spills(compiled):
         assert len(found) == count, (name, sorted(kernels))
         for k in found:
             print(k, kernels[k])
-            assert kernels[k]["ScratchSize [bytes/lane]"] == "0", (k, kernels[k])
-            assert kernels[k].get("VGPRs Spill", "0") == "0", (k, kernels[k])
-            assert kernels[k].get("SGPRs Spill", "0") == "0", (k, kernels[k])
+            no_scratch_no_spills(kernels[k])
             assert kernels[k]["LDS Size [bytes/block]"] == "0", (k, kernels[k])      # streaming passes and shuffles
             assert int(kernels[k]["VGPRs"]) <= 64, (k, kernels[k])                     # eight waves per SIMD stay possible
 

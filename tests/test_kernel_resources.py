@@ -12,7 +12,7 @@ import shutil
 
 import pytest
 
-from kernel_build import FRAME_SIZES as SIZES, FRAME_SOURCE, HIPCC, compile_kernels
+from kernel_build import FRAME_SIZES as SIZES, FRAME_SOURCE, HIPCC, compile_kernels, no_scratch_no_spills
 
 
 def _report(log2n, tmp):
@@ -135,8 +135,8 @@ def test_long_frame_column_pass_keeps_three_waves_and_no_vmem_wait_between_its_s
         for dc in (0, 1):
             name = f"_ZN4tdsa15big_cols_kernelILi6ELb{flat}ELb{dc}ELb0EEEvNS_13BigColsParamsE"
             rep = reports[name]
-            assert int(rep["ScratchSize [bytes/lane]"]) == 0 and int(rep["VGPRs"]) <= 168 and int(rep["Occupancy [waves/SIMD]"]) >= 3, rep
-            assert int(rep["SGPRs Spill"]) == 0, rep
+            no_scratch_no_spills(rep)
+            assert int(rep["VGPRs"]) <= 168 and int(rep["Occupancy [waves/SIMD]"]) >= 3, rep
             body = [ln for ln in body_of(name) if ln]
             stores = [i for i, ln in enumerate(body) if ln.startswith("buffer_store_dwordx4")]
             assert len(stores) == 32, len(stores)
@@ -152,8 +152,7 @@ def test_long_frame_column_pass_keeps_three_waves_and_no_vmem_wait_between_its_s
     # the long chirp-z frames' instantiations (raw frames in, times window x chirp; power / dB rows out): no scratch
     for name in ("_ZN4tdsa15big_cols_kernelILi6ELb1ELb0ELb1EEEvNS_13BigColsParamsE",
                  "_ZN4tdsa19big_cols_out_kernelILi6EEEvNS_16BigColsOutParamsE"):
-        rep = reports[name]
-        assert int(rep["ScratchSize [bytes/lane]"]) == 0 and int(rep["SGPRs Spill"]) == 0, (name, rep)
+        no_scratch_no_spills(reports[name])
 
     # row pass (big_rows_kernel): 128 VGPRs / 4 waves per SIMD without scratch, and the fetch of the next row spread over
     # the row's work - eight 16-byte loads, one at a time, each behind a stretch of arithmetic (bursts cost 13 %)

@@ -2,31 +2,22 @@
 load paths exist, use no scratch and spill no register, VGPRs stay within 128, and the LDS of a workgroup - the static
 part the compiler reports plus the padded row the launcher asks for - stays within 80 KiB, so that two workgroups fit a
 CU's 160 KiB."""
+import functools
 import os
-import re
-import shutil
 
 import pytest
 
-from kernel_build import CSRC, HIPCC, compile_kernels, makefile
+from kernel_build import CSRC, cross_compiled, header_const, in_makefile, no_scratch_no_spills
 from topdogspectrumanalyser_amd import measure as ms
 
 
-def _const(name):
-    m = re.search(r"constexpr int %s = ([^;]+);" % name, open(os.path.join(CSRC, "tdsa_meas.hpp")).read())
-    expr = re.sub(r"\bk\w+", lambda k: str(_const(k.group(0))), m.group(1))
-    return int(eval(expr))
+_const = functools.partial(header_const, "tdsa_meas.hpp")
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    mk = makefile()
-    assert "$(B)/tdsa_meas.o" in mk and re.search(r"^CAPI\s*=.*\bmeas\b", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_meas\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_wave\.hpp\b", mk, re.M)
-    assert not re.search(r"^\$\(B\)/tdsa_meas\.o:", mk, re.M)            # no flags of its own: the Makefile's
-    return compile_kernels("tdsa_meas.hip", str(tmp_path_factory.mktemp("meas") / "tdsa_meas.o"))
+    in_makefile("meas", ["tdsa_meas.hpp", "tdsa_wave.hpp"])      # no flags of its own: the Makefile's
+    return cross_compiled(tmp_path_factory, "tdsa_meas.hip")
 
 
 def test_meas_kernel_has_no_scratch_no_spills_and_fits_two_workgroups_per_cu(kernels):
@@ -36,8 +27,7 @@ def test_meas_kernel_has_no_scratch_no_spills_and_fits_two_workgroups_per_cu(ker
     for name in found:
         k = kernels[name]
         print(name, k)
-        assert k["ScratchSize [bytes/lane]"] == "0", k
-        assert k.get("VGPRs Spill", "0") == "0" and k.get("SGPRs Spill", "0") == "0", k
+        no_scratch_no_spills(k)
         assert int(k["VGPRs"]) <= 128, k
         assert int(k["LDS Size [bytes/block]"]) <= _const("kMeasStaticLdsBytes"), k
         assert int(k["LDS Size [bytes/block]"]) + row_bytes <= 80 * 1024, k

@@ -2,33 +2,23 @@
 at most two instantiations, uses no scratch and spills no register, VGPRs stay within 128, and the LDS of a workgroup
 stays within 40 KiB, so that four workgroups fit a CU's 160 KiB.  The Makefile builds the unit without fused
 multiply-add, and the header's constants are those powerstats.py and the contract promise."""
+import functools
 import os
-import re
-import shutil
 
 import pytest
 
 import pstat_contract as pc
-from kernel_build import CSRC, HIPCC, compile_kernels, flags, makefile
+from kernel_build import CSRC, cross_compiled, flags, header_const, in_makefile, no_scratch_no_spills
+from kernel_build import public_define as _define
 from topdogspectrumanalyser_amd import powerstats as ps
 
 
-def _const(name, header="tdsa_pstat.hpp"):
-    m = re.search(r"constexpr (?:int|long long) %s = ([^;]+);" % name, open(os.path.join(CSRC, header)).read())
-    expr = re.sub(r"\bk\w+", lambda k: str(_const(k.group(0))), m.group(1)).replace("1ll", "1")
-    return int(eval(expr))
-
-
-def _define(name):
-    m = re.search(r"^#define %s \(?(-?\d+)\)?$" % name, open(os.path.join(CSRC, "..", "..", "include", "tdsa_hip.h")).read(), re.M)
-    return int(m.group(1))
+_const = functools.partial(header_const, "tdsa_pstat.hpp")
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    return compile_kernels("tdsa_pstat.hip", str(tmp_path_factory.mktemp("pstat") / "tdsa_pstat.o"))
+    return cross_compiled(tmp_path_factory, "tdsa_pstat.hip")
 
 
 def test_pstat_kernel_has_no_scratch_no_spills_and_fits_four_workgroups_per_cu(kernels):
@@ -37,17 +27,13 @@ def test_pstat_kernel_has_no_scratch_no_spills_and_fits_four_workgroups_per_cu(k
     for name in found:
         k = kernels[name]
         print(name, k)
-        assert k["ScratchSize [bytes/lane]"] == "0", k
-        assert k.get("VGPRs Spill", "0") == "0" and k.get("SGPRs Spill", "0") == "0", k
+        no_scratch_no_spills(k)
         assert int(k["VGPRs"]) <= 128, k
         assert int(k["LDS Size [bytes/block]"]) == _const("kPstatLdsBytes") <= 40 * 1024, k      # no dynamic LDS is asked for
 
 
 def test_the_makefile_builds_the_unit_without_fused_multiply_add():
-    mk = makefile()
-    assert "$(B)/tdsa_pstat.o" in mk and re.search(r"^CAPI\s*=.*\bpstat\b", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_pstat\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_unpack\.hpp\b", mk, re.M)
-    assert re.search(r"^\$\(B\)/tdsa_pstat\.o:\s*EXTRA\s*\+=\s*-ffp-contract=off$", mk, re.M)
+    in_makefile("pstat", ["tdsa_pstat.hpp", "tdsa_unpack.hpp"], own_flags="-ffp-contract=off")
     fl = flags("tdsa_pstat.hip")
     assert "-ffp-contract=off" in fl and "--offload-arch=gfx950" in fl
     assert not [f for f in fl if "flush-denormals" in f or "fast-math" in f or "denormal-fp-math" in f], fl

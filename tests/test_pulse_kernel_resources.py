@@ -2,33 +2,24 @@
 use no scratch and spill no register, their VGPRs and LDS stay within the budget tdsa_pulse.hpp states, and the
 workgroups per CU the header promises follow from them.  The Makefile builds the unit without fused multiply-add, the
 header's constants are those pulses.py and include/tdsa_hip.h promise, and no kernel is launched cooperatively."""
+import functools
 import os
 import re
-import shutil
 
 import pytest
 
 import pulse_contract as pc
-from kernel_build import CSRC, HIPCC, compile_kernels, flags, makefile
+from kernel_build import CSRC, cross_compiled, flags, header_const, in_makefile, no_scratch_no_spills
+from kernel_build import public_define as _define
 from topdogspectrumanalyser_amd import pulses as pu
 
 
-def _const(name, header="tdsa_pulse.hpp"):
-    m = re.search(r"constexpr (?:int|long long) %s = ([^;]+);" % name, open(os.path.join(CSRC, header)).read())
-    expr = re.sub(r"\bk\w+", lambda k: str(_const(k.group(0))), m.group(1)).replace("1ll", "1")
-    return int(eval(expr))
-
-
-def _define(name):
-    m = re.search(r"^#define %s \(?(-?\d+)u?\)?$" % name, open(os.path.join(CSRC, "..", "..", "include", "tdsa_hip.h")).read(), re.M)
-    return int(m.group(1))
+_const = functools.partial(header_const, "tdsa_pulse.hpp")
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    if not shutil.which(HIPCC):
-        pytest.skip("hipcc not available")
-    return compile_kernels("tdsa_pulse.hip", str(tmp_path_factory.mktemp("pulse") / "tdsa_pulse.o"))
+    return cross_compiled(tmp_path_factory, "tdsa_pulse.hip")
 
 
 def test_the_kernels_have_no_scratch_no_spills_and_stay_within_the_stated_budget(kernels):
@@ -41,8 +32,7 @@ def test_the_kernels_have_no_scratch_no_spills_and_stay_within_the_stated_budget
                                  (stitch[0], "kPulseVgprBudget", "kPulseWorkgroupsPerCu")):
         k = kernels[name]
         print(name, k)
-        assert k["ScratchSize [bytes/lane]"] == "0", k
-        assert k.get("VGPRs Spill", "0") == "0" and k.get("SGPRs Spill", "0") == "0", k
+        no_scratch_no_spills(k)
         assert int(k["VGPRs"]) <= _const(budget), k
         assert int(k["LDS Size [bytes/block]"]) <= _const("kPulseLdsBudget"), k             # no dynamic LDS is asked for
         # workgroups per CU: waves per SIMD by registers, times the SIMDs, over the waves of a workgroup; LDS allows more
@@ -51,11 +41,7 @@ def test_the_kernels_have_no_scratch_no_spills_and_stay_within_the_stated_budget
 
 
 def test_the_makefile_builds_the_unit_without_fused_multiply_add():
-    mk = makefile()
-    assert "$(B)/tdsa_pulse.o" in mk and re.search(r"^CAPI\s*=.*\bpulse\b", mk, re.M)
-    assert re.search(r"^OBJS\s*=.*\$\(B\)/tdsa_pulse\.o", mk, re.M)
-    assert re.search(r"^HDRS\s*=.*\btdsa_pulse\.hpp\b", mk, re.M) and re.search(r"^HDRS\s*=.*\btdsa_wave\.hpp\b", mk, re.M)
-    assert re.search(r"^\$\(B\)/tdsa_pulse\.o:\s*EXTRA\s*\+=\s*-ffp-contract=off$", mk, re.M)
+    in_makefile("pulse", ["tdsa_pulse.hpp", "tdsa_wave.hpp"], own_flags="-ffp-contract=off")
     fl = flags("tdsa_pulse.hip")
     assert "-ffp-contract=off" in fl and "--offload-arch=gfx950" in fl
     assert not [f for f in fl if "flush-denormals" in f or "fast-math" in f or "denormal-fp-math" in f], fl

@@ -10,19 +10,19 @@ the default prototype (zoom.design_decimator(M), 34 taps per branch).
   spectra  ChannelSpectra end to end at M = 64, os = 2, nfft = 1024: the bank and all 64 x 610 frames in one launch
   diff     the largest |difference| between channel 5 and the DownConverter tuned to 5 fs / M, on the same block
 
-Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per figure: warm-up
-calls, then the median of `--reps` (at least 20) single calls, each between device events on the engine's stream the
-work is launched on.
+Every step runs in a child process of its own under a time limit; a step that fails ends the run with exit status 1
+(tools/stepbench.py).  Per figure: warm-up calls, then the median of `--reps` (at least 20) single
+calls, each between device events on the engine's stream the work is launched on.
 
-    python tools/chanbench.py [--out profiles/chanbench.txt] [--reps 20]
+    python tools/chanbench.py [--out profiles/chanbench.txt] [--reps 20] [--steps copy,bank_64_2]
 """
-import argparse
-import json
+import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+from stepbench import main, median_us, step_copy
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -30,19 +30,6 @@ sys.path.insert(0, ROOT)
 FS = 20e6
 N_SEC = 20_000_000
 SHAPES = [(M, os_) for M in (8, 64, 256) for os_ in (1, 2)]
-STEPS = ["copy"] + [f"bank_{M}_{os_}" for M, os_ in SHAPES] + ["spectra", "diff"]
-LIMIT_S = 240
-
-
-def median_us(eng, f, warm, reps):
-    for _ in range(warm):
-        f()
-    t = []
-    for _ in range(reps):
-        eng.timer_begin()
-        f()
-        t.append(eng.timer_end() * 1e3)
-    return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
 def capture(n):
@@ -50,26 +37,6 @@ def capture(n):
     rng = np.random.default_rng(4)
     iq = rng.integers(-128, 128, 2 * n).astype(np.int8)
     return iq, DeviceBuffer.of(iq)
-
-
-def step_copy(args):
-    import torch
-    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
-    y = torch.empty_like(x)
-    x.fill_(1.0)
-    for _ in range(3):
-        y.copy_(x)
-    t = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        y.copy_(x)
-        b.record()
-        b.synchronize()
-        t.append(a.elapsed_time(b) * 1e-3)
-    moved = 2 * x.numel() * 4
-    return dict(copy_bps=moved / float(np.median(t)), text=[
-        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
 
 
 def step_bank(args, M, os_):
@@ -133,57 +100,13 @@ def step_diff(args):
         f"largest |difference| {float(np.abs(y - z).max()):.3e}, largest |output| {scale:.3e}"])
 
 
-def run_step(args):
-    if args.step == "copy":
-        return step_copy(args)
-    if args.step == "spectra":
-        return step_spectra(args)
-    if args.step == "diff":
-        return step_diff(args)
-    _, M, os_ = args.step.split("_")
-    return step_bank(args, int(M), int(os_))
+def header(args):
+    return (f"polyphase channelizer on one C3 second ({N_SEC} int8 IQ samples in HBM, default prototype); every figure is "
+            f"the median of {args.reps} single calls after warm-up calls, between device events on the stream the work runs on")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warm", type=int, default=3)
-    ap.add_argument("--step", choices=STEPS, default=None)
-    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
-    args = ap.parse_args()
-    args.reps = max(args.reps, 20)
-    if args.step:
-        print("RESULT " + json.dumps(run_step(args)), flush=True)
-        return
-    lines = [f"polyphase channelizer on one C3 second ({N_SEC} int8 IQ samples in HBM, default prototype); every figure is "
-             f"the median of {args.reps} single calls after warm-up calls, between device events on the stream the work runs on"]
-    print(lines[0], flush=True)
-    copy_bps = 0.0
-    for step in STEPS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
-               "--copy-bps", repr(copy_bps)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
-            print(lines[-1], flush=True)
-            break
-        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-        if r.returncode != 0 or not res:
-            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
-            print(lines[-1], flush=True)
-            break
-        res = json.loads(res[-1][7:])
-        copy_bps = res.get("copy_bps", copy_bps)
-        for ln in res["text"]:
-            print(ln, flush=True)
-            lines.append(ln)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-
+STEPS = dict(copy=step_copy, **{f"bank_{M}_{os_}": functools.partial(step_bank, M=M, os_=os_) for M, os_ in SHAPES},
+             spectra=step_spectra, diff=step_diff)
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, header)

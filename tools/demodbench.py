@@ -9,16 +9,15 @@ the default audio filter (34 taps per phase) and 75 us de-emphasis, and AM at th
   split    the FM step again under `rocprofv3 --kernel-trace --stats`: the audio, post and history kernels separately
   numpy    for scale: the same three stages in float32 numpy on one host core, on 8 of the 128 channels, times 16
 
-Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per figure: warm-up
-calls, then the median of `--reps` (at least 20) single calls, each between device events on the engine's stream the
-work is launched on.
+Every step runs in a child process of its own under a time limit; a step that fails ends the run with exit status 1
+(tools/stepbench.py).  Per figure: warm-up calls, then the median of `--reps` (at least 20) single
+calls, each between device events on the engine's stream the work is launched on.
 
-    python tools/demodbench.py [--out profiles/demodbench.txt] [--reps 20]
+    python tools/demodbench.py [--out profiles/demodbench.txt] [--reps 20] [--steps copy,fm]
 """
-import argparse
 import csv
+import functools
 import glob
-import json
 import os
 import re
 import shutil
@@ -29,6 +28,8 @@ import time
 
 import numpy as np
 
+from stepbench import main, median_us, step_copy
+
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
@@ -36,45 +37,12 @@ FS = 20e6
 N_SEC = 20_000_000
 M, OS, R = 128, 2, 6
 TAU = 75e-6
-STEPS = ["copy", "fm", "am", "split", "numpy"]
-LIMIT_S = 240
-
-
-def median_us(eng, f, warm, reps):
-    for _ in range(warm):
-        f()
-    t = []
-    for _ in range(reps):
-        eng.timer_begin()
-        f()
-        t.append(eng.timer_end() * 1e3)
-    return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
 def capture(n):
     """Noise: an FM carrier per channel would cost minutes of host time, and the kernels' work does not depend on the data."""
     rng = np.random.default_rng(4)
     return rng.integers(-128, 128, 2 * n).astype(np.int8)
-
-
-def step_copy(args):
-    import torch
-    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
-    y = torch.empty_like(x)
-    x.fill_(1.0)
-    for _ in range(3):
-        y.copy_(x)
-    t = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        y.copy_(x)
-        b.record()
-        b.synchronize()
-        t.append(a.elapsed_time(b) * 1e-3)
-    moved = 2 * x.numel() * 4
-    return dict(copy_bps=moved / float(np.median(t)), text=[
-        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
 
 
 def step_demod(args, mode):
@@ -154,57 +122,14 @@ def step_numpy(args):
                       f"{dt * M / part:.1f} s for the second"])
 
 
-def run_step(args):
-    if args.step == "copy":
-        return step_copy(args)
-    if args.step == "split":
-        return step_split(args)
-    if args.step == "numpy":
-        return step_numpy(args)
-    return step_demod(args, args.step)
+def header(args):
+    return (f"analog demodulator on one C3 second through Channelizer({M}, os={OS}): {M} channels at {FS * OS / M / 1e3:.1f} kHz "
+            f"in HBM; every device figure is the median of {args.reps} single calls after warm-up calls, between device events on "
+            f"the stream the work runs on")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warm", type=int, default=3)
-    ap.add_argument("--step", choices=STEPS, default=None)
-    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
-    args = ap.parse_args()
-    args.reps = max(args.reps, 20)
-    if args.step:
-        print("RESULT " + json.dumps(run_step(args)), flush=True)
-        return
-    lines = [f"analog demodulator on one C3 second through Channelizer({M}, os={OS}): {M} channels at {FS * OS / M / 1e3:.1f} kHz "
-             f"in HBM; every device figure is the median of {args.reps} single calls after warm-up calls, between device events on "
-             f"the stream the work runs on"]
-    print(lines[0], flush=True)
-    copy_bps = 0.0
-    for step in STEPS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
-               "--copy-bps", repr(copy_bps)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
-            print(lines[-1], flush=True)
-            break
-        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-        if r.returncode != 0 or not res:
-            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
-            print(lines[-1], flush=True)
-            break
-        res = json.loads(res[-1][7:])
-        copy_bps = res.get("copy_bps", copy_bps)
-        for ln in res["text"]:
-            print(ln, flush=True)
-            lines.append(ln)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-
+STEPS = dict(copy=step_copy, fm=functools.partial(step_demod, mode="fm"), am=functools.partial(step_demod, mode="am"),
+             split=step_split, numpy=step_numpy)
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, header)

@@ -9,38 +9,24 @@
   scale    tdsa_rows_marker_peaks and tdsa_rows_stats on the rows of `second`, for scale (their code is not touched by
            the detector), between events on the plan's stream
 
-Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per device figure:
-warm-up calls, then the median of `--reps` (at least 20) single calls, each between device events on the handle's
-stream; a call ends when the records are in host memory, so the figure includes that copy and wait.  No time is fixed in
-advance: each figure stands next to its memory floor.
+Every step runs in a child process of its own under a time limit; a step that fails ends the run with exit status 1
+(tools/stepbench.py).  Per device figure: warm-up calls, then the median of `--reps` (at least 20)
+single calls, each between device events on the handle's stream; a call ends when the records are in host memory, so the
+figure includes that copy and wait.  No time is fixed in advance: each figure stands next to its memory floor.
 
-    python tools/detectbench.py [--out profiles/detectbench.txt] [--reps 20]
+    python tools/detectbench.py [--out profiles/detectbench.txt] [--reps 20] [--steps copy,second]
 """
-import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+from stepbench import main, median_us, step_copy
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
 N_ROWS, N_BINS = 2440, 16384
-STEPS = ["copy", "second", "worst", "scale"]
-LIMIT_S = 240
-
-
-def median_us(h, f, warm, reps):
-    for _ in range(warm):
-        f()
-    t = []
-    for _ in range(reps):
-        h.timer_begin()
-        f()
-        t.append(h.timer_end() * 1e3)
-    return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
 def capture(kind):
@@ -63,26 +49,6 @@ def capture(kind):
 
 def floor_us(copy_bps):
     return 4.0 * N_ROWS * N_BINS / copy_bps * 1e6 if copy_bps else float("nan")
-
-
-def step_copy(args):
-    import torch
-    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
-    y = torch.empty_like(x)
-    x.fill_(1.0)
-    for _ in range(3):
-        y.copy_(x)
-    t = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        y.copy_(x)
-        b.record()
-        b.synchronize()
-        t.append(a.elapsed_time(b) * 1e-3)
-    moved = 2 * x.numel() * 4
-    return dict(copy_bps=moved / float(np.median(t)), text=[
-        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
 
 
 def _detect(args, kind, **kw):
@@ -131,50 +97,12 @@ def step_scale(args):
         f"the same memory floor, {fl:7.1f} us"])
 
 
-def run_step(args):
-    return dict(copy=step_copy, second=step_second, worst=step_worst, scale=step_scale)[args.step](args)
+def header(args):
+    return (f"signal detection (tdsa_detect_*): every device figure is the median of {args.reps} single calls after warm-up "
+            f"calls, between device events on the handle's stream, records read back included")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warm", type=int, default=3)
-    ap.add_argument("--step", choices=STEPS, default=None)
-    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
-    args = ap.parse_args()
-    args.reps = max(args.reps, 20)
-    if args.step:
-        print("RESULT " + json.dumps(run_step(args)), flush=True)
-        return
-    lines = [f"signal detection (tdsa_detect_*): every device figure is the median of {args.reps} single calls after warm-up "
-             f"calls, between device events on the handle's stream, records read back included"]
-    print(lines[0], flush=True)
-    copy_bps = 0.0
-    for step in STEPS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
-               "--copy-bps", repr(copy_bps)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
-            print(lines[-1], flush=True)
-            break
-        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-        if r.returncode != 0 or not res:
-            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
-            print(lines[-1], flush=True)
-            break
-        res = json.loads(res[-1][7:])
-        copy_bps = res.get("copy_bps", copy_bps)
-        for ln in res["text"]:
-            print(ln, flush=True)
-            lines.append(ln)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-
+STEPS = dict(copy=step_copy, second=step_second, worst=step_worst, scale=step_scale)
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, header)

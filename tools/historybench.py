@@ -8,19 +8,20 @@
            memory (with the read-back), with the bytes each moves and the bytes that cross to the host
   host     the numpy restatement of the same tick (tests/history_contract.py) on the host's CPU, for scale
 
-Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per step: warm-up
-calls, then the median of `--reps` (at least 20) single calls, each between device events on the handle's stream.
+Every step runs in a child process of its own under a time limit; a step that fails ends the run with exit status 1
+(tools/stepbench.py).  Per step: warm-up calls, then the median of `--reps` (at least 20) single
+calls, each between device events on the handle's stream.
 
-    python tools/historybench.py [--out profiles/historybench.txt] [--reps 20]
+    python tools/historybench.py [--out profiles/historybench.txt] [--reps 20] [--steps copy,ribbon]
 """
-import argparse
-import json
+import functools
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
+
+from stepbench import main, median_us, step_copy
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -28,7 +29,6 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 N = 16384
 PUSH_ROWS = 256
-STEPS = ("copy", "push", "ribbon", "lines", "surface", "host")
 LIMIT_S = {"copy": 120, "push": 120, "ribbon": 180, "lines": 240, "surface": 180, "host": 300}
 
 
@@ -36,42 +36,11 @@ def rows_db(rng, n_rows):
     return rng.normal(-80.0, 12.0, size=(n_rows, N)).astype(np.float32)
 
 
-def median_us(h, f, warm, reps):
-    for _ in range(warm):
-        f()
-    t = []
-    for _ in range(reps):
-        h.timer_begin()
-        f()
-        t.append(h.timer_end() * 1e3)
-    return float(np.median(t)), float(np.min(t)), float(np.max(t))
-
-
 def fill(h, rng, n_rows):
     from topdogspectrumanalyser_amd import DeviceBuffer
     with DeviceBuffer.of(rows_db(rng, n_rows)) as d:
         h.push_rows(None, d.ptr, n_rows)
         h.lines(0, 1) if h.kind == "heights" else h.surface(columns=1)
-
-
-def step_copy(args):
-    import torch
-    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
-    y = torch.empty_like(x)
-    x.fill_(1.0)
-    for _ in range(3):
-        y.copy_(x)
-    t = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        y.copy_(x)
-        b.record()
-        b.synchronize()
-        t.append(a.elapsed_time(b) * 1e-3)
-    moved = 2 * x.numel() * 4
-    return dict(copy_bps=moved / float(np.median(t)), text=[
-        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
 
 
 def step_push(args):
@@ -155,56 +124,13 @@ def step_host(args):
     return dict(text=text)
 
 
-def run_step(args):
-    if args.step == "copy":
-        return step_copy(args)
-    if args.step == "push":
-        return step_push(args)
-    if args.step == "host":
-        return step_host(args)
-    return view_step(args, args.step)
+def header(args):
+    return (f"3-D history views at n = {N} bins; every figure is the median of {args.reps} single calls after {args.warm} "
+            "warm-up calls, between device events on the handle's stream unless it says wall")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warm", type=int, default=3)
-    ap.add_argument("--step", choices=STEPS, default=None)
-    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
-    args = ap.parse_args()
-    args.reps = max(args.reps, 20)
-    if args.step:
-        print("RESULT " + json.dumps(run_step(args)), flush=True)
-        return
-    lines = [f"3-D history views at n = {N} bins; every figure is the median of {args.reps} single calls after {args.warm} "
-             "warm-up calls, between device events on the handle's stream unless it says wall"]
-    print(lines[0], flush=True)
-    copy_bps = 0.0
-    for step in STEPS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
-               "--copy-bps", repr(copy_bps)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S[step])
-        except subprocess.TimeoutExpired:
-            lines.append(f"{step}: no result within {LIMIT_S[step]} s; stopping")
-            print(lines[-1], flush=True)
-            break
-        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-        if r.returncode != 0 or not res:
-            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
-            print(lines[-1], flush=True)
-            break
-        res = json.loads(res[-1][7:])
-        copy_bps = res.get("copy_bps", copy_bps)
-        for ln in res["text"]:
-            print(ln, flush=True)
-            lines.append(ln)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-
+STEPS = dict(copy=step_copy, push=step_push,
+             **{name: functools.partial(view_step, name=name) for name in ("ribbon", "lines", "surface")}, host=step_host)
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, header, LIMIT_S)

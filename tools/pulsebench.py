@@ -9,21 +9,21 @@
   dense     the pathological stream: every other sample on, 10e6 pulses of one sample (capacity 4096: the rest is counted)
   streams   256 channelizer streams of a C3 second: [256][78125] complex64, stride 78125 + 3, each with its own train
 
-Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per device figure:
-warm-up calls, then the median of `--reps` (at least 20) single calls, each between device events on the handle's
-stream.  process_device does not wait, so a figure is the device time of the passes alone.  The three kernels' shares
-are timed the same way with the other two masked out (tdsa_pulse_debug_limits); they read what the last whole call
-left.  No time is fixed in advance: each figure stands next to its memory floor and the power statistics' time.
+Every step runs in a child process of its own under a time limit; a step that fails ends the run with exit status 1
+(tools/stepbench.py).  Per device figure: warm-up calls, then the median of `--reps` (at least 20)
+single calls, each between device events on the handle's stream.  process_device does not wait, so a figure is the
+device time of the passes alone.  The three kernels' shares are timed the same way with the other two masked out
+(tdsa_pulse_debug_limits); they read what the last whole call left.  No time is fixed in advance: each figure stands
+next to its memory floor and the power statistics' time.
 
     python tools/pulsebench.py [--out profiles/pulsebench.txt] [--reps 20] [--steps int8,dense]
 """
-import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+from stepbench import main, median_us, step_copy
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -31,20 +31,7 @@ sys.path.insert(0, ROOT)
 N = 20_000_000                    # a C3 second
 PERIOD, WIDTH = 10_000, 1_000
 STREAMS, PER_STREAM, GAP = 256, N // 256, 3
-STEPS = ["copy", "int8", "c64", "dense", "streams"]
 ON, OFF = 0.2, 0.05
-LIMIT_S = 240
-
-
-def median_us(h, f, warm, reps):
-    for _ in range(warm):
-        f()
-    t = []
-    for _ in range(reps):
-        h.timer_begin()
-        f()
-        t.append(h.timer_end() * 1e3)
-    return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
 def train_c64(shape, period=PERIOD, width=WIDTH):
@@ -68,26 +55,6 @@ def train_i8(n=N):
     out[0::2] = np.clip(np.rint(x.real * 128.0), -128, 127)
     out[1::2] = np.clip(np.rint(x.imag * 128.0), -128, 127)
     return out
-
-
-def step_copy(args):
-    import torch
-    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
-    y = torch.empty_like(x)
-    x.fill_(1.0)
-    for _ in range(3):
-        y.copy_(x)
-    t = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        y.copy_(x)
-        b.record()
-        b.synchronize()
-        t.append(a.elapsed_time(b) * 1e-3)
-    moved = 2 * x.numel() * 4
-    return dict(copy_bps=moved / float(np.median(t)), text=[
-        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
 
 
 def _figure(args, us, lo, hi, nbytes):
@@ -162,54 +129,12 @@ def step_streams(args):
                                   f"elements), a train of 10 % duty each, one call", 8 * STREAMS * PER_STREAM, res))
 
 
-def run_step(args):
-    return dict(copy=step_copy, int8=step_int8, c64=step_c64, dense=step_dense, streams=step_streams)[args.step](args)
+def header(args):
+    return (f"pulse analysis (tdsa_pulse_*): every device figure is the median of {args.reps} single calls after warm-up calls, "
+            f"between device events on the handle's stream; the records stay on the device.  on_level {ON}, off_level {OFF}, min_width 1")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warm", type=int, default=3)
-    ap.add_argument("--step", choices=STEPS, default=None)
-    ap.add_argument("--steps", default=",".join(STEPS), help="the steps to run, in the order above")
-    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
-    args = ap.parse_args()
-    args.reps = max(args.reps, 20)
-    if args.step:
-        print("RESULT " + json.dumps(run_step(args)), flush=True)
-        return
-    lines = [f"pulse analysis (tdsa_pulse_*): every device figure is the median of {args.reps} single calls after warm-up calls, "
-             f"between device events on the handle's stream; the records stay on the device.  on_level {ON}, off_level {OFF}, min_width 1"]
-    print(lines[0], flush=True)
-    copy_bps, failed = 0.0, False
-    for step in [st for st in STEPS if st in args.steps.split(",")]:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
-               "--copy-bps", repr(copy_bps)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
-            print(lines[-1], flush=True)
-            failed = True
-            break
-        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-        if r.returncode != 0 or not res:
-            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
-            print(lines[-1], flush=True)
-            failed = True
-            break
-        res = json.loads(res[-1][7:])
-        copy_bps = res.get("copy_bps", copy_bps)
-        for ln in res["text"]:
-            print(ln, flush=True)
-            lines.append(ln)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    sys.exit(1 if failed else 0)
-
+STEPS = dict(copy=step_copy, int8=step_int8, c64=step_c64, dense=step_dense, streams=step_streams)
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, header)

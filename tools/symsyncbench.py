@@ -9,20 +9,20 @@
            per sample and 8 K bytes written per segment at the copy rate
   numpy    for scale: the float64 contract (tests/symsync_contract.py) on the tick's segment on one host core
 
-Every step runs in a child process of its own under a time limit; a step that fails ends the run.  Per device figure:
-warm-up calls, then the median of `--reps` (at least 20) single calls, each between device events on the handle's
-stream; a call ends when the segments' records are in host memory, so the figure includes that copy and wait.
+Every step runs in a child process of its own under a time limit; a step that fails ends the run with exit status 1
+(tools/stepbench.py).  Per device figure: warm-up calls, then the median of `--reps` (at least 20)
+single calls, each between device events on the handle's stream; a call ends when the segments' records are in host
+memory, so the figure includes that copy and wait.
 
-    python tools/symsyncbench.py [--out profiles/symsyncbench.txt] [--reps 20]
+    python tools/symsyncbench.py [--out profiles/symsyncbench.txt] [--reps 20] [--steps copy,tick]
 """
-import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
+
+from stepbench import main, median_us, step_copy
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -32,19 +32,6 @@ TICK = 16384
 N_SEC = 20_000_000
 D = 2
 SEG = 4096
-STEPS = ["copy", "tick", "second", "numpy"]
-LIMIT_S = 240
-
-
-def median_us(h, f, warm, reps):
-    for _ in range(warm):
-        f()
-    t = []
-    for _ in range(reps):
-        h.timer_begin()
-        f()
-        t.append(h.timer_end() * 1e3)
-    return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
 def signal(n, sps):
@@ -55,26 +42,6 @@ def signal(n, sps):
     x = np.repeat(sym, sps)[:n] * np.exp(1j * 0.002 * np.arange(n))
     x += 0.01 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
     return x.astype(np.complex64)
-
-
-def step_copy(args):
-    import torch
-    x = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
-    y = torch.empty_like(x)
-    x.fill_(1.0)
-    for _ in range(3):
-        y.copy_(x)
-    t = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        y.copy_(x)
-        b.record()
-        b.synchronize()
-        t.append(a.elapsed_time(b) * 1e-3)
-    moved = 2 * x.numel() * 4
-    return dict(copy_bps=moved / float(np.median(t)), text=[
-        f"copy: 1 GiB device to device, median of {args.reps}: {moved / np.median(t) / 1e12:.2f} TB/s read + written"])
 
 
 def step_tick(args):
@@ -134,50 +101,12 @@ def step_numpy(args):
     return dict(text=[f"numpy: the float64 contract on the tick's segment on one host core: {dt * 1e3:.1f} ms"])
 
 
-def run_step(args):
-    return dict(copy=step_copy, tick=step_tick, second=step_second, numpy=step_numpy)[args.step](args)
+def header(args):
+    return (f"symbol recovery (tdsa_symsync_*): every device figure is the median of {args.reps} single calls after warm-up "
+            f"calls, between device events on the handle's stream, records read back included")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warm", type=int, default=3)
-    ap.add_argument("--step", choices=STEPS, default=None)
-    ap.add_argument("--copy-bps", dest="copy_bps", type=float, default=0.0)
-    args = ap.parse_args()
-    args.reps = max(args.reps, 20)
-    if args.step:
-        print("RESULT " + json.dumps(run_step(args)), flush=True)
-        return
-    lines = [f"symbol recovery (tdsa_symsync_*): every device figure is the median of {args.reps} single calls after warm-up "
-             f"calls, between device events on the handle's stream, records read back included"]
-    print(lines[0], flush=True)
-    copy_bps = 0.0
-    for step in STEPS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps), "--warm", str(args.warm),
-               "--copy-bps", repr(copy_bps)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            lines.append(f"{step}: no result within {LIMIT_S} s; stopping")
-            print(lines[-1], flush=True)
-            break
-        res = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-        if r.returncode != 0 or not res:
-            lines.append(f"{step}: exit status {r.returncode}; stopping\n{r.stderr[-1500:]}")
-            print(lines[-1], flush=True)
-            break
-        res = json.loads(res[-1][7:])
-        copy_bps = res.get("copy_bps", copy_bps)
-        for ln in res["text"]:
-            print(ln, flush=True)
-            lines.append(ln)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-
+STEPS = dict(copy=step_copy, tick=step_tick, second=step_second, numpy=step_numpy)
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, header)
