@@ -762,6 +762,96 @@ int tdsa_pulse_debug_limits(tdsa_pulse h, int max_launch_tiles, int passes);
 int tdsa_pulse_timer_begin(tdsa_pulse h);
 int tdsa_pulse_timer_end(tdsa_pulse h, float* elapsed_ms);
 
+/* -------- correlation search of IQ streams: where a known sequence starts -------------------
+ * A sliding, normalised cross-correlation of every stream against one reference r - a preamble, a sync word, a
+ * Zadoff-Chu or Barker code, a radar's transmit pulse - and a peak search over it: one record per match.
+ * Streams and samples.  A handle has C streams, 1 <= C <= 256; stream c's samples of a call lie at in + c * in_stride,
+ *   counted in samples of the call's format (TDSA_IN_I8 / _U8 / _C64, unpacked as the power statistics and the pulse
+ *   analysis do; the format may change from call to call).  The samples of a stream count from the last reset across
+ *   calls: n = 0, 1, ... (int64).
+ * Reference.  r[0 .. L-1] complex64, 2 <= L <= 1024, every component finite, E_r = sum |r[k]|^2 > 0 formed in float64
+ *   and rounded once to float32 (it must stay finite and above 0).  H = floor(L / 2).  _set_reference resets the streams.
+ * Window.  Window n is complete once sample n + L - 1 has arrived.  For every complete window, all in float32:
+ *     c1[n] = sum_{k <  H} x[n+k] conj(r[k])        c2[n] = sum_{k >= H} x[n+k] conj(r[k])        c[n] = fl(c1 + c2)
+ *     e[n]  = sum_k |x[n+k]|^2                       m[n] = fl(fl(fl(c_re^2) + fl(c_im^2)) / fl(E_r e[n]))
+ *   If e[n] = 0, or a component of c1 or c2, or e, is not finite: m[n] = 0 and the window counts in n_bad.  An m that
+ *   comes out as NaN (inf / inf, 0 / 0 after an overflow or underflow) is stored as the quiet NaN 0x7fc00000.
+ * Order of the sums: ONE fixed order per window, wherever it lies in a tile, a launch, a call or a stride and whichever
+ *   load path read it.  Every sum is a chain of fused multiply-adds from +0 in ascending k.  re(c1), re(c2): per k
+ *   fma(x_re, r_re, .) then fma(x_im, r_im, .).  im(c1), im(c2): per k fma(x_im, r_re, .) then fma(x_re, -r_im, .).
+ *   e = fl(a + b), a the chain of fma(x_re, x_re, .), b the chain of fma(x_im, x_im, .), each over all L samples.
+ * Match.  With a float32 threshold, 0 < threshold <= 1, and min_distance W, 1 <= W <= 65536, window n is a match when
+ *   m[n] >= threshold, m[n] > m[j] for every j in [max(0, n-W), n) and m[n] >= m[j] for every j in (n, n+W]: the first
+ *   of equal maxima wins.  m is never negative, so the two comparisons with m[j] are those of the float32 bits as
+ *   unsigned integers, in which a NaN ranks above +inf; a NaN window is never a match (m[n] >= threshold is false).
+ *   The decision on n needs m up to n + W: the last W complete windows of a stream stay undecided in the handle,
+ *   together with the L - 1 samples of history, until a later call brings their neighbours.
+ * Flush.  _flush decides the undecided windows with the right-hand range clipped at the last complete window.  After
+ *   it the streams take no samples until a reset: a process call returns TDSA_ERR_ARG with a text that says so.
+ * Records, 32 bytes per match: index (= n), metric (= m[n]), energy (= e[n]), c1_re, c1_im, c2_re, c2_im.  Matches get
+ *   ordinals 0, 1, ... in time order per stream; ordinal k < capacity is stored at slot k, the rest are counted in
+ *   n_lost; nothing is overwritten.
+ * Summary per stream: n_total samples, n_windows complete windows, n_decided of them decided, n_matches (the lost ones
+ *   included), n_lost, n_bad, flushed.
+ * Metric trace.  With trace = K > 0 at _create the handle keeps m and c of the most recent K complete windows of each
+ *   stream on the device (K is lowered to 2^28 / (24 C) if above: the trace of all streams stays within 256 MiB).
+ *   _read_trace(h, stream, first, count, m_out, c_out) copies windows first .. first + count - 1 to host memory
+ *   (c_out: count complex64, may be NULL); a range that reaches outside [max(0, n_windows - K), n_windows) is
+ *   TDSA_ERR_ARG.
+ * Split invariance.  Every bit of the records, the summaries and the trace is the same for any split of the input into
+ *   calls (empty calls included), either entry point, any launch cut, any stride and any alignment of the base.
+ * Accuracy against exact arithmetic: a component of c1 or c2 within 2 (L + 1) 2^-24 A, A the sum of the absolute
+ *   values of its real products; e within 2 (2 L + 1) 2^-24 e; m within what follows from the two plus 8 2^-24 m
+ *   (tests/corr_contract.py derives it).  Twice the first-order bound for so many terms; the header promises no more.
+ * _create(device, streams, capacity, trace, max_host_samples, ref, L, &h): 1 <= capacity, streams * capacity <= 2^22.
+ * After it threshold = 1 and min_distance = L.  _configure(threshold, min_distance) and _set_reference reset the
+ * streams and return when earlier calls have finished, as _reset does; the device memory of a handle grows with
+ * min_distance: 24 bytes times the next power of two above 2 W + 2^21 / C + trace, per stream.
+ * _process: host samples through pinned staging, C * n_in <= max_host_samples; returns when they are consumed.
+ * _process_dev: samples in device memory, aligned to one sample, on plan p's stream (ordered after its work, and its
+ * later work after this) or on the handle's own for p = NULL; it does NOT wait.  in_stride >= n_in when C > 1; n_in = 0
+ * returns TDSA_OK and does nothing; a call of any length is cut into launches.  _read goes behind the last launch and
+ * waits: n_streams summaries from first_stream on, and for each of them its `capacity` record slots (records_host:
+ * n_streams * capacity records, may be NULL), of which the first min(n_matches, capacity) are valid.  _debug_limits is
+ * for the tests and tools/corrbench.py: fewer tiles of TDSA_CORR_TILE windows per launch (at least `streams`), a mask
+ * of the passes to launch (1 correlate, 2 block maxima and count, 4 scan, 8 emit; anything but 15 leaves the state
+ * meaningless until the next reset) and a variant of the correlate pass (0 as shipped: 4 for L <= 128, else 6; 1 .. 5: 4,
+ * 8, 16 windows per thread, then 4, 8 with packed fused multiply-adds, the reference through scalar loads; 6, 7: 8, then
+ * 8 packed, the reference read from LDS: the same bits from all of them).  A process call that returns TDSA_ERR_HIP may
+ * have enqueued some of its launches: the streams are then undefined until the next reset.  Argument errors are reported before any HIP call. */
+#define TDSA_CORR_MAX_STREAMS 256
+#define TDSA_CORR_MAX_RECORDS 4194304
+#define TDSA_CORR_MIN_REF 2
+#define TDSA_CORR_MAX_REF 1024
+#define TDSA_CORR_MAX_DISTANCE 65536
+#define TDSA_CORR_TILE 2048
+#define TDSA_CORR_WINDOWS_PER_THREAD 8
+#define TDSA_CORR_MAX_LAUNCH_TILES 1024
+typedef struct tdsa_corr_record {
+  int64_t index;
+  float metric, energy;
+  float c1_re, c1_im, c2_re, c2_im;
+} tdsa_corr_record;                             /* 32 bytes */
+typedef struct tdsa_corr_summary {
+  uint64_t n_total, n_windows, n_decided, n_matches, n_lost, n_bad;
+  int32_t flushed, reserved;
+} tdsa_corr_summary;                            /* 56 bytes */
+typedef struct tdsa_corr_s* tdsa_corr;
+int tdsa_corr_create(int device_id, int streams, int capacity, int64_t trace, size_t max_host_samples, const void* ref_c64,
+                     int ref_len, tdsa_corr* out);
+int tdsa_corr_destroy(tdsa_corr h);
+int tdsa_corr_set_reference(tdsa_corr h, const void* ref_c64, int ref_len);
+int tdsa_corr_configure(tdsa_corr h, float threshold, int min_distance);
+int tdsa_corr_reset(tdsa_corr h);
+int tdsa_corr_process(tdsa_corr h, int in_format, const void* in_host, size_t n_in, size_t in_stride);
+int tdsa_corr_process_dev(tdsa_corr h, tdsa_plan p, int in_format, const void* in_dev, size_t n_in, size_t in_stride);
+int tdsa_corr_flush(tdsa_corr h);
+int tdsa_corr_read(tdsa_corr h, int first_stream, int n_streams, tdsa_corr_record* records_host, tdsa_corr_summary* summaries_host);
+int tdsa_corr_read_trace(tdsa_corr h, int stream, int64_t first, int64_t count, float* m_out, void* c_out_c64);
+int tdsa_corr_debug_limits(tdsa_corr h, int max_launch_tiles, int passes, int variant);
+int tdsa_corr_timer_begin(tdsa_corr h);
+int tdsa_corr_timer_end(tdsa_corr h, float* elapsed_ms);
+
 /* -------- stepped sweeps: one capture per tuning step, stitched into one trace --------------
  * What hackrf_sweep / rtl_power do per tuning step - capture, window, FFT, keep the clean middle, lay the steps side by
  * side - and what HackRFSweepDataSource._parse does with their output (datasources/hackrf_sweep.py:135-166: sort by

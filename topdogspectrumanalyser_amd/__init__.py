@@ -20,6 +20,7 @@ from .detect import Detections, SignalDetector  # noqa: F401
 from .measure import ChannelMeasure, Measurements, channel_plan, channels_from_emission, limit_line  # noqa: F401
 from .powerstats import PowerStatistics, PowerStats, gaussian_ccdf  # noqa: F401
 from .pulses import PulseAnalyzer, PulseTrain, levels_from_db  # noqa: F401
+from .correlate import Correlator, Matches, barker, from_symbols, zadoff_chu  # noqa: F401
 from .zerospan import ZeroSpan, view_plan  # noqa: F401
 from .history3d import RibbonView, SurfaceView, ThreeDView, TraceHistory  # noqa: F401
 from .sweep import IqSweepDataSource, SweepAssembler, plan_steps  # noqa: F401
@@ -31,4 +32,4 @@ __all__ = ["DeviceBuffer", "SpectrumEngine", "HostPipe", "TraceState", "TraceAve
            "TraceHistory", "RibbonView", "ThreeDView", "SurfaceView", "Channelizer", "ChannelSpectra",
            "Demodulator", "design_audio_filter", "deemphasis_pole", "SignalDetector", "Detections", "ChannelMeasure", "Measurements",
            "channel_plan", "limit_line", "channels_from_emission", "PowerStats", "PowerStatistics", "gaussian_ccdf",
-           "PulseAnalyzer", "PulseTrain", "levels_from_db"]
+           "PulseAnalyzer", "PulseTrain", "levels_from_db", "Correlator", "Matches", "zadoff_chu", "barker", "from_symbols"]

@@ -1,4 +1,4 @@
-"""What the measurement handles share on the way in: IQ streams (PowerStats, PulseAnalyzer) and float32 dB rows
+"""What the measurement handles share on the way in: IQ streams (PowerStats, PulseAnalyzer, Correlator) and float32 dB rows
 (SignalDetector, ChannelMeasure).  Each mixin holds the staging limit of the host entry point, the checks of the input
 and both process calls; _process names the library's (host, device) pair, as _destroy and _timer name theirs."""
 from __future__ import annotations

@@ -85,6 +85,16 @@ class PulseSummary(C.Structure):
                 ("open", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CorrRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("metric", C.c_float), ("energy", C.c_float), ("c1_re", C.c_float),
+                ("c1_im", C.c_float), ("c2_re", C.c_float), ("c2_im", C.c_float)]
+
+
+class CorrSummary(C.Structure):
+    _fields_ = [("n_total", C.c_uint64), ("n_windows", C.c_uint64), ("n_decided", C.c_uint64), ("n_matches", C.c_uint64),
+                ("n_lost", C.c_uint64), ("n_bad", C.c_uint64), ("flushed", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/tdsa_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -217,6 +227,19 @@ _SIGNATURES = {
     "tdsa_pulse_debug_limits": (C.c_int, [_P, C.c_int, C.c_int]),
     "tdsa_pulse_timer_begin": (C.c_int, [_P]),
     "tdsa_pulse_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_corr_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_size_t, _P, C.c_int, C.POINTER(_P)]),
+    "tdsa_corr_destroy": (C.c_int, [_P]),
+    "tdsa_corr_set_reference": (C.c_int, [_P, _P, C.c_int]),
+    "tdsa_corr_configure": (C.c_int, [_P, C.c_float, C.c_int]),
+    "tdsa_corr_reset": (C.c_int, [_P]),
+    "tdsa_corr_process": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_size_t]),
+    "tdsa_corr_process_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.c_size_t]),
+    "tdsa_corr_flush": (C.c_int, [_P]),
+    "tdsa_corr_read": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "tdsa_corr_read_trace": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, _P]),
+    "tdsa_corr_debug_limits": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "tdsa_corr_timer_begin": (C.c_int, [_P]),
+    "tdsa_corr_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_sweep_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tdsa_sweep_destroy": (C.c_int, [_P]),
     "tdsa_sweep_set_geometry": (C.c_int, [_P, _P, C.c_double, C.c_int, C.c_int, _P]),

@@ -4,7 +4,7 @@
 // their lifetime, the timer entry points, and the one rule that orders a handle's launches whichever stream each goes
 // on.  Over Lane stand three bases, each with the checks of a call and both entry points: Feed for the streaming filters
 // (down-converter, channelizer, demodulator: taps, history, input count), IqAccum for the accumulators over IQ streams
-// (power statistics, pulse analysis) and RowAnalyser for the analysers of dB rows (signal detection, channel
+// (power statistics, pulse analysis, correlation search) and RowAnalyser for the analysers of dB rows (signal detection, channel
 // measurements: the records grown on demand and the tail of a call).  All three stage a host block through Staging.  The
 // public face of the library is include/tdsa_hip.h.
 #pragma once
@@ -568,7 +568,7 @@ struct IqNames {
   const char *handle, *takes;
 };
 
-// The base of the accumulators over IQ streams (power statistics, pulse analysis) over Lane: C streams of n_in samples
+// The base of the accumulators over IQ streams (power statistics, pulse analysis, correlation search) over Lane: C streams of n_in samples
 // each in I8, U8 or C64, stream c at in + c * in_stride samples.  Neither entry point leaves anything in the caller's
 // memory: the state stays on the device until the handle's _read, and the device entry point does not wait.  A handle
 // type H supplies its state and H::run(s, fmt, in, n_in, in_stride), its launches on stream s between order(s) and
