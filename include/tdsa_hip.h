@@ -527,6 +527,66 @@ int tdsa_symsync_symbols_per_segment(uint64_t step, size_t seg_len, int* K);
 int tdsa_symsync_timer_begin(tdsa_symsync h);
 int tdsa_symsync_timer_end(tdsa_symsync h, float* elapsed_ms);
 
+/* -------- FSK analysis: symbol clock, deviation, symbols, FSK error --------------------------
+ * Feed-forward and per segment like the symbol recovery above, whose 32.32 positions, step, nu and resampler it shares:
+ * segment s is in[s * hop + j], j < seg_len, analysed on its own; the handle keeps no state between calls.  Input:
+ * TDSA_FSK_IQ complex64, or TDSA_FSK_FREQ float32 that is a frequency already.  levels M = 2, 4 or 8; a level is an odd
+ * integer l = 2 i - (M - 1), i = 0 .. M - 1.
+ *   0 discriminate  (IQ) d_j = arg(x[j+1] conj x[j]) / pi in half turns per sample, j < n_d = seg_len - 1; not unwrapped:
+ *                   the signal is taken to stay inside +-fs/2.  (FREQ) d_j = in_j, n_d = seg_len.
+ *   1 boxcar        b_j = (((d_j + d_j+1) + ...) + d_j+B-1) * float32(1 / B), float32 adds in ascending order,
+ *                   j < n_b = n_d - B + 1, B = 1 .. 64; B = 1 leaves d bit for bit.
+ *   2 timing        e_j = (b_j+L - b_j)^2, j < n_b - L, L = 1 .. 64 (none: P = C = 0); P = sum e_j, C = sum e_j
+ *                   exp(-2 pi i (j nu mod 2^32) / 2^32); a = arg C / pi ((0, 0): 0), t = -a / 2 (+ 1 if negative), taken to
+ *                   32 fractional bits; delta_fx = (floor(t step) + L 2^31 + (step >> 1)) mod step, + step if below 2^32:
+ *                   the transitions of e lie L / 2 samples past their phase, the symbol centres half a symbol later.
+ *                   TDSA_FSK_FIXED: the caller's delta_fx instead, 2^32 <= delta_fx < step + 2^32.
+ *   3 resample      K = floor((n_b - 4) 2^32 / step) - 1 symbols (2 .. 4096); v_k = the cubic Lagrange interpolation of
+ *                   b[i-1 .. i+2] at pos = delta_fx + k step, as the symbol recovery forms it.
+ *   4 levels        lo = min v, hi = max v, o = (hi + lo) / 2, g = (hi - lo) float32(1 / (2 (M - 1))); then twice:
+ *                   i_k = clamp(floor((v_k - o) / (g + g) + M / 2), 0, M - 1) in float32 (a NaN: 0), l_k = 2 i_k - (M - 1),
+ *                   D = K sum l^2 - (sum l)^2 in integers; D != 0: g = (K sum l v - sum l sum v) / D, o = (sum v - g
+ *                   sum l) / K in float64, rounded to float32; D = 0 (one level, also hi = lo): o, g stay,
+ *                   TDSA_FSK_ONE_LEVEL.  The indices are those of the second round.
+ *   5 errors        err_k = v_k - fmaf(g, l_k, o); err_sumsq = sum err_k^2 in float64; err_peak = the largest |err_k|,
+ *                   err_peak_k its lowest k.
+ * Levels: float32, segment s at out + s * out_stride, the first K of each row are written; idx (or NULL): uint8 of the
+ * same shape, i_k.  One 64-byte record per segment.  A segment whose P, C or any v_k is not finite has
+ * TDSA_FSK_NONFINITE set, NaN levels, zero indices and an otherwise zero record; no other segment is touched.  Every sum is one fixed tree per (seg_len, B, L, K), so a segment's results depend on its samples
+ * alone: not on n_seg, its place or the entry point.  _process: host memory through pinned staging, n_samples and
+ * n_seg * seg_len <= max_host_samples.  _process_dev: device memory, on plan p's stream (ordered after its work, and its
+ * later work after this) or on the handle's own for p = NULL; returns when the records are in records_host.
+ * _symbols_per_segment needs no device.  Argument errors are reported before any HIP call. */
+#define TDSA_FSK_IQ 0
+#define TDSA_FSK_FREQ 1
+#define TDSA_FSK_AUTO 0
+#define TDSA_FSK_FIXED 1
+#define TDSA_FSK_NONFINITE 1u
+#define TDSA_FSK_ONE_LEVEL 2u
+typedef struct tdsa_fsk_record {
+  uint64_t delta_fx;           /* the first symbol's position among the b_j, 32.32 samples */
+  float c_re, c_im, p;         /* the symbol-rate line of e and its sum */
+  float offset, dev;           /* o and g: the centre of the levels and half the spacing of adjacent ones */
+  float lo, hi;                /* the smallest and the largest v_k */
+  float err_peak;
+  double err_sumsq;
+  int32_t err_peak_k;
+  int32_t sum_l;               /* sum of l_k of the second round */
+  uint32_t flags, reserved;
+} tdsa_fsk_record;
+typedef struct tdsa_fsk_s* tdsa_fsk;
+int tdsa_fsk_create(int device_id, size_t max_host_samples, tdsa_fsk* out);
+int tdsa_fsk_destroy(tdsa_fsk h);
+int tdsa_fsk_configure(tdsa_fsk h, uint64_t step, uint32_t nu, int levels, int input_kind, int boxcar, int lag,
+                       int timing_mode, uint64_t delta_fx);
+int tdsa_fsk_process(tdsa_fsk h, const void* in_host, size_t n_samples, size_t seg_len, size_t hop, int n_seg,
+                     float* out_host, size_t out_stride, uint8_t* idx_host, tdsa_fsk_record* records_host);
+int tdsa_fsk_process_dev(tdsa_fsk h, tdsa_plan p, const void* in_dev, size_t seg_len, size_t hop, int n_seg,
+                         void* out_dev, size_t out_stride, void* idx_dev, tdsa_fsk_record* records_host);
+int tdsa_fsk_symbols_per_segment(uint64_t step, size_t seg_len, int input_kind, int boxcar, int* K);
+int tdsa_fsk_timer_begin(tdsa_fsk h);
+int tdsa_fsk_timer_end(tdsa_fsk h, float* elapsed_ms);
+
 /* -------- signal detection: noise floor, emissions, occupancy ----------------------------
  * Rows are [n_rows][n_bins] float32 dB rows, 1 <= n_bins <= 16384, the input of tdsa_rows_top_peaks.  Per row, with
  * seg = row[bin_lo .. bin_hi] (inclusive) and n_eff its length:
