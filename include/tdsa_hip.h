@@ -498,7 +498,8 @@ int tdsa_demod_timer_end(tdsa_demod d, float* elapsed_ms);
  * shape, y.  One record per segment.  A segment whose P or C is not finite has TDSA_SYMSYNC_NONFINITE set, NaN symbols
  * and an otherwise zero record; no other segment is touched.  TDSA_SYMSYNC_NO_CARRIER: the transform's power is not
  * finite, step_f = theta_fx = 0.  A segment's results depend on its samples alone: not on n_seg, its place or the entry
- * point.  _process: host memory through pinned staging, n_samples and n_seg * seg_len <= max_host_samples.
+ * point.  _process: host memory through pinned staging, n_samples and n_seg * seg_len <= max_host_samples; a hop that
+ * takes a segment beyond the block is refused whatever its size.
  * _process_dev: device memory, on plan p's stream (ordered after its work, and its later work after this) or on the
  * handle's own for p = NULL; returns when the records are in records_host.  _symbols_per_segment needs no device.
  * Argument errors are reported before any HIP call. */

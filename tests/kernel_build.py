@@ -57,8 +57,17 @@ def remarks(stderr):
 
 def header_const(header, name):
     """`constexpr int` or `constexpr long long` `name` of csrc/`header` as a Python int; other k... names in its
-    initialiser are looked up in the same header."""
-    m = re.search(r"constexpr (?:int|long long) %s = ([^;]+);" % name, open(os.path.join(CSRC, header)).read())
+    initialiser are looked up in the same header.  A name the header does not define is looked up in the headers of
+    csrc it includes."""
+    text = open(os.path.join(CSRC, header)).read()
+    m = re.search(r"constexpr (?:int|long long) %s = ([^;]+);" % name, text)
+    if not m:
+        for inc in re.findall(r'^#include "(\w+\.hpp)"', text, re.M):
+            try:
+                return header_const(inc, name)
+            except LookupError:
+                pass
+        raise LookupError(f"{name} is not in {header} or what it includes")
     expr = re.sub(r"\bk\w+", lambda k: str(header_const(header, k.group(0))), m.group(1)).replace("1ll", "1")
     return int(eval(expr))
 

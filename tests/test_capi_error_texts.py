@@ -1,6 +1,6 @@
 """The texts tdsa_last_error_string returns for the argument errors of the detector, the channel measurements, the power
-statistics and the pulse analysis that need no live handle, and for the null-handle timer calls of every handle type
-that has a timer.  Every text is compared whole: the entry points of these handles share their checks, and a shared
+statistics, the pulse analysis, the symbol recovery and the FSK analysis that need no live handle, and for the
+null-handle timer calls of every handle type that has a timer.  Every text is compared whole: the entry points of these handles share their checks, and a shared
 check must go on naming the handle it speaks for.  No call here reaches a device."""
 import ctypes as C
 
@@ -23,6 +23,11 @@ def out():
 
 DETECT_OK = (0, 63, 31, 10.0, 1, 0, 3.0, 16)          # bin_lo, bin_hi, rank, margin_db, min_width, max_gap, xdb, max_signals
 MEAS_OK = (1, ints(0), ints(63), 0, 63, 0.99, 26.0)   # n_channels, lo, hi, obw_lo, obw_hi, fraction, xdb
+ONE = 1 << 32                                         # one sample in 32.32: 4 samples per symbol have nu = 2^30
+SYM_OK = (4 * ONE, 1 << 30, 4, 0.0, 0, 0)             # step, nu, order, ref_arg, timing_mode, delta_fx
+FSK_OK = (4 * ONE, 1 << 30, 2, 0, 2, 2, 0, 0)         # step, nu, levels, input_kind, boxcar, lag, timing_mode, delta_fx
+STEP_RANGE = "4 .. 64 samples per symbol in 32.32 fixed point"
+DELTA_RANGE = "2^32 <= delta_fx < step + 2^32"
 
 CASES = [
     # ---- signal detection ------------------------------------------------------------------------------------------
@@ -124,11 +129,57 @@ CASES = [
     ("tdsa_pulse_debug_limits", (None, 16, 7), "null pulse handle"),
     ("tdsa_pulse_timer_begin", (None,), "null pulse handle"),
     ("tdsa_pulse_timer_end", (None, None), "null pulse handle"),
+    # ---- symbol recovery ----------------------------------------------------------------------------------------------
+    ("tdsa_symsync_create", (0, 4096, None), "null out"),
+    ("tdsa_symsync_create", (0, 8, out()), "max_host_samples=8: at least 16"),
+    ("tdsa_symsync_configure", (None, 4 * ONE - 1) + SYM_OK[1:], f"step={4 * ONE - 1}: {STEP_RANGE}"),
+    ("tdsa_symsync_configure", (None, 64 * ONE + 1, 1 << 26) + SYM_OK[2:], f"step={64 * ONE + 1}: {STEP_RANGE}"),
+    ("tdsa_symsync_configure", (None, 4 * ONE, (1 << 30) + 2) + SYM_OK[2:], "nu=1073741826: the phase step of this symbol rate is 1073741824"),
+    ("tdsa_symsync_configure", (None, 4 * ONE, (1 << 30) - 2) + SYM_OK[2:], "nu=1073741822: the phase step of this symbol rate is 1073741824"),
+    ("tdsa_symsync_configure", (None, 4 * ONE, 1 << 30, 3, 0.0, 0, 0), "order=3: 0, 2, 4 or 8"),
+    ("tdsa_symsync_configure", (None, 4 * ONE, 1 << 30, 4, float("nan"), 0, 0), "ref_arg is not finite"),
+    ("tdsa_symsync_configure", (None, 4 * ONE, 1 << 30, 4, 0.0, 2, 0), "timing_mode=2: TDSA_SYMSYNC_AUTO or _FIXED"),
+    ("tdsa_symsync_configure", (None, 4 * ONE, 1 << 30, 4, 0.0, 1, ONE - 1), f"delta_fx={ONE - 1}: {DELTA_RANGE}"),
+    ("tdsa_symsync_configure", (None, 4 * ONE, 1 << 30, 4, 0.0, 1, 5 * ONE), f"delta_fx={5 * ONE}: {DELTA_RANGE}"),
+    ("tdsa_symsync_configure", (None,) + SYM_OK, "null symbol synchroniser"),
+    ("tdsa_symsync_symbols_per_segment", (4 * ONE, 100, None), "null K"),
+    ("tdsa_symsync_symbols_per_segment", (4 * ONE - 1, 100, C.byref(N)), f"step={4 * ONE - 1}: {STEP_RANGE}"),
+    ("tdsa_symsync_process", (None, BUF, 100, 100, 100, 1, BUF, 64, None, BUF), "null symbol synchroniser"),
+    ("tdsa_symsync_process", (None, None, 100, 100, 0, 0, None, 0, None, None), "null symbol synchroniser"),
+    ("tdsa_symsync_process_dev", (None, None, BUF, 100, 100, 1, BUF, 64, None, BUF), "null symbol synchroniser"),
+    ("tdsa_symsync_process_dev", (None, None, C.c_void_p(4100), 100, 100, 1, BUF, 64, None, BUF), "null symbol synchroniser"),
+    ("tdsa_symsync_timer_begin", (None,), "null symbol synchroniser"),
+    ("tdsa_symsync_timer_end", (None, None), "null symbol synchroniser"),
+    # ---- FSK analysis --------------------------------------------------------------------------------------------------
+    ("tdsa_fsk_create", (0, 4096, None), "null out"),
+    ("tdsa_fsk_create", (0, 8, out()), "max_host_samples=8: at least 16"),
+    ("tdsa_fsk_configure", (None, 4 * ONE - 1) + FSK_OK[1:], f"step={4 * ONE - 1}: {STEP_RANGE}"),
+    ("tdsa_fsk_configure", (None, 64 * ONE + 1, 1 << 26) + FSK_OK[2:], f"step={64 * ONE + 1}: {STEP_RANGE}"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, (1 << 30) + 2) + FSK_OK[2:], "nu=1073741826: the phase step of this symbol rate is 1073741824"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, (1 << 30) - 2) + FSK_OK[2:], "nu=1073741822: the phase step of this symbol rate is 1073741824"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 3, 0, 2, 2, 0, 0), "levels=3: 2, 4 or 8"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 2, 2, 2, 0, 0), "input_kind=2: TDSA_FSK_IQ or _FREQ"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 0, 0, 2, 0, 0), "boxcar=0: 1 .. 64 samples"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 0, 65, 2, 0, 0), "boxcar=65: 1 .. 64 samples"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 0, 2, 0, 0, 0), "lag=0: 1 .. 64 samples"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 0, 2, 65, 0, 0), "lag=65: 1 .. 64 samples"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 0, 2, 2, 2, 0), "timing_mode=2: TDSA_FSK_AUTO or _FIXED"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 0, 2, 2, 1, ONE - 1), f"delta_fx={ONE - 1}: {DELTA_RANGE}"),
+    ("tdsa_fsk_configure", (None, 4 * ONE, 1 << 30, 2, 0, 2, 2, 1, 5 * ONE), f"delta_fx={5 * ONE}: {DELTA_RANGE}"),
+    ("tdsa_fsk_configure", (None,) + FSK_OK, "null FSK analyser"),
+    ("tdsa_fsk_symbols_per_segment", (4 * ONE, 100, 0, 2, None), "null K"),
+    ("tdsa_fsk_symbols_per_segment", (64 * ONE + 1, 100, 0, 2, C.byref(N)), f"step={64 * ONE + 1}: {STEP_RANGE}"),
+    ("tdsa_fsk_symbols_per_segment", (4 * ONE, 100, -1, 2, C.byref(N)), "input_kind=-1: TDSA_FSK_IQ or _FREQ"),
+    ("tdsa_fsk_symbols_per_segment", (4 * ONE, 100, 1, 65, C.byref(N)), "boxcar=65: 1 .. 64 samples"),
+    ("tdsa_fsk_process", (None, BUF, 100, 100, 100, 1, BUF, 64, None, BUF), "null FSK analyser"),
+    ("tdsa_fsk_process", (None, None, 100, 100, 0, 0, None, 0, None, None), "null FSK analyser"),
+    ("tdsa_fsk_process_dev", (None, None, BUF, 100, 100, 1, BUF, 64, None, BUF), "null FSK analyser"),
+    ("tdsa_fsk_process_dev", (None, None, C.c_void_p(4098), 100, 100, 1, BUF, 64, None, BUF), "null FSK analyser"),
+    ("tdsa_fsk_timer_begin", (None,), "null FSK analyser"),
+    ("tdsa_fsk_timer_end", (None, None), "null FSK analyser"),
     # ---- the timers of the other handle types ------------------------------------------------------------------------
     ("tdsa_demod_timer_begin", (None,), "null demodulator"),
     ("tdsa_demod_timer_end", (None, None), "null demodulator"),
-    ("tdsa_symsync_timer_begin", (None,), "null symbol synchroniser"),
-    ("tdsa_symsync_timer_end", (None, None), "null symbol synchroniser"),
     ("tdsa_sweep_timer_begin", (None,), "null sweep"),
     ("tdsa_sweep_timer_end", (None, None), "null sweep"),
     ("tdsa_zspan_timer_begin", (None,), "null zero span"),

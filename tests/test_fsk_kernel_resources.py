@@ -14,7 +14,8 @@ _const = functools.partial(header_const, "tdsa_fsk.hpp")
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
     # contraction is off for the file
-    in_makefile("fsk", ["tdsa_fsk.hpp", "tdsa_fsk_math.hpp", "tdsa_symsync_math.hpp", "tdsa_demod_math.hpp"],
+    in_makefile("fsk", ["tdsa_fsk.hpp", "tdsa_fsk_math.hpp", "tdsa_symsync_math.hpp", "tdsa_demod_math.hpp", "tdsa_seg.hpp",
+                        "tdsa_seg_block.hpp"],
                 own_flags="-ffp-contract=off")
     return cross_compiled(tmp_path_factory, "tdsa_fsk.hip")
 
@@ -31,10 +32,10 @@ def test_fsk_kernels_have_no_scratch_no_spills_and_the_budgeted_static_lds(kerne
 
 
 def test_lds_at_the_largest_k_stays_inside_the_declared_budget():
-    assert (_const("kFskThreads"), _const("kFskMaxSymbols")) == (256, fk.MAX_SYMBOLS)
+    assert (_const("kSegThreads"), _const("kSegMaxSymbols")) == (256, fk.MAX_SYMBOLS)
     assert (_const("kFskMaxBoxcar"), _const("kFskMaxLag")) == (fk.MAX_BOXCAR, fk.MAX_LAG)
     # a tile of e is whole rounds of the workgroup, and its b and d fit their arrays at the largest B and L
-    assert _const("kFskTile") % _const("kFskThreads") == 0
+    assert _const("kFskTile") % _const("kSegThreads") == 0
     assert _const("kFskTileB") >= _const("kFskTile") + fk.MAX_LAG
     assert _const("kFskTileD") >= _const("kFskTileB") + fk.MAX_BOXCAR - 1
     limit = _const("kFskMaxLdsBytes")

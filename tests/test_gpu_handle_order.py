@@ -1,5 +1,5 @@
 """A handle's launches are totally ordered whichever stream each goes on (the ordering rule of Lane in
-csrc/tdsa_capi_internal.hpp).  Each of the ten handle types that can launch on a producer plan's stream is fed the same
+csrc/tdsa_capi_internal.hpp).  Each of the twelve handle types that can launch on a producer plan's stream is fed the same
 input in six pieces, hopping engine A's stream -> its own -> engine B's stream -> ..., and has to return exactly what a
 second handle returns that was fed the same pieces on its own stream throughout.  Every piece depends on the state the
 piece before it left (filter history, ring position, hold row, a step written twice, an open pulse, a record buffer that
@@ -15,9 +15,9 @@ import detect_contract as dc
 import meas_contract as mc
 import pstat_contract as psc
 import pulse_contract as plc
-from topdogspectrumanalyser_amd import (Channelizer, ChannelMeasure, Demodulator, DeviceBuffer, DownConverter, PowerStats,
-                                        PulseAnalyzer, SignalDetector, SpectrumEngine, SweepAssembler, TraceHistory, ZeroSpan,
-                                        _native as nat)
+from topdogspectrumanalyser_amd import (Channelizer, ChannelMeasure, Demodulator, DeviceBuffer, DownConverter, FskAnalyzer,
+                                        PowerStats, PulseAnalyzer, SignalDetector, SpectrumEngine, SweepAssembler, SymbolSync,
+                                        TraceHistory, ZeroSpan, _native as nat)
 
 pytestmark = pytest.mark.gpu
 
@@ -300,6 +300,45 @@ def test_signal_detector_hopping_streams(engines):
     assert got["rows"]["n_found"][4] > 4 and got["rows"]["flags"][9] == dc.FLAG_NAN_FLOOR and got["flagged"] == 1
     assert _same(got, one)
     assert _same(got, dict(rows=_fields(rr), signals=_fields(sig), occupancy=occ, seen=seen, flagged=flagged))
+
+
+# ---- symbol recovery and FSK analysis: 4 samples per symbol, segments of 64 samples, pieces as the detector's rows ---------
+SEG_LEN = 64
+
+
+def _seg_input():
+    rng = np.random.default_rng(20)
+    n = SEG_LEN * int(ROW_STARTS[-1])
+    return (rng.normal(size=n) + 1j * rng.normal(size=n)).astype(np.complex64)
+
+
+def _seg_run(make, units, calls):
+    """The calls (engine, first segment, segments) of the handle make() gives, outputs of units[0] and second outputs of
+    units[1] bytes K to a segment back to back: both as bytes, and the records of every call."""
+    total = int(ROW_STARTS[-1])
+    with make() as h, DeviceBuffer.of(_seg_input()) as d_x:
+        K = h.symbols_per_segment(SEG_LEN)
+        with DeviceBuffer(units[0] * K * total) as d_o, DeviceBuffer(units[1] * K * total) as d_a:
+            rec = [h.process_device(eng, d_x.at(8 * SEG_LEN * a, 8 * SEG_LEN * n), SEG_LEN, SEG_LEN, n,
+                                    d_o.at(units[0] * K * a, units[0] * K * n), K,
+                                    d_a.at(units[1] * K * a, units[1] * K * n)).records for eng, a, n in calls]
+            return dict(K=K, out=d_o.get(d_o.size, np.uint8), aux=d_a.get(d_a.size, np.uint8), records=_fields(np.concatenate(rec)))
+
+
+def _seg_pieces(streams):
+    return [(eng, int(a), n) for eng, a, n in zip(streams, ROW_STARTS, ROW_PIECES)]
+
+
+@pytest.mark.parametrize("make,units,K", [(lambda: SymbolSync(4, "qpsk", max_host_samples=64), (8, 8), 14),
+                                          (lambda: FskAnalyzer(4, 2, max_host_samples=64), (4, 1), 13)],
+                         ids=["symbol_sync", "fsk_analyzer"])
+def test_segment_analysers_hopping_streams(engines, make, units, K):
+    got, one = _seg_run(make, units, _seg_pieces(_hopping(engines))), _seg_run(make, units, _seg_pieces(SINGLE))
+    whole = _seg_run(make, units, [(None, 0, int(ROW_STARTS[-1]))])
+    assert got["K"] == K and got["records"]["p"].size == ROW_STARTS[-1] and not (got["records"]["flags"] & 1).any()
+    assert got["out"].any() and got["aux"].any()
+    assert _same(got, one)
+    assert _same(got, whole)
 
 
 # ---- channel measurements: as the detector, 2 channels, the limit line replaced after the third piece -------------------

@@ -410,3 +410,73 @@ def test_device_evm_matches_the_contracts_evm(syncs, mod, sps):
                   f"freq {r.freq[g]:+.6f} cycles/symbol, lock {r.lock[g]:.1f}")
             assert abs(ratio - 1.0) <= 0.05
     assert not r.flags.any()
+
+
+# ---- the -1s that need a live handle ---------------------------------------------------------------------------------------------
+def test_error_returns_with_a_live_handle():
+    import ctypes as C
+    lib = nat.lib
+    err = lambda: lib.tdsa_last_error_string().decode()                                   # noqa: E731
+    P = lambda addr: C.c_void_p(int(addr))                                               # noqa: E731
+    x = np.zeros(8192, dtype=np.complex64)
+    sym = np.zeros(8192, dtype=np.complex64)
+    rw = np.zeros(8192, dtype=np.complex64)
+    rec = np.zeros(64, dtype=sy.RECORD)
+    px, ps, pw, pr = (v.ctypes.data for v in (x, sym, rw, rec))
+    assert px % 8 == 0 and ps % 8 == 0 and pw % 8 == 0 and pr % 8 == 0
+    raw = C.c_void_p()
+    assert lib.tdsa_symsync_create(0, 4096, C.byref(raw)) == 0
+    try:
+        # no argument is wrong: the state is (TDSA_ERR_STATE)
+        assert lib.tdsa_symsync_process(raw, P(px), 100, 100, 100, 1, P(ps), 64, None, P(pr)) == -3 and "not configured" in err()
+        assert lib.tdsa_symsync_process_dev(raw, None, P(px), 100, 100, 1, P(ps), 64, None, P(pr)) == -3 and "not configured" in err()
+        assert lib.tdsa_symsync_process(raw, None, 100, 100, 100, 1, P(ps), 64, None, P(pr)) == -3     # asked before the arguments
+        assert lib.tdsa_symsync_process_dev(raw, None, P(px), 100, 100, 1, None, 64, None, P(pr)) == -3
+    finally:
+        assert lib.tdsa_symsync_destroy(raw) == 0
+    with sy.SymbolSync(4, max_host_samples=4096) as s, DeviceBuffer(8 * 4096) as d_x, DeviceBuffer(8 * 4096) as d_s, \
+            DeviceBuffer(8 * 4096) as d_w:
+        K = s.symbols_per_segment(100)                                                    # 23
+        assert K == 23
+        host = lambda **kw: lib.tdsa_symsync_process(s._h, *[kw.get(k, v) for k, v in (                    # noqa: E731
+            ("inp", P(px)), ("n", 1000), ("seg", 100), ("hop", 100), ("n_seg", 2), ("out", P(ps)), ("stride", 64), ("raw", P(pw)), ("rec", P(pr)))])
+        dev = lambda **kw: lib.tdsa_symsync_process_dev(s._h, None, *[kw.get(k, v) for k, v in (           # noqa: E731
+            ("inp", P(d_x.ptr)), ("seg", 100), ("hop", 100), ("n_seg", 2), ("out", P(d_s.ptr)), ("stride", 64), ("raw", P(d_w.ptr)), ("rec", P(pr)))])
+        for call in (host, dev):
+            assert call() == 0, err()
+            assert call(raw=None) == 0, err()                                              # the raw symbols are optional
+            assert call(inp=None) == -1 and err() == "null samples"
+            assert call(out=None) == -1 and err() == "null symbols"
+            assert call(rec=None) == -1 and err() == "null records"
+            base_in, base_out, base_raw = (px, ps, pw) if call is host else (d_x.ptr, d_s.ptr, d_w.ptr)
+            for off in (dict(inp=P(base_in + 4)), dict(out=P(base_out + 4)), dict(raw=P(base_raw + 4)), dict(rec=P(pr + 4))):
+                assert call(**off) == -1 and err() == "pointers must be aligned to 8 bytes", off
+            assert call(n_seg=0) == -1 and "n_seg=0" in err()
+            assert call(n_seg=-1) == -1 and "n_seg=-1" in err()
+            assert call(hop=0) == -1 and "hop=0" in err()
+            assert call(stride=K - 1) == -1 and f"out_stride={K - 1}: a segment gives {K} symbols" in err()
+            assert call(stride=K) == 0, err()
+            # K outside 2 .. 4096: K = floor((seg_len - 4) / 4) - 1
+            assert call(seg=15, hop=15, n_seg=1) == -1 and "seg_len=15 gives 1 symbols per segment: 2 .. 4096" in err()
+            assert call(seg=3, hop=3, n_seg=1) == -1 and "gives -1 symbols" in err()
+            assert call(seg=16396, hop=1, n_seg=1) == -1 and "gives 4097 symbols" in err()
+            if call is host:
+                assert call(seg=16, hop=16, n_seg=1) == 0, err()
+        # the host entry point alone: the block and the staging
+        assert host(n=199) == -1 and "need 200 samples, the block has 199" in err()
+        assert host(n=99, n_seg=1) == -1 and "the block has 99" in err()
+        assert host(n=1000, n_seg=3, hop=1 << 63) == -1 and "the block has 1000" in err()             # a product that would wrap
+        assert host(n=200) == 0, err()
+        assert host(n=4097, n_seg=1) == -1 and "the handle stages at most 4096 (max_host_samples)" in err()
+        assert host(n=149, n_seg=50, hop=1) == -1 and "max_host_samples" in err()                     # 50 segments of 100 overlap
+        assert host(n=139, n_seg=40, hop=1) == 0, err()
+        n_dev = C.c_int()
+        assert lib.tdsa_device_count(C.byref(n_dev)) == 0
+        if n_dev.value > 1:                                                                # a plan on another device
+            from topdogspectrumanalyser_amd import SpectrumEngine
+            with SpectrumEngine(64, device=1) as eng:
+                assert lib.tdsa_symsync_process_dev(s._h, eng._h, P(d_x.ptr), 100, 100, 2, P(d_s.ptr), 64, None, P(pr)) == -1
+                assert "different devices" in err()
+        assert lib.tdsa_symsync_timer_end(s._h, None) == -1 and err() == "null elapsed_ms"
+        s.timer_begin()
+        assert dev() == 0 and s.timer_end() >= 0.0

@@ -14,7 +14,7 @@ _const = functools.partial(header_const, "tdsa_symsync.hpp")
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
     # contraction is off for the file
-    in_makefile("symsync", ["tdsa_symsync.hpp", "tdsa_symsync_math.hpp"], own_flags="-ffp-contract=off")
+    in_makefile("symsync", ["tdsa_symsync.hpp", "tdsa_symsync_math.hpp", "tdsa_seg.hpp", "tdsa_seg_block.hpp"], own_flags="-ffp-contract=off")
     return cross_compiled(tmp_path_factory, "tdsa_symsync.hip")
 
 
@@ -29,7 +29,7 @@ def test_symsync_kernel_has_no_scratch_no_spills_and_the_budgeted_static_lds(ker
 
 
 def test_dynamic_lds_stays_within_the_budget_for_every_accepted_k():
-    assert (_const("kSymThreads"), _const("kSymMaxSymbols"), _const("kSymMaxGrid")) == (256, sy.MAX_SYMBOLS, 8192)
+    assert (_const("kSegThreads"), _const("kSegMaxSymbols"), _const("kSymMaxGrid")) == (256, sy.MAX_SYMBOLS, 8192)
     limit = _const("kSymMaxLdsBytes")
     assert limit <= 101 * 1024                                   # y at most 32 KiB, the transform at most 64 KiB, scratch
     worst = 0

@@ -72,6 +72,105 @@ class _IqStreams:
                                                      C.c_void_p(int(ptr)), n, stride))
 
 
+ONE = 1 << 32                          # one sample, and one turn of the symbol clock, in 32.32 fixed point
+MIN_SPS, MAX_SPS = 4.0, 64.0
+MAX_SYMBOLS = 4096
+
+
+def fixed_step(samples_per_symbol: float) -> int:
+    """round(sps 2^32): samples per symbol in 32.32 fixed point."""
+    return int(round(float(samples_per_symbol) * ONE))
+
+
+def phase_step(samples_per_symbol: float) -> int:
+    """round(2^32 / sps): the symbol clock's phase step per sample."""
+    return int(round(ONE / float(samples_per_symbol)))
+
+
+class _Segments:
+    """Segments of seg_len samples, `hop` apart, each analysed on its own at the symbol clock of the constructor: K
+    outputs per segment, an optional second output of the same shape and one record.  A handle supplies _k(seg_len), its
+    K formula, _record, the dtype of a record, and _filled, the (sentinel, dtype) of either output."""
+    _process = ("", "")
+    _record = None
+    _filled = ((), ())
+
+    def _rate(self, samples_per_symbol: float) -> None:
+        """samples_per_symbol of the constructor: step and nu."""
+        sps = float(samples_per_symbol)
+        if not MIN_SPS <= sps <= MAX_SPS:
+            raise ValueError(f"samples_per_symbol={samples_per_symbol}: {MIN_SPS:g} .. {MAX_SPS:g}")
+        self.samples_per_symbol = sps
+        self.step, self.nu = fixed_step(sps), phase_step(sps)
+
+    def _stage(self, timing, device: int, max_host_samples: int) -> None:
+        """timing ("auto", or the first symbol's position in samples), device and max_host_samples of the constructor."""
+        if isinstance(timing, str):
+            if timing != "auto":
+                raise ValueError(f"timing={timing!r}: 'auto' or the first symbol's position in samples")
+            self.timing_mode, self.delta_fx = nat.SYMSYNC_AUTO, 0
+        else:
+            self.timing_mode, self.delta_fx = nat.SYMSYNC_FIXED, int(round(float(timing) * ONE))
+            if not ONE <= self.delta_fx < self.step + ONE:
+                raise ValueError(f"timing={timing}: 1 <= timing < samples_per_symbol + 1")
+        self.device = int(device)
+        self.max_host_samples = int(max_host_samples)
+        if self.max_host_samples < 16:
+            raise ValueError(f"max_host_samples={max_host_samples}: at least 16")
+
+    def symbols_per_segment(self, seg_len: int) -> int:
+        """K of a segment of seg_len samples; ValueError outside 2 .. 4096."""
+        K = self._k(seg_len)
+        if not 2 <= K <= MAX_SYMBOLS:
+            raise ValueError(f"seg_len={seg_len} gives {K} symbols per segment: 2 .. {MAX_SYMBOLS}")
+        return K
+
+    def _check(self, seg_len: int, hop: int, n_seg: int, out_stride: int) -> int:
+        K = self.symbols_per_segment(seg_len)
+        if int(hop) < 1:
+            raise ValueError(f"hop={hop}: at least one sample")
+        if int(n_seg) < 1:
+            raise ValueError(f"n_seg={n_seg}: at least one segment")
+        if int(out_stride) < K:
+            raise ValueError(f"out_stride={out_stride}: a segment gives {K} symbols")
+        return K
+
+    def _host(self, a: np.ndarray, seg_len: int, hop: Optional[int], out_stride: Optional[int], second: bool):
+        """The host call over the stream a: every whole segment of seg_len samples, `hop` (default seg_len) apart.
+        Returns (K, records, outputs, second outputs or None); the outputs are [n_seg][out_stride] with the sentinel where
+        the library writes nothing, or [n_seg][K] where no out_stride is given."""
+        seg_len = int(seg_len)
+        hop = seg_len if hop is None else int(hop)
+        if a.size < seg_len:
+            raise ValueError(f"{a.size} samples: less than one segment of {seg_len}")
+        n_seg = (a.size - seg_len) // max(hop, 1) + 1
+        K = self.symbols_per_segment(seg_len)
+        stride = K if out_stride is None else int(out_stride)
+        self._check(seg_len, hop, n_seg, stride)
+        used = (n_seg - 1) * hop + seg_len
+        if used > self.max_host_samples or n_seg * seg_len > self.max_host_samples:
+            raise ValueError(f"{n_seg} segments of {seg_len} samples: the handle stages at most {self.max_host_samples} "
+                             "(max_host_samples)")
+        out, aux = (np.full((n_seg, stride), fill, dtype=dtype) if wanted else None
+                    for wanted, (fill, dtype) in zip((True, second), self._filled))
+        rec = np.zeros(n_seg, dtype=self._record)
+        nat.check(getattr(nat.lib, self._process[0])(self._h, a.ctypes.data_as(C.c_void_p), used, seg_len, hop, n_seg,
+                                                     out.ctypes.data_as(C.c_void_p), stride,
+                                                     aux.ctypes.data_as(C.c_void_p) if second else None,
+                                                     rec.ctypes.data_as(C.c_void_p)))
+        if out_stride is None:
+            out, aux = out[:, :K], aux[:, :K] if second else None
+        return K, rec, out, aux
+
+    @staticmethod
+    def timing_quality(records: np.ndarray) -> np.ndarray:
+        """|C| / P of a call's records, the depth of the symbol-rate line; 0 where P is not above 0."""
+        with np.errstate(all="ignore"):
+            p = records["p"].astype(np.float64)
+            c = np.hypot(records["c_re"].astype(np.float64), records["c_im"].astype(np.float64))
+            return np.where(p > 0, c / np.where(p > 0, p, 1.0), 0.0)
+
+
 class _DbRows:
     """[n_rows][self.n_bins] float32 dB rows; each call returns the records of its rows.  A handle supplies
     _records(n_rows), the two empty record arrays of a call, and _result(rows, sub), what a call returns for them."""

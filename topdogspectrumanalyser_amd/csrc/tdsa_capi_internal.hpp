@@ -2,11 +2,12 @@
 // concern) share: error reporting, the status macros, the host idioms they all use, the few functions that cross files,
 // the plan itself, and - at the end, because they need the plan - Lane, the base of the handle types: their stream,
 // their lifetime, the timer entry points, and the one rule that orders a handle's launches whichever stream each goes
-// on.  Over Lane stand three bases, each with the checks of a call and both entry points: Feed for the streaming filters
+// on.  Over Lane stand four bases, each with the checks of a call and both entry points: Feed for the streaming filters
 // (down-converter, channelizer, demodulator: taps, history, input count), IqAccum for the accumulators over IQ streams
-// (power statistics, pulse analysis, correlation search) and RowAnalyser for the analysers of dB rows (signal detection, channel
-// measurements: the records grown on demand and the tail of a call).  All three stage a host block through Staging.  The
-// public face of the library is include/tdsa_hip.h.
+// (power statistics, pulse analysis, correlation search), RowAnalyser for the analysers of dB rows (signal detection, channel
+// measurements: the records grown on demand and the tail of a call) and SegAnalyser for the analysers of segments
+// (symbol recovery, FSK analysis: the symbol clock, the staged outputs, create and destroy).  All four stage a host
+// block through Staging.  The public face of the library is include/tdsa_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,7 @@
 
 #include "../../include/tdsa_hip.h"
 #include "tdsa_kernels.hpp"
+#include "tdsa_seg.hpp"
 
 namespace tdsa {
 #pragma GCC visibility push(hidden)
@@ -708,6 +710,202 @@ struct RowAnalyser : Lane {
     TRY(h->producer_stream(p, &s));
     TRY(h->order(s));
     return run(h, s, rows, n_rows, row_host, sub_host);
+  }
+};
+
+// What the messages of a segment analyser call it: "null <handle>", "tdsa_<prefix>_configure" and "<prefix> create",
+// "TDSA_<mode>_AUTO or _FIXED", "null <out>".
+struct SegNames {
+  const char *handle, *prefix, *mode, *out;
+};
+
+static_assert(TDSA_SYMSYNC_AUTO == TDSA_FSK_AUTO && TDSA_SYMSYNC_FIXED == TDSA_FSK_FIXED, "one timing_mode for both");
+
+// The base of the segment analysers (symbol recovery, FSK analysis) over Lane: n_seg segments of seg_len samples, `hop`
+// apart, each with the symbol clock of _configure; per segment K outputs into rows out_stride wide, an optional second
+// output of the same shape, and one record in the caller's memory, through a device buffer that grows on demand.  Both
+// entry points return when the records have arrived.  A handle type H supplies
+//   H::who, H::out_unit, H::aux_unit, H::rec_unit   its names; the bytes of an output of either kind and of a record
+//   h->in_unit()                                    the bytes of an input sample
+//   h->symbols(seg_len)                             its K, as a long long that may lie outside 2 .. kSegMaxSymbols
+//   h->aligned(in, out, aux, rec)                   the alignment of a call's pointers, with its own messages
+//   h->launch(s, in, seg_len, hop, n_seg, out, out_stride, aux, K)   its kernel on s, returning a hipError_t
+// and, to create, what it does on the device before there is a handle.
+//
+// The checks of a call come in ONE order (check): null handle, not configured, null samples, null output, null
+// records, alignment, n_seg, hop, K, out_stride; host() adds the block and the staging limit after them, dev() the
+// plan's device.  None of them makes a HIP call.
+struct SegAnalyser : Lane {
+  size_t max_host = 0;             // samples one host call stages
+  float2* d_nco = nullptr;         // [kSegNcoTable]
+  Staging in;                      // of a host block, 8 bytes a sample at most ...
+  char* d_out = nullptr;           // ... of its outputs, [out_cap()] of out_unit bytes, then [out_cap()] of aux_unit ...
+  char* h_out = nullptr;
+  void* d_rec = nullptr;           // ... and of the records of either entry point, grown on demand
+  size_t rec_cap = 0;
+  bool configured = false;
+  uint64_t step = 0, delta_fx = 0;
+  uint32_t nu = 0;
+  int fixed = 0;
+
+  size_t out_cap() const { return max_host / 4 + 1; }   // K n_seg < seg_len n_seg / 4
+
+  // (cos, -sin) of 2 pi k / 4096 from the first quarter turn, so that whole quarter turns are exact
+  static std::vector<float2> nco_table() {
+    std::vector<float2> nco(kSegNcoTable);
+    const int q = kSegNcoTable / 4;
+    for (int k = 0; k < kSegNcoTable; ++k) {
+      const double th = 2.0 * 3.14159265358979323846 * double(k % q) / double(kSegNcoTable);
+      const float c = k % q ? float(std::cos(th)) : 1.0f, s = k % q ? float(std::sin(th)) : 0.0f;
+      const float cs[4] = {c, -s, -c, s}, sn[4] = {s, c, -s, -c};   // cos, sin of th + quarter turns
+      nco[k] = make_float2(cs[k / q], -sn[k / q]);
+    }
+    return nco;
+  }
+
+  // tdsa_<x>_create; prepare() runs on the device before there is a handle and returns a status
+  template <class H, class Prepare>
+  static int create(int device_id, size_t max_host_samples, H** out, Prepare&& prepare) {
+    if (!out) return fail(TDSA_ERR_ARG, "null out");
+    *out = nullptr;
+    if (max_host_samples < 16) return fail(TDSA_ERR_ARG, "max_host_samples=%zu: at least 16", max_host_samples);
+    HIPCHK(hipSetDevice(device_id));
+    TRY(prepare());
+    H* h = new (std::nothrow) H();
+    if (!h) return fail(TDSA_ERR_NOMEM, "out of host memory");
+    h->device = device_id;
+    h->max_host = max_host_samples;
+    const std::vector<float2> nco = nco_table();
+    const size_t out_bytes = h->out_cap() * (H::out_unit + H::aux_unit);
+    hipError_t e = h->open(true);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_nco), kSegNcoTable * sizeof(float2));
+    if (e == hipSuccess) e = h->in.alloc(max_host_samples * sizeof(float2));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_out), out_bytes);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_out), out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_nco, nco.data(), kSegNcoTable * sizeof(float2), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // the host copy of the table is released
+    if (e != hipSuccess) {
+      (void)destroy(h);
+      return fail(TDSA_ERR_HIP, "%s create: %s", H::who.prefix, hipGetErrorString(e));
+    }
+    *out = h;
+    return TDSA_OK;
+  }
+  // tdsa_<x>_destroy, also of a handle whose create failed half way
+  template <class H>
+  static int destroy(H* h) {
+    if (!h) return TDSA_OK;
+    h->drain();
+    free_all({h->d_nco, h->d_out, h->d_rec});
+    h->in.release();
+    if (h->h_out) (void)hipHostFree(h->h_out);
+    h->close();
+    delete h;
+    return TDSA_OK;
+  }
+
+  // The clock of _configure and _symbols_per_segment.  A _configure checks step and nu, then its own arguments, then
+  // the timing, and last hands the clock to the handle, which may be null.
+  static int check_step(uint64_t step) {
+    if (step < kSegMinStep || step > kSegMaxStep)
+      return fail(TDSA_ERR_ARG, "step=%llu: 4 .. 64 samples per symbol in 32.32 fixed point", (unsigned long long)step);
+    return TDSA_OK;
+  }
+  static int check_rate(uint64_t step, uint32_t nu) {
+    TRY(check_step(step));
+    const unsigned __int128 turn = (unsigned __int128)1 << 64;
+    const uint64_t want = uint64_t((turn + step / 2) / step);   // round(2^32 / sps)
+    if (uint64_t(nu) + 1 < want || uint64_t(nu) > want + 1)
+      return fail(TDSA_ERR_ARG, "nu=%u: the phase step of this symbol rate is %llu", nu, (unsigned long long)want);
+    return TDSA_OK;
+  }
+  static int check_timing(const SegNames& who, uint64_t step, int timing_mode, uint64_t delta_fx) {
+    if (timing_mode != TDSA_SYMSYNC_AUTO && timing_mode != TDSA_SYMSYNC_FIXED)
+      return fail(TDSA_ERR_ARG, "timing_mode=%d: TDSA_%s_AUTO or _FIXED", timing_mode, who.mode);
+    if (timing_mode == TDSA_SYMSYNC_FIXED && (delta_fx < kSegOne || delta_fx >= step + kSegOne))
+      return fail(TDSA_ERR_ARG, "delta_fx=%llu: 2^32 <= delta_fx < step + 2^32", (unsigned long long)delta_fx);
+    return TDSA_OK;
+  }
+  static int set_clock(SegAnalyser* h, const SegNames& who, uint64_t step, uint32_t nu, int timing_mode, uint64_t delta_fx) {
+    if (!h) return fail(TDSA_ERR_ARG, "null %s", who.handle);
+    h->step = step;
+    h->nu = nu;
+    h->fixed = timing_mode == TDSA_SYMSYNC_FIXED;
+    h->delta_fx = h->fixed ? delta_fx : 0;
+    h->configured = true;
+    return TDSA_OK;
+  }
+  // what _symbols_per_segment hands back of a K that may lie outside an int
+  static int clamp_k(long long k) { return k < 0 ? 0 : k > 0x7fffffff ? 0x7fffffff : int(k); }
+
+  // the checks both entry points share; *K_out = symbols per segment
+  template <class H>
+  static int check(const H* h, const void* in, size_t seg_len, size_t hop, int n_seg, const void* out, size_t out_stride,
+                   const void* aux, const void* rec, int* K_out) {
+    if (!h) return fail(TDSA_ERR_ARG, "null %s", H::who.handle);
+    if (!h->configured) return fail(TDSA_ERR_STATE, "not configured: call tdsa_%s_configure first", H::who.prefix);
+    if (!in) return fail(TDSA_ERR_ARG, "null samples");
+    if (!out) return fail(TDSA_ERR_ARG, "null %s", H::who.out);
+    if (!rec) return fail(TDSA_ERR_ARG, "null records");
+    TRY(h->aligned(in, out, aux, rec));
+    if (n_seg < 1) return fail(TDSA_ERR_ARG, "n_seg=%d: at least one segment", n_seg);
+    if (hop < 1) return fail(TDSA_ERR_ARG, "hop=%zu: at least one sample", hop);
+    const long long K = h->symbols(seg_len);
+    if (K < 2 || K > kSegMaxSymbols)
+      return fail(TDSA_ERR_ARG, "seg_len=%zu gives %lld symbols per segment: 2 .. %d", seg_len, K, kSegMaxSymbols);
+    if (out_stride < size_t(K)) return fail(TDSA_ERR_ARG, "out_stride=%zu: a segment gives %lld symbols", out_stride, K);
+    *K_out = int(K);
+    return TDSA_OK;
+  }
+
+  // host: through the staging on the handle's own stream, the outputs K wide back to back on the way, the second
+  // kind's behind the room of the first; returns when outputs and records are in the caller's memory
+  template <class H>
+  static int host(H* h, const void* in, size_t n_samples, size_t seg_len, size_t hop, int n_seg, void* out,
+                  size_t out_stride, void* aux, void* rec) {
+    int K = 0;
+    TRY(check(h, in, seg_len, hop, n_seg, out, out_stride, aux, rec, &K));
+    // hop first, so that the product below cannot wrap
+    if (seg_len > n_samples || (n_seg > 1 && hop > (n_samples - seg_len) / (size_t(n_seg) - 1)))
+      return fail(TDSA_ERR_ARG, "%d segments of %zu samples every %zu need %zu samples, the block has %zu", n_seg, seg_len,
+                  hop, (size_t(n_seg) - 1) * hop + seg_len, n_samples);
+    if (n_samples > h->max_host || size_t(n_seg) * seg_len > h->max_host)
+      return fail(TDSA_ERR_ARG, "block of %zu samples in %d segments of %zu, the handle stages at most %zu "
+                  "(max_host_samples)", n_samples, n_seg, seg_len, h->max_host);
+    TRY(h->own_stream());
+    TRY(grow_device(&h->d_rec, &h->rec_cap, size_t(n_seg), h->stream, H::rec_unit));
+    // the previous host call has waited: the staging is free
+    TRY(h->in.fill(h->stream, in, 1, n_samples, n_samples, h->in_unit()));
+    const size_t rows = size_t(n_seg) * size_t(K), aux_at = h->out_cap() * H::out_unit;
+    HIPCHK(h->launch(h->stream, h->in.d_in, seg_len, hop, n_seg, h->d_out, size_t(K), aux ? h->d_out + aux_at : nullptr, K));
+    TRY(h->done(h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, rows * H::out_unit, hipMemcpyDeviceToHost, h->stream));
+    if (aux) HIPCHK(hipMemcpyAsync(h->h_out + aux_at, h->d_out + aux_at, rows * H::aux_unit, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(rec, h->d_rec, size_t(n_seg) * H::rec_unit, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t orow = size_t(K) * H::out_unit, arow = size_t(K) * H::aux_unit;
+    for (size_t s = 0; s < size_t(n_seg); ++s) {
+      std::memcpy(static_cast<char*>(out) + s * out_stride * H::out_unit, h->h_out + s * orow, orow);
+      if (aux) std::memcpy(static_cast<char*>(aux) + s * out_stride * H::aux_unit, h->h_out + aux_at + s * arow, arow);
+    }
+    return TDSA_OK;
+  }
+  // dev: in place, on plan p's stream (null: the handle's own)
+  template <class H>
+  static int dev(H* h, tdsa_plan p, const void* in, size_t seg_len, size_t hop, int n_seg, void* out, size_t out_stride,
+                 void* aux, void* rec) {
+    int K = 0;
+    TRY(check(h, in, seg_len, hop, n_seg, out, out_stride, aux, rec, &K));
+    if (p && p->device != h->device) return fail(TDSA_ERR_ARG, "plan and %s live on different devices", H::who.handle);
+    hipStream_t s;
+    TRY(h->producer_stream(p, &s));
+    TRY(h->order(s));
+    TRY(grow_device(&h->d_rec, &h->rec_cap, size_t(n_seg), h->last, H::rec_unit));
+    HIPCHK(h->launch(s, in, seg_len, hop, n_seg, out, out_stride, aux, K));
+    HIPCHK(hipMemcpyAsync(rec, h->d_rec, size_t(n_seg) * H::rec_unit, hipMemcpyDeviceToHost, s));
+    TRY(h->done(s));
+    HIPCHK(hipStreamSynchronize(s));   // the records are the call's result: they are in the caller's memory on return
+    return TDSA_OK;
   }
 };
 

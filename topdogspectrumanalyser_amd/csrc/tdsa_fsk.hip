@@ -19,6 +19,7 @@
 
 #include "tdsa_fsk.hpp"
 #include "tdsa_fsk_math.hpp"
+#include "tdsa_seg_block.hpp"
 
 // every rounding below is written out
 #pragma clang fp contract(off)
@@ -26,53 +27,7 @@
 namespace tdsa {
 namespace {
 
-constexpr int kT = kFskThreads;
-
-__device__ inline float2 rot(const float2* nco, uint32_t p) {
-  const float2 h = nco[p >> 20];
-  float2 r;
-  sym_rot(p, h.x, h.y, &r.x, &r.y);
-  return r;
-}
-
-// The workgroup's fold of one 16-byte slot a thread, every thread gets the result; the first barrier frees `red` from
-// its last use.  fold(p, q) combines the slots of threads t and t + o into t's.
-template <class T, class Fold>
-__device__ inline T block_fold(T v, T* red, int tid, Fold fold) {
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int o = kT / 2; o >= 1; o >>= 1) {
-    if (tid < o) red[tid] = fold(red[tid], red[tid + o]);
-    __syncthreads();
-  }
-  return red[0];
-}
-
-__device__ inline float4 block_sum3(float x, float y, float z, float4* red, int tid) {
-  return block_fold(make_float4(x, y, z, 0.0f), red, tid,
-                    [](float4 p, float4 q) { return make_float4(p.x + q.x, p.y + q.y, p.z + q.z, 0.0f); });
-}
-__device__ inline double2 block_sum2(double x, double y, double2* red, int tid) {
-  return block_fold(make_double2(x, y), red, tid, [](double2 p, double2 q) { return make_double2(p.x + q.x, p.y + q.y); });
-}
-// integers: exact, whatever the tree
-__device__ inline int4 block_sum2i(int x, int y, int4* red, int tid) {
-  return block_fold(make_int4(x, y, 0, 0), red, tid, [](int4 p, int4 q) { return make_int4(p.x + q.x, p.y + q.y, 0, 0); });
-}
-// .x the smallest, .y the largest, .z above zero where any thread's is: its flag for a value that is not finite
-__device__ inline float4 block_minmax(float lo, float hi, float bad, float4* red, int tid) {
-  return block_fold(make_float4(lo, hi, bad, 0.0f), red, tid, [](float4 p, float4 q) {
-    return make_float4(q.x < p.x ? q.x : p.x, q.y > p.y ? q.y : p.y, q.z > p.z ? q.z : p.z, 0.0f);
-  });
-}
-// (value, index) pairs: the largest value, among equals the lowest index - an order, so any tree gives the same pair
-__device__ inline float4 block_argmax(float best, int idx, float4* red, int tid) {
-  return block_fold(make_float4(best, __int_as_float(idx), 0.0f, 0.0f), red, tid, [](float4 p, float4 q) {
-    const int pi = __float_as_int(p.y), qi = __float_as_int(q.y);
-    return q.x > p.x || (q.x == p.x && qi < pi) ? q : p;
-  });
-}
+constexpr int kT = kSegThreads;
 
 // d_j of a segment: the phase step from x[j] to x[j + 1] in half turns, or the input itself
 template <int KIND>

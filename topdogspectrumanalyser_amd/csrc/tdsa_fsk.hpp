@@ -4,21 +4,18 @@
 
 #include <cstdint>
 
+#include "tdsa_seg.hpp"
+
 namespace tdsa {
 
-constexpr int kFskThreads = 256;
-constexpr int kFskMaxSymbols = 4096;                 // K per segment
 constexpr int kFskMaxBoxcar = 64;                    // B
 constexpr int kFskMaxLag = 64;                       // L
-constexpr int kFskNcoTable = 4096;                   // the rotation's table: the top 12 phase bits
 constexpr int kFskTile = 1024;                       // stage 2: differences e_j per tile, a multiple of the workgroup
 constexpr int kFskTileB = kFskTile + kFskMaxLag;     // ... the b_j they need ...
 constexpr int kFskTileD = kFskTileB + kFskMaxBoxcar; // ... and the d_j those need (one spare)
 // the two reductions' scratch (16 bytes a thread each), the tile's d and b, the segment's scalars
-constexpr int kFskStaticLdsBytes = 2 * kFskThreads * 16 + (kFskTileB + kFskTileD) * 4 + 64;
-constexpr int kFskMaxLdsBytes = kFskMaxSymbols * 4 + kFskStaticLdsBytes;   // v[K] beside them: under 34 KiB of the CU's 160
-constexpr uint64_t kFskOne = uint64_t(1) << 32;      // one sample in 32.32
-constexpr uint64_t kFskMinStep = 4 * kFskOne, kFskMaxStep = 64 * kFskOne;
+constexpr int kFskStaticLdsBytes = 2 * kSegThreads * 16 + (kFskTileB + kFskTileD) * 4 + 64;
+constexpr int kFskMaxLdsBytes = kSegMaxSymbols * 4 + kFskStaticLdsBytes;   // v[K] beside them: under 34 KiB of the CU's 160
 
 constexpr int kFskIq = 0, kFskFreq = 1;              // the input kinds (include/tdsa_hip.h: TDSA_FSK_IQ, _FREQ)
 constexpr unsigned kFskFlagNonFinite = 1u;           // P, C or a v_k is not finite: NaN levels, zero indices, a zero record
@@ -61,7 +58,7 @@ struct FskLaunch {
   int fixed = 0;                 // timing: 1 = delta_fx below instead of stage 2's
   uint64_t delta_fx = 0;
   int K = 0;
-  const float2* nco = nullptr;   // [kFskNcoTable] (cos, -sin) of 2 pi k / 4096
+  const float2* nco = nullptr;   // [kSegNcoTable] (cos, -sin) of 2 pi k / 4096
   float* out = nullptr;          // [n_seg][out_stride] the levels v
   uint8_t* idx = nullptr;        // the same shape, the indices i of the second round, or null
   long long out_stride = 0;

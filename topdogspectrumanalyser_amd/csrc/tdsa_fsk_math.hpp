@@ -22,19 +22,15 @@ TDSA_HD inline float fsk_level_scale(int levels) { return 1.0f / float(2 * (leve
 // floor(t step), then L / 2 samples on to where the transitions lie among the b_j, half a symbol on to the symbol
 // centres, modulo step and into [2^32, step + 2^32).  All in integers.
 TDSA_HD inline uint64_t fsk_delta_from_t(float t, uint64_t step, int lag) {
-  const uint64_t tq = uint64_t(t * 0x1p32f);        // <= 2^32
-  const uint64_t sh = step >> 32, sl = step & 0xffffffffu;
-  uint64_t d = tq * sh + ((tq * sl) >> 32);         // floor(tq step / 2^32) without overflow
+  uint64_t d = sym_phase_to_samples(t, step);
   d += (uint64_t(lag) << 31) + (step >> 1);
   d %= step;
   if (d < (uint64_t(1) << 32)) d += step;
   return d;
 }
-// ... from the spectral line C of e: a = arg C / pi, t = -a / 2 (+ 1 if negative), as sym_delta forms it
+// ... from the spectral line C of e, as sym_delta takes its t
 TDSA_HD inline uint64_t fsk_delta(float c_re, float c_im, uint64_t step, int lag) {
-  float t = demod_atan2_over_pi(c_im, c_re) * -0.5f;
-  if (t < 0.0f) t = t + 1.0f;
-  return fsk_delta_from_t(t, step, lag);
+  return fsk_delta_from_t(sym_clock_phase(c_re, c_im), step, lag);
 }
 
 // Stage 4's first guess from the extremes: o = (hi + lo) / 2, g = (hi - lo) float32(1 / (2 (M - 1)))

@@ -14,6 +14,7 @@
 // n_seg or on which segment it is.  The arithmetic is tdsa_symsync_math.hpp's.
 #include <hip/hip_runtime.h>
 
+#include "tdsa_seg_block.hpp"
 #include "tdsa_symsync.hpp"
 #include "tdsa_symsync_math.hpp"
 
@@ -23,14 +24,7 @@
 namespace tdsa {
 namespace {
 
-constexpr int kT = kSymThreads;
-
-__device__ inline float2 rot(const float2* nco, uint32_t p) {
-  const float2 h = nco[p >> 20];
-  float2 r;
-  sym_rot(p, h.x, h.y, &r.x, &r.y);
-  return r;
-}
+constexpr int kT = kSegThreads;
 
 __device__ inline float2 cmul(float2 a, float2 b) {
   float2 r;
@@ -42,44 +36,6 @@ __device__ inline float2 power(float2 y, int order) {
   float2 z;
   sym_pow(y.x, y.y, order, &z.x, &z.y);
   return z;
-}
-
-// four sums over the workgroup at once, every thread gets them; the first barrier frees `red` from its last use
-__device__ inline float4 block_sum4(float4 v, float4* red, int tid) {
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int o = kT / 2; o >= 1; o >>= 1) {
-    if (tid < o) {
-      const float4 p = red[tid], q = red[tid + o];
-      red[tid] = make_float4(p.x + q.x, p.y + q.y, p.z + q.z, p.w + q.w);
-    }
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// (value, index) pairs: the largest value, among equals the lowest index - an order, so any tree gives the same pair;
-// .z rides along as a sum
-__device__ inline float4 block_argmax(float best, int idx, float tot, float4* red, int tid) {
-  __syncthreads();
-  red[tid] = make_float4(best, __int_as_float(idx), tot, 0.0f);
-  __syncthreads();
-  for (int o = kT / 2; o >= 1; o >>= 1) {
-    if (tid < o) {
-      float4 p = red[tid];
-      const float4 q = red[tid + o];
-      const int pi = __float_as_int(p.y), qi = __float_as_int(q.y);
-      if (q.x > p.x || (q.x == p.x && qi < pi)) {
-        p.x = q.x;
-        p.y = q.y;
-      }
-      p.z = p.z + q.z;
-      red[tid] = p;
-    }
-    __syncthreads();
-  }
-  return red[0];
 }
 
 __global__ __launch_bounds__(kT) void symsync_kernel(SymLaunch a) {
@@ -169,7 +125,7 @@ __global__ __launch_bounds__(kT) void symsync_kernel(SymLaunch a) {
       bi = g;
     }
   }
-  const float4 am = block_argmax(best, bi, tot, red, tid);
+  const float4 am = block_argmax_sum(best, bi, tot, red, tid);
   uint32_t step_f = 0, theta = 0;
   if (isfinite(am.z)) {
     const int gs = __float_as_int(am.y);

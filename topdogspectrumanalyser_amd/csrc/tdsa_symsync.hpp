@@ -4,16 +4,13 @@
 
 #include <cstdint>
 
+#include "tdsa_seg.hpp"
+
 namespace tdsa {
 
-constexpr int kSymThreads = 256;
-constexpr int kSymMaxSymbols = 4096;                 // K per segment
-constexpr int kSymMaxGrid = 2 * kSymMaxSymbols;      // G, the carrier transform's length
-constexpr int kSymNcoTable = 4096;                   // the rotation's table: the top 12 phase bits
-constexpr int kSymStaticLdsBytes = kSymThreads * 16 + 64;     // the reduction's scratch and the segment's scalars
-constexpr int kSymMaxLdsBytes = (kSymMaxSymbols + kSymMaxGrid) * 8 + kSymStaticLdsBytes;   // ~100 KiB of the CU's 160
-constexpr uint64_t kSymOne = uint64_t(1) << 32;      // one sample in 32.32
-constexpr uint64_t kSymMinStep = 4 * kSymOne, kSymMaxStep = 64 * kSymOne;
+constexpr int kSymMaxGrid = 2 * kSegMaxSymbols;      // G, the carrier transform's length
+constexpr int kSymStaticLdsBytes = kSegThreads * 16 + 64;     // the reduction's scratch and the segment's scalars
+constexpr int kSymMaxLdsBytes = (kSegMaxSymbols + kSymMaxGrid) * 8 + kSymStaticLdsBytes;   // ~100 KiB of the CU's 160
 
 constexpr unsigned kSymFlagNonFinite = 1u;           // P or C is not finite: NaN symbols, a zero record
 constexpr unsigned kSymFlagCarrier = 2u;             // the carrier transform's peak is not finite: step_f = theta_fx = 0
@@ -51,7 +48,7 @@ struct SymLaunch {
   int fixed = 0;                 // timing: 1 = delta_fx below instead of stage 1's
   uint64_t delta_fx = 0;
   int K = 0, log2G = 0;
-  const float2* nco = nullptr;   // [kSymNcoTable] (cos, -sin) of 2 pi k / 4096
+  const float2* nco = nullptr;   // [kSegNcoTable] (cos, -sin) of 2 pi k / 4096
   float2* sym = nullptr;         // [n_seg][out_stride]
   float2* raw = nullptr;         // the same shape, the symbols before derotation, or null
   long long out_stride = 0;

@@ -63,15 +63,23 @@ TDSA_HD inline void sym_rot(uint32_t p, float hx, float hy, float* rr, float* ri
   *ri = hy + fmaf(hy, cm1, hx * sl);
 }
 
-// Stage 1's end: the timing offset from the spectral line C of |x|^2, in 32.32 samples.  a = arg C / pi, t = -a / 2
-// (+ 1 if negative), floor(t step) with t taken to 32 fractional bits, + step below one sample: in [2^32, step + 2^32).
-TDSA_HD inline uint64_t sym_delta(float c_re, float c_im, uint64_t step) {
-  float t = demod_atan2_over_pi(c_im, c_re) * -0.5f;
-  if (t < 0.0f) t = t + 1.0f;
+// The clock phase of a spectral line C at the symbol rate, in symbols: a = arg C / pi, t = -a / 2 (+ 1 if negative),
+// 0 <= t <= 1 ...
+TDSA_HD inline float sym_clock_phase(float c_re, float c_im) {
+  const float t = demod_atan2_over_pi(c_im, c_re) * -0.5f;
+  return t < 0.0f ? t + 1.0f : t;
+}
+// ... and floor(t step) with t taken to 32 fractional bits: (tq * step) >> 32 without overflow, step = sh 2^32 + sl
+TDSA_HD inline uint64_t sym_phase_to_samples(float t, uint64_t step) {
   const uint64_t tq = uint64_t(t * 0x1p32f);        // <= 2^32
-  // (tq * step) >> 32 without overflow: step = sh 2^32 + sl
   const uint64_t sh = step >> 32, sl = step & 0xffffffffu;
-  uint64_t d = tq * sh + ((tq * sl) >> 32);
+  return tq * sh + ((tq * sl) >> 32);
+}
+
+// Stage 1's end: the timing offset from the spectral line C of |x|^2, in 32.32 samples: floor(t step), + step below
+// one sample: in [2^32, step + 2^32).
+TDSA_HD inline uint64_t sym_delta(float c_re, float c_im, uint64_t step) {
+  uint64_t d = sym_phase_to_samples(sym_clock_phase(c_re, c_im), step);
   if (d < (uint64_t(1) << 32)) d += step;
   return d;
 }

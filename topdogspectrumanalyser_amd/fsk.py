@@ -17,8 +17,9 @@ from typing import Optional, Union
 import numpy as np
 
 from . import _native as nat
+from ._inputs import _Segments
 from .engine import SpectrumEngine
-from .symbols import MAX_SPS, MAX_SYMBOLS, MIN_SPS, ONE, fixed_step, phase_step
+from .symbols import MAX_SPS, MAX_SYMBOLS, MIN_SPS, ONE, fixed_step, phase_step  # noqa: F401  (importable from here)
 from .zoom import check_same_device
 
 MAX_BOXCAR = MAX_LAG = 64
@@ -99,8 +100,6 @@ def result_from(records: np.ndarray, levels, indices, K: int, M: int, sps: float
     """The derived figures of a call's records."""
     r = records
     with np.errstate(all="ignore"):
-        p = r["p"].astype(np.float64)
-        q = np.where(p > 0, np.hypot(r["c_re"].astype(np.float64), r["c_im"].astype(np.float64)) / np.where(p > 0, p, 1.0), 0.0)
         g = r["dev"].astype(np.float64)
         outer = g * (M - 1)
         ok = outer > 0
@@ -109,11 +108,11 @@ def result_from(records: np.ndarray, levels, indices, K: int, M: int, sps: float
         pe = np.where(ok, r["err_peak"].astype(np.float64) / np.where(ok, outer, 1.0), 0.0)
     delay = boxcar / 2.0 if kind == nat.FSK_IQ else (boxcar - 1) / 2.0
     h = g * sps if kind == nat.FSK_IQ else np.full(r.size, np.nan)
-    return FskResult(levels, indices, r["delta_fx"].astype(np.float64) / ONE + delay, q, r["offset"].astype(np.float64), outer,
-                     h, fe, pe, r["flags"].copy(), r, M)
+    return FskResult(levels, indices, r["delta_fx"].astype(np.float64) / ONE + delay, _Segments.timing_quality(r),
+                     r["offset"].astype(np.float64), outer, h, fe, pe, r["flags"].copy(), r, M)
 
 
-class FskAnalyzer(nat._Handle, nat._Timer):
+class FskAnalyzer(_Segments, nat._Handle, nat._Timer):
     """FSK analysis of segments at `samples_per_symbol` (4 .. 64, any real number).
 
     levels: 2, 4, 8 or "msk" (2).  input: "iq" (complex64) or "freq" (float32, a frequency already).  timing: "auto" (the
@@ -122,38 +121,26 @@ class FskAnalyzer(nat._Handle, nat._Timer):
     each - with B = L = 1 the clock drowns in noise from 8 samples per symbol upward."""
     _destroy = "tdsa_fsk_destroy"
     _timer = ("tdsa_fsk_timer_begin", "tdsa_fsk_timer_end")
+    _process = ("tdsa_fsk_process", "tdsa_fsk_process_dev")
+    _record = RECORD
+    _filled = ((SENTINEL, np.float32), (SENTINEL_INDEX, np.uint8))
 
     def __init__(self, samples_per_symbol: float, levels: Union[int, str] = 2, input: str = "iq",
                  timing: Union[str, float] = "auto", boxcar: Optional[int] = None, lag: Optional[int] = None, device: int = 0,
                  max_host_samples: int = 1 << 20):
-        sps = float(samples_per_symbol)
-        if not MIN_SPS <= sps <= MAX_SPS:
-            raise ValueError(f"samples_per_symbol={samples_per_symbol}: {MIN_SPS:g} .. {MAX_SPS:g}")
-        self.samples_per_symbol = sps
-        self.step, self.nu = fixed_step(sps), phase_step(sps)
+        self._rate(samples_per_symbol)
         self.levels = level_count(levels)
         if input not in KINDS:
             raise ValueError(f"input={input!r}: 'iq' or 'freq'")
         self.input, self.kind = input, KINDS[input]
-        half = max(1, int(math.floor(sps / 2)))
+        half = max(1, int(math.floor(self.samples_per_symbol / 2)))
         self.boxcar = half if boxcar is None else int(boxcar)
         self.lag = half if lag is None else int(lag)
         if not 1 <= self.boxcar <= MAX_BOXCAR:
             raise ValueError(f"boxcar={boxcar}: 1 .. {MAX_BOXCAR}")
         if not 1 <= self.lag <= MAX_LAG:
             raise ValueError(f"lag={lag}: 1 .. {MAX_LAG}")
-        if isinstance(timing, str):
-            if timing != "auto":
-                raise ValueError(f"timing={timing!r}: 'auto' or the first symbol's position in samples")
-            self.timing_mode, self.delta_fx = nat.FSK_AUTO, 0
-        else:
-            self.timing_mode, self.delta_fx = nat.FSK_FIXED, int(round(float(timing) * ONE))
-            if not ONE <= self.delta_fx < self.step + ONE:
-                raise ValueError(f"timing={timing}: 1 <= timing < samples_per_symbol + 1")
-        self.device = int(device)
-        self.max_host_samples = int(max_host_samples)
-        if self.max_host_samples < 16:
-            raise ValueError(f"max_host_samples={max_host_samples}: at least 16")
+        self._stage(timing, device, max_host_samples)
         self._h = C.c_void_p()
         nat.check(nat.lib.tdsa_fsk_create(self.device, self.max_host_samples, C.byref(self._h)))
         nat.check(nat.lib.tdsa_fsk_configure(self._h, self.step, self.nu, self.levels, self.kind, self.boxcar, self.lag,
@@ -163,22 +150,8 @@ class FskAnalyzer(nat._Handle, nat._Timer):
     def _unit(self) -> int:
         return 8 if self.kind == nat.FSK_IQ else 4
 
-    def symbols_per_segment(self, seg_len: int) -> int:
-        """K of a segment of seg_len samples; ValueError outside 2 .. 4096."""
-        K = symbols_per_segment(self.step, seg_len, self.kind, self.boxcar)
-        if not 2 <= K <= MAX_SYMBOLS:
-            raise ValueError(f"seg_len={seg_len} gives {K} symbols per segment: 2 .. {MAX_SYMBOLS}")
-        return K
-
-    def _check(self, seg_len: int, hop: int, n_seg: int, out_stride: int) -> int:
-        K = self.symbols_per_segment(seg_len)
-        if int(hop) < 1:
-            raise ValueError(f"hop={hop}: at least one sample")
-        if int(n_seg) < 1:
-            raise ValueError(f"n_seg={n_seg}: at least one segment")
-        if int(out_stride) < K:
-            raise ValueError(f"out_stride={out_stride}: a segment gives {K} symbols")
-        return K
+    def _k(self, seg_len: int) -> int:
+        return symbols_per_segment(self.step, seg_len, self.kind, self.boxcar)
 
     def _result(self, rec, levels, indices, K) -> FskResult:
         return result_from(rec, levels, indices, K, self.levels, self.samples_per_symbol, self.kind, self.boxcar)
@@ -191,27 +164,7 @@ class FskAnalyzer(nat._Handle, nat._Timer):
             raise ValueError(f"input of dtype {a.dtype} and shape {a.shape}: one "
                              f"{'complex' if self.kind == nat.FSK_IQ else 'real'} stream")
         a = np.ascontiguousarray(a, dtype=np.complex64 if self.kind == nat.FSK_IQ else np.float32)
-        seg_len = int(seg_len)
-        hop = seg_len if hop is None else int(hop)
-        if a.size < seg_len:
-            raise ValueError(f"{a.size} samples: less than one segment of {seg_len}")
-        n_seg = (a.size - seg_len) // max(hop, 1) + 1
-        K = self.symbols_per_segment(seg_len)
-        stride = K if out_stride is None else int(out_stride)
-        self._check(seg_len, hop, n_seg, stride)
-        used = (n_seg - 1) * hop + seg_len
-        if used > self.max_host_samples or n_seg * seg_len > self.max_host_samples:
-            raise ValueError(f"{n_seg} segments of {seg_len} samples: the handle stages at most {self.max_host_samples} "
-                             "(max_host_samples)")
-        lev = np.full((n_seg, stride), SENTINEL, dtype=np.float32)
-        idx = np.full((n_seg, stride), SENTINEL_INDEX, dtype=np.uint8) if indices else None
-        rec = np.zeros(n_seg, dtype=RECORD)
-        nat.check(nat.lib.tdsa_fsk_process(self._h, a.ctypes.data_as(C.c_void_p), used, seg_len, hop, n_seg,
-                                           lev.ctypes.data_as(C.c_void_p), stride,
-                                           idx.ctypes.data_as(C.c_void_p) if indices else None,
-                                           rec.ctypes.data_as(C.c_void_p)))
-        if out_stride is None:
-            return self._result(rec, lev[:, :K], idx[:, :K] if indices else None, K)
+        K, rec, lev, idx = self._host(a, seg_len, hop, out_stride, indices)
         return self._result(rec, lev, idx, K)
 
     def process_device(self, engine: Optional[SpectrumEngine], ptr: int, seg_len: int, hop: int, n_seg: int, out_ptr: int,
@@ -230,7 +183,7 @@ class FskAnalyzer(nat._Handle, nat._Timer):
         if engine is not None:
             check_same_device(engine.device, self.device)
         rec = np.zeros(int(n_seg), dtype=RECORD)
-        nat.check(nat.lib.tdsa_fsk_process_dev(self._h, engine._h if engine is not None else None, C.c_void_p(ptr),
-                                               int(seg_len), int(hop), int(n_seg), C.c_void_p(out_ptr), int(out_stride),
-                                               C.c_void_p(idx_ptr) if idx_ptr else None, rec.ctypes.data_as(C.c_void_p)))
+        nat.check(getattr(nat.lib, self._process[1])(self._h, engine._h if engine is not None else None, C.c_void_p(ptr),
+                                                     int(seg_len), int(hop), int(n_seg), C.c_void_p(out_ptr), int(out_stride),
+                                                     C.c_void_p(idx_ptr) if idx_ptr else None, rec.ctypes.data_as(C.c_void_p)))
         return self._result(rec, None, None, K)

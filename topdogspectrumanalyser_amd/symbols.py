@@ -16,13 +16,11 @@ from typing import Optional, Union
 import numpy as np
 
 from . import _native as nat
+from ._inputs import MAX_SPS, MAX_SYMBOLS, MIN_SPS, ONE, _Segments, fixed_step, phase_step  # noqa: F401  (fsk.py, tests)
 from .analytics import constellation_points
 from .engine import SpectrumEngine
 from .zoom import check_same_device
 
-ONE = 1 << 32
-MIN_SPS, MAX_SPS = 4.0, 64.0
-MAX_SYMBOLS = 4096
 ORDERS = {"bpsk": 2, "qpsk": 4, "16qam": 4, "64qam": 4, "8psk": 8}
 
 RECORD = np.dtype([("delta_fx", np.uint64), ("c_re", np.float32), ("c_im", np.float32), ("p", np.float32),
@@ -78,16 +76,6 @@ def reference_phase(points, M: int) -> float:
     return float(np.angle(np.sum(p ** int(M))))
 
 
-def fixed_step(samples_per_symbol: float) -> int:
-    """round(sps 2^32): samples per symbol in 32.32 fixed point."""
-    return int(round(float(samples_per_symbol) * ONE))
-
-
-def phase_step(samples_per_symbol: float) -> int:
-    """round(2^32 / sps): the symbol clock's phase step per sample."""
-    return int(round(ONE / float(samples_per_symbol)))
-
-
 def symbols_per_segment(step: int, seg_len: int) -> int:
     """K = floor((seg_len - 4) 2^32 / step) - 1 (negative for a segment too short to ask)."""
     return ((int(seg_len) - 4) * ONE) // int(step) - 1 if int(seg_len) >= 4 else -1
@@ -117,14 +105,12 @@ def result_from(records: np.ndarray, symbols: np.ndarray, raw: Optional[np.ndarr
     """The derived figures of a call's records."""
     r = records
     with np.errstate(all="ignore"):
-        p = r["p"].astype(np.float64)
-        q = np.where(p > 0, np.hypot(r["c_re"].astype(np.float64), r["c_im"].astype(np.float64)) / np.where(p > 0, p, 1.0), 0.0)
         lock = np.where(r["mean"] > 0, r["peak"].astype(np.float64) / np.where(r["mean"] > 0, r["mean"], 1.0), 0.0)
-    return SymbolResult(symbols, r["delta_fx"].astype(np.float64) / ONE, q, r["step_f"].astype(np.int32) / float(ONE),
-                        r["theta_fx"].astype(np.int32) * (2.0 * math.pi / ONE), lock, r["flags"].copy(), r, raw)
+    return SymbolResult(symbols, r["delta_fx"].astype(np.float64) / ONE, _Segments.timing_quality(r),
+                        r["step_f"].astype(np.int32) / float(ONE), r["theta_fx"].astype(np.int32) * (2.0 * math.pi / ONE), lock, r["flags"].copy(), r, raw)
 
 
-class SymbolSync(nat._Handle, nat._Timer):
+class SymbolSync(_Segments, nat._Handle, nat._Timer):
     """Symbol recovery of complex64 segments at `samples_per_symbol` (4 .. 64, any real number).
 
     modulation: names the carrier order and the reference phase (or pass order= and ref_arg= yourself).  timing: "auto"
@@ -132,15 +118,14 @@ class SymbolSync(nat._Handle, nat._Timer):
     carrier=False leaves stage 3 and 4 out: the symbols are the resampler's."""
     _destroy = "tdsa_symsync_destroy"
     _timer = ("tdsa_symsync_timer_begin", "tdsa_symsync_timer_end")
+    _process = ("tdsa_symsync_process", "tdsa_symsync_process_dev")
+    _record = RECORD
+    _filled = ((SENTINEL, np.complex64), (SENTINEL, np.complex64))
 
     def __init__(self, samples_per_symbol: float, modulation: str = "qpsk", timing: Union[str, float] = "auto",
                  carrier: bool = True, device: int = 0, max_host_samples: int = 1 << 20, order: Optional[int] = None,
                  ref_arg: Optional[float] = None):
-        sps = float(samples_per_symbol)
-        if not MIN_SPS <= sps <= MAX_SPS:
-            raise ValueError(f"samples_per_symbol={samples_per_symbol}: {MIN_SPS:g} .. {MAX_SPS:g}")
-        self.samples_per_symbol = sps
-        self.step, self.nu = fixed_step(sps), phase_step(sps)
+        self._rate(samples_per_symbol)
         self.modulation = str(modulation).lower()
         if not carrier:
             self.order, self.ref_arg = 0, 0.0
@@ -154,39 +139,14 @@ class SymbolSync(nat._Handle, nat._Timer):
             self.ref_arg = float(ref_arg)
             if not math.isfinite(self.ref_arg):
                 raise ValueError(f"ref_arg={ref_arg}")
-        if isinstance(timing, str):
-            if timing != "auto":
-                raise ValueError(f"timing={timing!r}: 'auto' or the first symbol's position in samples")
-            self.timing_mode, self.delta_fx = nat.SYMSYNC_AUTO, 0
-        else:
-            self.timing_mode, self.delta_fx = nat.SYMSYNC_FIXED, int(round(float(timing) * ONE))
-            if not ONE <= self.delta_fx < self.step + ONE:
-                raise ValueError(f"timing={timing}: 1 <= timing < samples_per_symbol + 1")
-        self.device = int(device)
-        self.max_host_samples = int(max_host_samples)
-        if self.max_host_samples < 16:
-            raise ValueError(f"max_host_samples={max_host_samples}: at least 16")
+        self._stage(timing, device, max_host_samples)
         self._h = C.c_void_p()
         nat.check(nat.lib.tdsa_symsync_create(self.device, self.max_host_samples, C.byref(self._h)))
         nat.check(nat.lib.tdsa_symsync_configure(self._h, self.step, self.nu, self.order, self.ref_arg, self.timing_mode,
                                                  self.delta_fx))
 
-    def symbols_per_segment(self, seg_len: int) -> int:
-        """K of a segment of seg_len samples; ValueError outside 2 .. 4096."""
-        K = symbols_per_segment(self.step, seg_len)
-        if not 2 <= K <= MAX_SYMBOLS:
-            raise ValueError(f"seg_len={seg_len} gives {K} symbols per segment: 2 .. {MAX_SYMBOLS}")
-        return K
-
-    def _check(self, seg_len: int, hop: int, n_seg: int, out_stride: int) -> int:
-        K = self.symbols_per_segment(seg_len)
-        if int(hop) < 1:
-            raise ValueError(f"hop={hop}: at least one sample")
-        if int(n_seg) < 1:
-            raise ValueError(f"n_seg={n_seg}: at least one segment")
-        if int(out_stride) < K:
-            raise ValueError(f"out_stride={out_stride}: a segment gives {K} symbols")
-        return K
+    def _k(self, seg_len: int) -> int:
+        return symbols_per_segment(self.step, seg_len)
 
     def process(self, x, seg_len: int, hop: Optional[int] = None, raw: bool = False,
                 out_stride: Optional[int] = None) -> SymbolResult:
@@ -195,27 +155,7 @@ class SymbolSync(nat._Handle, nat._Timer):
         if not np.iscomplexobj(a) or a.ndim != 1:
             raise ValueError(f"input of dtype {a.dtype} and shape {a.shape}: one complex stream")
         a = np.ascontiguousarray(a, dtype=np.complex64)
-        seg_len = int(seg_len)
-        hop = seg_len if hop is None else int(hop)
-        if a.size < seg_len:
-            raise ValueError(f"{a.size} samples: less than one segment of {seg_len}")
-        n_seg = (a.size - seg_len) // max(hop, 1) + 1
-        K = self.symbols_per_segment(seg_len)
-        stride = K if out_stride is None else int(out_stride)
-        self._check(seg_len, hop, n_seg, stride)
-        used = (n_seg - 1) * hop + seg_len
-        if used > self.max_host_samples or n_seg * seg_len > self.max_host_samples:
-            raise ValueError(f"{n_seg} segments of {seg_len} samples: the handle stages at most {self.max_host_samples} "
-                             "(max_host_samples)")
-        sym = np.full((n_seg, stride), SENTINEL, dtype=np.complex64)
-        rw = sym.copy() if raw else None
-        rec = np.zeros(n_seg, dtype=RECORD)
-        nat.check(nat.lib.tdsa_symsync_process(self._h, a.ctypes.data_as(C.c_void_p), used, seg_len, hop, n_seg,
-                                               sym.ctypes.data_as(C.c_void_p), stride,
-                                               rw.ctypes.data_as(C.c_void_p) if raw else None,
-                                               rec.ctypes.data_as(C.c_void_p)))
-        if out_stride is None:
-            return result_from(rec, sym[:, :K], rw[:, :K] if raw else None)
+        _, rec, sym, rw = self._host(a, seg_len, hop, out_stride, raw)
         return result_from(rec, sym, rw)
 
     def process_device(self, engine: Optional[SpectrumEngine], ptr: int, seg_len: int, hop: int, n_seg: int, out_ptr: int,
@@ -232,9 +172,9 @@ class SymbolSync(nat._Handle, nat._Timer):
         if engine is not None:
             check_same_device(engine.device, self.device)
         rec = np.zeros(int(n_seg), dtype=RECORD)
-        nat.check(nat.lib.tdsa_symsync_process_dev(self._h, engine._h if engine is not None else None, C.c_void_p(ptr),
-                                                   int(seg_len), int(hop), int(n_seg), C.c_void_p(out_ptr),
-                                                   int(out_stride), C.c_void_p(raw_ptr) if raw_ptr else None,
-                                                   rec.ctypes.data_as(C.c_void_p)))
+        nat.check(getattr(nat.lib, self._process[1])(self._h, engine._h if engine is not None else None, C.c_void_p(ptr),
+                                                     int(seg_len), int(hop), int(n_seg), C.c_void_p(out_ptr),
+                                                     int(out_stride), C.c_void_p(raw_ptr) if raw_ptr else None,
+                                                     rec.ctypes.data_as(C.c_void_p)))
         return result_from(rec, None)
 
