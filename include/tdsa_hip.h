@@ -588,6 +588,59 @@ int tdsa_fsk_symbols_per_segment(uint64_t step, size_t seg_len, int input_kind, 
 int tdsa_fsk_timer_begin(tdsa_fsk h);
 int tdsa_fsk_timer_end(tdsa_fsk h, float* elapsed_ms);
 
+/* -------- eye diagrams: I / Q and FSK eyes on a recovered symbol clock ------------------------
+ * Folds segments of a stream on one symbol clock per segment - the one the symbol recovery or the FSK analysis has just
+ * put into its record, or the caller's - into a density image of P columns over one symbol by H rows over [lo, hi),
+ * kept as integers on the device across calls until _reset or _configure.  Segment s is in[s * hop + j], j < seg_len.
+ * step = round(sps 2^32), 4 .. 64 samples per symbol; P = 4, 8, 16, 32 or 64; H = 8 .. 256; P H <= 8192; lo < hi, finite.
+ *   series   TDSA_EYE_IQ    x itself, complex64, n = seg_len; two eyes: 0 = I, 1 = Q.
+ *            TDSA_EYE_FM    complex64: d_j = the FSK analysis' discriminator, b = its boxcar over B = 1 .. 64 (its stages
+ *                           0 and 1, bit for bit), n = seg_len - B; one eye.
+ *            TDSA_EYE_REAL  float32 through the same boxcar (B = 1: as it is), n = seg_len - B + 1; one eye.
+ *   K        the producer's: tdsa_symsync_symbols_per_segment (IQ), tdsa_fsk_symbols_per_segment with TDSA_FSK_IQ (FM)
+ *            or _FREQ (REAL) and B; 3 <= K <= 4096.
+ *   clock    tdsa_eye_clock per segment.  delta_fx = 0: the segment is counted as skipped and contributes nothing; else
+ *            2^32 <= delta_fx < step + 2^32.  step_f and theta_fx are read for IQ only.
+ *   points   k = 1 .. K - 2, c = 0 .. P - 1: pos = delta_fx + k step + floor((c - P / 2) step / P) (the floor of the
+ *            signed product: an arithmetic shift), i = pos >> 32, mu = the top 24 bits of the fraction; the value is the
+ *            symbol recovery's cubic Lagrange interpolation of series[i-1 .. i+2], per part for IQ.  Every tap lies inside
+ *            the series.  IQ: v = y exp(-2 pi i phi / 2^32), phi = theta_fx + k step_f + floor((c - P / 2) int32(step_f)
+ *            / P) mod 2^32, the symbol recovery's rotation and product; step_f = theta_fx = 0 leaves finite values as
+ *            they are.  Column P / 2 is the symbol recovery's symbols [1 .. K - 2], or the FSK analysis' levels
+ *            [1 .. K - 2], bit for bit.
+ *   rows     scale = float32(double(H) / (double(hi) - double(lo))); t = (v - lo) * scale in float32, two roundings.  NaN:
+ *            n_nan; t < 0: n_under; t >= H (+inf too): n_over; else row int(t), row 0 the lowest.
+ * State: counts[eyes][H][P] uint64; totals[10] uint64 = per eye {n_points, n_under, n_over, n_nan} (eye 1 zero for FM and
+ * REAL), then {segments, skipped}.  Sums of integers: the same bits for any split of the segments over calls, any n_seg,
+ * either entry point.  sum counts + n_under + n_over + n_nan = n_points = (segments - skipped) (K - 2) P per eye.
+ * traces (or NULL): [n_seg][K - 2][P] float32 (FM, REAL) or complex64 (IQ); a skipped segment's are left untouched.
+ * _process: host memory through pinned staging, n_samples <= max_host_samples; returns when the staging is free.
+ * _process_dev: device samples (and traces), host clocks (copied before the call returns), on plan p's stream or the
+ * handle's own for p = NULL; does not wait.  _read waits and copies eyes H P counts and the 10 totals.
+ * _symbols_per_segment needs no device.  Argument errors are reported before any HIP call. */
+#define TDSA_EYE_IQ 0
+#define TDSA_EYE_FM 1
+#define TDSA_EYE_REAL 2
+#define TDSA_EYE_MAX_BINS 8192
+#define TDSA_EYE_TOTALS 10
+typedef struct tdsa_eye_clock {
+  uint64_t delta_fx;           /* the first symbol's position in the series, 32.32 samples; 0 = skip the segment */
+  uint32_t step_f, theta_fx;   /* IQ: the carrier's phase step per symbol and its phase at symbol 0, turns / 2^32 */
+} tdsa_eye_clock;
+typedef struct tdsa_eye_s* tdsa_eye;
+int tdsa_eye_create(int device_id, size_t max_host_samples, int max_segments, tdsa_eye* out);
+int tdsa_eye_destroy(tdsa_eye h);
+int tdsa_eye_configure(tdsa_eye h, uint64_t step, int kind, int boxcar, int points, int rows, float lo, float hi);
+int tdsa_eye_symbols_per_segment(uint64_t step, size_t seg_len, int kind, int boxcar, int* K);
+int tdsa_eye_process(tdsa_eye h, const void* in_host, size_t n_samples, size_t seg_len, size_t hop, int n_seg,
+                     const tdsa_eye_clock* clocks_host, void* traces_host);
+int tdsa_eye_process_dev(tdsa_eye h, tdsa_plan p, const void* in_dev, size_t seg_len, size_t hop, int n_seg,
+                         const tdsa_eye_clock* clocks_host, void* traces_dev);
+int tdsa_eye_read(tdsa_eye h, uint64_t* counts_host, uint64_t* totals_host);
+int tdsa_eye_reset(tdsa_eye h);
+int tdsa_eye_timer_begin(tdsa_eye h);
+int tdsa_eye_timer_end(tdsa_eye h, float* elapsed_ms);
+
 /* -------- signal detection: noise floor, emissions, occupancy ----------------------------
  * Rows are [n_rows][n_bins] float32 dB rows, 1 <= n_bins <= 16384, the input of tdsa_rows_top_peaks.  Per row, with
  * seg = row[bin_lo .. bin_hi] (inclusive) and n_eff its length:

@@ -28,6 +28,8 @@ SYMSYNC_NONFINITE, SYMSYNC_NO_CARRIER = 1, 2
 FSK_IQ, FSK_FREQ = 0, 1
 FSK_AUTO, FSK_FIXED = 0, 1
 FSK_NONFINITE, FSK_ONE_LEVEL = 1, 2
+EYE_IQ, EYE_FM, EYE_REAL = 0, 1, 2
+EYE_MAX_BINS, EYE_TOTALS = 8192, 10
 DETECT_NAN_FLOOR = 1
 MEAS_EMPTY, MEAS_INF, MEAS_MASK_FAIL = 1, 2, 4
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
@@ -199,6 +201,16 @@ _SIGNATURES = {
     "tdsa_fsk_symbols_per_segment": (C.c_int, [C.c_uint64, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "tdsa_fsk_timer_begin": (C.c_int, [_P]),
     "tdsa_fsk_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_eye_create": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.POINTER(_P)]),
+    "tdsa_eye_destroy": (C.c_int, [_P]),
+    "tdsa_eye_configure": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]),
+    "tdsa_eye_symbols_per_segment": (C.c_int, [C.c_uint64, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "tdsa_eye_process": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _P, _P]),
+    "tdsa_eye_process_dev": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_int, _P, _P]),
+    "tdsa_eye_read": (C.c_int, [_P, _P, _P]),
+    "tdsa_eye_reset": (C.c_int, [_P]),
+    "tdsa_eye_timer_begin": (C.c_int, [_P]),
+    "tdsa_eye_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_detect_create": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
     "tdsa_detect_destroy": (C.c_int, [_P]),
     "tdsa_detect_configure": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int]),

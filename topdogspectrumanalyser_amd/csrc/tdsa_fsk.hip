@@ -29,18 +29,6 @@ namespace {
 
 constexpr int kT = kSegThreads;
 
-// d_j of a segment: the phase step from x[j] to x[j + 1] in half turns, or the input itself
-template <int KIND>
-__device__ inline float disc(const void* seg, int j) {
-  if constexpr (KIND == kFskIq) {
-    const float2* x = static_cast<const float2*>(seg);
-    const float2 y0 = x[j], y1 = x[j + 1];
-    return demod_fm(y1.x, y1.y, y0.x, y0.y);
-  } else {
-    return static_cast<const float*>(seg)[j];
-  }
-}
-
 // a segment that is not finite: NaN levels, zero indices, a zero record with the flag; a thread rewrites only the
 // out[k] it wrote itself
 __device__ inline void fsk_not_finite(FskRecord* rec, float* out, uint8_t* idx, int K, int tid) {
@@ -80,13 +68,9 @@ __global__ __launch_bounds__(kT) void fsk_kernel(FskLaunch a) {
   for (int j0 = 0; j0 < n_e; j0 += kFskTile) {
     const int ne = n_e - j0 < kFskTile ? n_e - j0 : kFskTile;
     const int nb = ne + L, nd = nb + B - 1;
-    for (int m = tid; m < nd; m += kT) td[m] = disc<KIND>(seg, j0 + m);
+    for (int m = tid; m < nd; m += kT) td[m] = seg_disc<KIND == kFskIq>(seg, j0 + m);
     __syncthreads();
-    for (int m = tid; m < nb; m += kT) {
-      float sum = td[m];
-      for (int i = 1; i < B; ++i) sum = sum + td[m + i];
-      tb[m] = sum * inv_b;
-    }
+    seg_boxcar_tile(td, tb, nb, B, inv_b, tid);
     __syncthreads();   // the next tile writes td behind this barrier, tb behind its own first
     for (int m = tid; m < ne; m += kT) {
       const float df = tb[m + L] - tb[m];

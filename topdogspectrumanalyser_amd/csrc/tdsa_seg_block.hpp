@@ -1,5 +1,5 @@
-// tdsa_seg_block.hpp - what the kernels of the segment analysers (tdsa_symsync.hip, tdsa_fsk.hip) share, device only: the
-// rotation and the workgroup's folds.  A kernel's bit-for-bit tests pin the tree of every float fold, and it is stated
+// tdsa_seg_block.hpp - what the kernels of the segment analysers (tdsa_symsync.hip, tdsa_fsk.hip) and of the eye diagrams
+// (tdsa_eye.hip) share, device only: the rotation, the discriminator and the boxcar of a tile, the workgroup's folds.  A kernel's bit-for-bit tests pin the tree of every float fold, and it is stated
 // here and nowhere else: thread t's slot with that of t + 128, t + 64, ... 1, own slot first.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +15,28 @@ __device__ inline float2 rot(const float2* nco, uint32_t p) {
   float2 r;
   sym_rot(p, h.x, h.y, &r.x, &r.y);
   return r;
+}
+
+// d_j of a segment: the phase step from x[j] to x[j + 1] in half turns (IQ: complex64), or the input itself (float32)
+template <bool IQ>
+__device__ inline float seg_disc(const void* seg, int j) {
+  if constexpr (IQ) {
+    const float2* x = static_cast<const float2*>(seg);
+    const float2 y0 = x[j], y1 = x[j + 1];
+    return demod_fm(y1.x, y1.y, y0.x, y0.y);
+  } else {
+    return static_cast<const float*>(seg)[j];
+  }
+}
+
+// The boxcar of a tile in LDS: tb[m] = (((td[m] + td[m + 1]) + ...) + td[m + B - 1]) * inv_b, m < nb, float32 adds in
+// ascending order; consecutive threads read td at stride one.  The caller's barriers stand around it.
+__device__ inline void seg_boxcar_tile(const float* td, float* tb, int nb, int B, float inv_b, int tid) {
+  for (int m = tid; m < nb; m += kSegThreads) {
+    float sum = td[m];
+    for (int i = 1; i < B; ++i) sum = sum + td[m + i];
+    tb[m] = sum * inv_b;
+  }
 }
 
 // The workgroup's fold of one 16-byte slot a thread, every thread gets the result; the first barrier frees `red` from
