@@ -641,6 +641,66 @@ int tdsa_eye_reset(tdsa_eye h);
 int tdsa_eye_timer_begin(tdsa_eye h);
 int tdsa_eye_timer_end(tdsa_eye h, float* elapsed_ms);
 
+/* -------- modulation quality: decisions, gain / phase / offset fit, error vector -------------
+ * The last stage of the chain for linear modulations (BPSK .. 64QAM, any table of up to 64 points): rows of symbols as
+ * the symbol recovery leaves them, segment s = y[s * in_stride + k], k < K, complex64, 2 <= K <= 4096, in_stride >= 1
+ * (rows may overlap).  _set_points takes T = 1 .. 64 finite float32 pairs r_i, not all zero, and uploads beside them
+ * r_abs[i] = sqrtf(fl(fl(re^2) + fl(im^2))) and inv_rho = float32(1 / sqrt(sum |r_i|^2 / T)), formed in float64.
+ * Float32 and float64 arithmetic is written operation by operation, nothing is fused; a product of two float32 values
+ * is exact in float64; a complex product is four products, one difference and one sum.  Every sum over k is one fixed
+ * tree per K: thread t of 256 folds k = t, t + 256, ... in order from 0.0, the 64 partial sums of a wave fold by the
+ * xor butterfly (v = v + the value of lane ^ o, o = 32 .. 1), the four wave sums as (W0 + W1) + (W2 + W3).
+ *   0 first guess  S_y = sum y, S_yy = sum (re^2 + im^2) in float64.  c0 = float32(S_y / K) per part; v = S_yy / K -
+ *                  (Re(S_y / K)^2 + Im(S_y / K)^2); a0 = (sqrtf(float32(max(v, 0))) inv_rho, 0).  S_y or S_yy not finite:
+ *                  TDSA_MODQ_NONFINITE, zero indices, NaN error vectors, an otherwise zero record; no other segment is
+ *                  touched.  a0 = 0: TDSA_MODQ_DEGENERATE, zero indices, a = 0, c = c0, error vectors y - c0 and
+ *                  err_sumsq, err_peak, err_peak_k from them; the other sums, s_ry, s_cy and changed are zero.
+ *   1 decide       q = conj(a) / (a_re^2 + a_im^2) in float64, each part rounded to float32 once; t = y - c; w = t q;
+ *                  d_i = fl(fl((w_re - r_re)^2) + fl((w_im - r_im)^2)); the index is the lowest i of the smallest d_i
+ *                  (compared with <; a NaN never wins; every d_i NaN: 0).
+ *   2 fit          n_i = the symbols decided for point i.  In float64 and in index order S_r = sum n_i r_i, S_rr =
+ *                  sum n_i (re^2 + im^2); tree sums S_ry = sum conj(r_k) y_k, S_cy = sum r_k y_k.  D = K S_rr - |S_r|^2;
+ *                  a = (K S_ry - conj(S_r) S_y) / D, c = (S_y - a S_r) / K with the unrounded a, each part rounded to
+ *                  float32 once.  Every symbol on one index, or D <= 0: a and c stay, TDSA_MODQ_ONE_POINT.
+ *   3 two rounds   round 1 decides with (a0, c0) and fits, round 2 decides with that fit and fits again; `changed` counts
+ *                  the k whose index differs between the rounds.
+ *   4 errors       against round 2's indices with the final (a, c): w as in 1, eps_k = w_k - r_k, e2_k = fl(fl(eps_re^2) +
+ *                  fl(eps_im^2)), m_k = sqrtf(fl(fl(w_re^2) + fl(w_im^2))) - r_abs, p_k = the demodulator's atan2 / pi of
+ *                  w_k conj(r_k) in half turns (0 where r_k = 0).  Tree sums of e2, m^2, p^2 in float64; ref_sumsq is
+ *                  round 2's S_rr.  err_peak is the largest e2 with the lowest k, compared with > from 0 at k = 0.
+ * Outputs: one record per segment, the indices as uint8 [n_seg][out_stride] and, unless err is NULL, eps as complex64 of
+ * the same shape (the error vector over time); the gaps of out_stride > K are not touched.  Given y, the record, the
+ * indices and eps are this text's bit for bit, phase_sumsq within the arctangent's bound.  A segment's bits do not
+ * depend on n_seg, its place or the entry point.
+ * _process: a host block of n_symbols <= max_host_symbols through pinned staging.  _process_dev: device pointers
+ * (symbols and error vectors aligned to 8 bytes), on plan p's stream (ordered after its work, and its later work after
+ * this) or the handle's own for p = NULL.  Both return when the records are in host memory.  Argument errors are
+ * reported before any HIP call. */
+#define TDSA_MODQ_MAX_POINTS 64
+#define TDSA_MODQ_MAX_SYMBOLS 4096
+#define TDSA_MODQ_NONFINITE 1u
+#define TDSA_MODQ_DEGENERATE 2u
+#define TDSA_MODQ_ONE_POINT 4u
+typedef struct tdsa_modq_record {
+  float a_re, a_im, c_re, c_im;          /* y ~ a r + c */
+  double s_y[2], s_yy, s_ry[2], s_cy[2]; /* S_y, S_yy, and round 2's S_ry, S_cy */
+  double err_sumsq, ref_sumsq, mag_sumsq, phase_sumsq;
+  float err_peak;                        /* the largest e2 ... */
+  uint32_t err_peak_k;                   /* ... and its lowest k */
+  uint32_t changed, flags;
+  uint32_t reserved[2];
+} tdsa_modq_record;
+typedef struct tdsa_modq_s* tdsa_modq;
+int tdsa_modq_create(int device_id, size_t max_host_symbols, tdsa_modq* out);
+int tdsa_modq_destroy(tdsa_modq h);
+int tdsa_modq_set_points(tdsa_modq h, const float* points, int n_points);   /* points: n_points (re, im) pairs */
+int tdsa_modq_process(tdsa_modq h, const void* in_host, size_t n_symbols, int K, size_t in_stride, int n_seg,
+                      uint8_t* idx_host, size_t out_stride, void* err_host, tdsa_modq_record* records_host);
+int tdsa_modq_process_dev(tdsa_modq h, tdsa_plan p, const void* in_dev, int K, size_t in_stride, int n_seg, void* idx_dev,
+                          size_t out_stride, void* err_dev, tdsa_modq_record* records_host);
+int tdsa_modq_timer_begin(tdsa_modq h);
+int tdsa_modq_timer_end(tdsa_modq h, float* elapsed_ms);
+
 /* -------- signal detection: noise floor, emissions, occupancy ----------------------------
  * Rows are [n_rows][n_bins] float32 dB rows, 1 <= n_bins <= 16384, the input of tdsa_rows_top_peaks.  Per row, with
  * seg = row[bin_lo .. bin_hi] (inclusive) and n_eff its length:

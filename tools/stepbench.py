@@ -1,5 +1,5 @@
 """The driver of the step benches: chanbench, demodbench, detectbench, historybench, measbench,
-pstatbench, pulsebench, symsyncbench, corrbench, fskbench and eyebench.  A bench lists its steps, name -> f(args) returning dict(text=[...], **figures),
+pstatbench, pulsebench, symsyncbench, corrbench, fskbench, eyebench and modqbench.  A bench lists its steps, name -> f(args) returning dict(text=[...], **figures),
 and ends in main(__file__, STEPS, header).  Every step runs in a child process of its own under a time limit; the first
 step that fails, prints no result or runs out of time is the last one started, and the process exits with status 1."""
 import argparse

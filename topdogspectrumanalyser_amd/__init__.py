@@ -18,6 +18,7 @@ from .demod import Demodulator, deemphasis_pole, design_audio_filter  # noqa: F4
 from .symbols import SymbolSync, rrc_taps  # noqa: F401
 from .fsk import FskAnalyzer, FskResult  # noqa: F401
 from .eye import EyeDiagram, EyeImage  # noqa: F401
+from .modquality import ModQResult, ModQuality  # noqa: F401
 from .detect import Detections, SignalDetector  # noqa: F401
 from .measure import ChannelMeasure, Measurements, channel_plan, channels_from_emission, limit_line  # noqa: F401
 from .powerstats import PowerStatistics, PowerStats, gaussian_ccdf  # noqa: F401
@@ -35,4 +36,4 @@ __all__ = ["DeviceBuffer", "SpectrumEngine", "HostPipe", "TraceState", "TraceAve
            "Demodulator", "design_audio_filter", "deemphasis_pole", "SignalDetector", "Detections", "ChannelMeasure", "Measurements",
            "channel_plan", "limit_line", "channels_from_emission", "PowerStats", "PowerStatistics", "gaussian_ccdf",
            "PulseAnalyzer", "PulseTrain", "levels_from_db", "Correlator", "Matches", "zadoff_chu", "barker", "from_symbols", "FskAnalyzer", "FskResult",
-           "EyeDiagram", "EyeImage"]
+           "EyeDiagram", "EyeImage", "ModQuality", "ModQResult"]

@@ -30,6 +30,8 @@ FSK_AUTO, FSK_FIXED = 0, 1
 FSK_NONFINITE, FSK_ONE_LEVEL = 1, 2
 EYE_IQ, EYE_FM, EYE_REAL = 0, 1, 2
 EYE_MAX_BINS, EYE_TOTALS = 8192, 10
+MODQ_MAX_POINTS, MODQ_MAX_SYMBOLS = 64, 4096
+MODQ_NONFINITE, MODQ_DEGENERATE, MODQ_ONE_POINT = 1, 2, 4
 DETECT_NAN_FLOOR = 1
 MEAS_EMPTY, MEAS_INF, MEAS_MASK_FAIL = 1, 2, 4
 ZS_DET_REAL, ZS_DET_MAG, ZS_DET_DB = 0, 1, 2
@@ -211,6 +213,13 @@ _SIGNATURES = {
     "tdsa_eye_reset": (C.c_int, [_P]),
     "tdsa_eye_timer_begin": (C.c_int, [_P]),
     "tdsa_eye_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tdsa_modq_create": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_P)]),
+    "tdsa_modq_destroy": (C.c_int, [_P]),
+    "tdsa_modq_set_points": (C.c_int, [_P, _P, C.c_int]),
+    "tdsa_modq_process": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_size_t, C.c_int, _P, C.c_size_t, _P, _P]),
+    "tdsa_modq_process_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_size_t, C.c_int, _P, C.c_size_t, _P, _P]),
+    "tdsa_modq_timer_begin": (C.c_int, [_P]),
+    "tdsa_modq_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tdsa_detect_create": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.POINTER(_P)]),
     "tdsa_detect_destroy": (C.c_int, [_P]),
     "tdsa_detect_configure": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int]),
