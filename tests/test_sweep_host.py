@@ -1,8 +1,8 @@
 """Stepped sweeps, host side (no GPU): the float64 restatement in tests/sweep_contract.py checks itself against np.interp
 and against the reference's recorded sweep (tests/golden/sweep.npz; live against the reference class where its tree is
 there), plan_steps covers its span on the fftshift(fftfreq) axis, bad geometry is refused, the peak rule holds on
-hand-made cases, tdsa_sweep.hip compiles for gfx950 without scratch, and the C-ABI refuses bad arguments before it
-touches a device."""
+hand-made cases, tdsa_sweep.hip compiles for gfx950 without scratch, the inputs of tests/test_gpu_sweep_shapes.py tell
+the contract from every mutant of it, and the C-ABI refuses bad arguments before it touches a device."""
 import ctypes as C
 import os
 import re
@@ -212,6 +212,153 @@ def test_sweep_kernels_compile_scratch_free():
         assert int(kernels[k]["LDS Size [bytes/block]"]) <= 64 * 1024, (k, kernels[k])
     # the stitch takes its step table as dynamic LDS: 16 bytes for each of at most 4096 steps
     assert 4096 * 16 <= 64 * 1024
+
+
+# ---------------------------------------------------------------------------------------------------- the shapes suite
+def _const(name):
+    return int(re.search(r"constexpr int %s = (\d+);" % name, open(os.path.join(CSRC, "tdsa_sweep.hip")).read()).group(1))
+
+
+def _differs(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return ~((a == b) | (np.isnan(a) & np.isnan(b)))
+
+
+def test_inputs_of_the_shapes_suite_discriminate():
+    """The CPU half of tests/test_gpu_sweep_shapes.py: the cases reach every path of the two kernels, and on the very
+    arrays the GPU half feeds every mutant of tests/sweep_contract.py gives another result than the contract."""
+    block, batch = _const("kDetBlock"), _const("kDetBatch")
+    sblock, smax = _const("kStitchBlock"), _const("kStitchMaxBlocks")
+    Fs = sc.frame_counts(batch)
+    if batch == 8:
+        assert Fs == (1, 2, 7, 8, 9, 10, 16, 17, 25)
+    cases = sc.detector_cases(block, batch)
+    assert len(cases) == len(set(cases)) <= 40
+
+    # ---- the detector cases reach what they are for
+    quads = [c for c in cases if sc.takes_quads(c[0], *c[3:])]
+    wide = [c for c in quads if c[2] - c[1] > 2 * 4 * block]
+    assert {(k0 % 4, k1 % 4) for _, k0, k1, *_ in wide} == {(a, b) for a in range(4) for b in range(4)}
+    for N, k0, k1, *_ in wide:
+        assert ((k1 + 3) // 4 - k0 // 4 + block - 1) // block >= 3          # workgroups in x, as the launch counts them
+    assert {c[3] for c in wide} == set(Fs)
+    assert any(k0 == 0 and k1 == N for N, k0, k1, *_ in wide)
+    small = {(k0, k1) for N, k0, k1, *_ in quads if N <= 64}
+    assert {k1 - k0 for k0, k1 in small if k0 // 4 == (k1 - 1) // 4} >= {1, 2, 3}
+    assert any(k1 - k0 == 2 and k0 // 4 != (k1 - 1) // 4 for k0, k1 in small)
+    assert any(k1 - k0 == 4 and k0 % 4 == 0 for k0, k1 in small)
+    scalar = [c for c in cases if not sc.takes_quads(c[0], *c[3:])]
+    assert {c[3] for c in scalar} == set(Fs) and all(k1 - k0 > 4 * block for _, k0, k1, *_ in scalar)
+    alone = lambda N, F, pad, off: ((off % 16 != 0) + (N % 4 != 0) + ((F * N + pad) % 4 != 0 and N % 4 == 0)) == 1
+    assert all(alone(N, F, pad, off) for N, _, _, F, pad, off in scalar)
+    assert {off for *_, pad, off in scalar if off} == {4, 8, 12} and {pad for *_, pad, off in scalar if pad} == {1, 2, 3}
+    assert any(N % 4 for N, *_ in scalar)
+
+    # ---- on their rows every mutant shows
+    for i, (N, k0, k1, F, pad, off) in enumerate(cases):
+        S, K = sc.case_steps(N), k1 - k0
+        rows, special = sc.spiky_rows(S, F, N, seed=i)
+        level = sc.level_rows(S, F, N, seed=i)
+        buf, stride = sc.lay_out(rows, pad, off)
+        assert stride == F * N + pad and buf.size == off // 4 + S * stride
+        assert np.array_equal(buf[off // 4:].reshape(S, stride)[:, :F * N].reshape(S, F, N), rows, equal_nan=True)
+        assert (buf == sc.SENTINEL).sum() == off // 4 + S * pad and not (rows == 0).any()
+        b = np.arange(N)
+        for s in range(S):
+            plain = rows[s][~special[s]]
+            assert np.unique(plain).size == plain.size                       # all distinct
+            clean = ~special[s].any(axis=0)
+            assert clean.sum() > 0.3 * N or N <= 64
+            assert np.array_equal(np.argmax(rows[s][:, clean], axis=0), ((b + s) % F)[clean])
+            assert F == 1 or np.array_equal(np.argmin(rows[s][:, clean], axis=0), ((b + s + 1) % F)[clean])
+            for det in ("sample", "max", "min"):
+                want = sc.detector(rows[s], k0, k1, det)
+                if K > 4 * block + 8:
+                    assert _differs(want, sc.detector_quad_shifted(rows[s], k0, k1, det, 4 * block)).any(), (i, det)
+            if K > 4 * block and F > 1:               # every frame holds the maximum of many kept bins and the minimum of others
+                for det in ("max", "min"):
+                    want = sc.detector(rows[s], k0, k1, det)
+                    for f in range(F):
+                        assert _differs(want, sc.detector_skipping(rows[s], k0, k1, det, f)).any(), (i, det, f)
+            if F > 1:
+                assert _differs(sc.detector(rows[s], k0, k1, "sample"),
+                                sc.detector_skipping(rows[s], k0, k1, "sample", F - 1)).any(), i
+            # avg: the level rows; a frame left out moves every kept bin by ten times the allowance or more
+            want = sc.detector(level[s], k0, k1, "avg")
+            assert np.isfinite(want).all()
+            lv = level[s][:, k0:k1]
+            assert (lv.max(axis=0) - lv.min(axis=0)).max() <= 6.0
+            for f in range(F):
+                moved = np.abs(sc.detector_skipping(level[s], k0, k1, "avg", f) - want)
+                assert moved.min() >= 10 * sc.AVG_BOUND_DB, (i, f, float(moved.min()))
+            if K > 4 * block + 8:
+                moved = np.abs(sc.detector_quad_shifted(level[s], k0, k1, "avg", 4 * block) - want)[4 * block:-4]
+                assert (moved >= 10 * sc.AVG_BOUND_DB).mean() > 0.9
+    # the special values come out as the contract says
+    sp = sc.special_rows(2, 9, 64, seed=1)
+    mx, mn, av, sm = (sc.detector(sp[0], 0, 64, d) for d in ("max", "min", "avg", "sample"))
+    for pattern in (0, 1, 2, 3, 11):
+        assert np.isnan(mx[pattern]) and np.isnan(mn[pattern]) and np.isnan(av[pattern])
+    assert np.isnan(sm[1]) and np.isnan(sm[3]) and not np.isnan(sm[0]) and not np.isnan(sm[2])
+    assert av[4] == -300.0 and mx[4] == -np.inf and np.isfinite(av[5]) and mn[5] == -np.inf and np.isfinite(mx[6])
+    assert abs(av[7] - 299.0) < 1e-9 and abs(av[8] + 299.0) < 1e-9 and mx[9] == 299.0 and mn[10] == -299.0
+    assert np.isfinite(av[12:16]).all() and np.isnan(av).sum() == 5 * 4
+
+    # ---- the stitch cases
+    stitch_cases = sc.stitch_cases(sblock)
+    reached, long_seen = set(), 0
+    for name, tag, grid_tag in stitch_cases:
+        N, k0, k1, bin_hz, centres, T, present, grid = sc.stitch_inputs(name, tag, grid_tag, sblock, smax)
+        K = k1 - k0
+        assert bin_hz == 1.0 / (N * (1.0 / 1e6)) and np.all(np.isfinite(grid)) and np.all(np.diff(grid) > 0)
+        assert grid[1] - grid[0] > 0 and grid.size <= max(60000, sblock * smax + sblock + 1)
+        xp = sc.frequencies(centres[present], k0, k1, N, bin_hz)
+        fp = T[present].reshape(-1)
+        assert xp[0] == 0.0 or not present[0]
+        assert np.all(np.diff(sc.frequencies(centres, k0, k1, N, bin_hz)) > 0)
+        reached.add(int(present.sum()))
+        if grid_tag == "long":
+            long_seen = max(long_seen, grid.size)
+            continue
+        assert grid[0] < xp[0] and (grid[-1] > xp[-1] or grid_tag.startswith("cells"))
+        if grid_tag == "ulp":
+            assert grid[1] < xp[0] and grid[-2] > xp[-1]
+            on, below, above = np.isin(grid, xp), np.isin(grid, np.nextafter(xp, -np.inf)), np.isin(grid, np.nextafter(xp, np.inf))
+            assert on.sum() == below.sum() == above.sum() >= min(xp.size, 8000)
+            if present.sum() > sblock:                   # a table cut at the first round of its load shows, in both modes
+                for mode in ("interp", "peak"):
+                    want = sc.assemble(T, present, centres, k0, k1, N, bin_hz, grid, mode)
+                    assert _differs(want, sc.assemble_table_cut(T, present, centres, k0, k1, N, bin_hz, grid, mode, sblock)).any()
+        if grid_tag.startswith("cells"):
+            h = grid[1] - grid[0]
+            assert abs(h / bin_hz - (8.0 if grid_tag == "cells8" else 3.5 * K)) < 1e-6
+            lower_on, upper_on = np.isin(grid - 0.5 * h, xp), np.isin(grid + 0.5 * h, xp)
+            assert lower_on.sum() >= 30 and upper_on.sum() >= 30, (name, tag, grid_tag)
+            want = sc.stitch(grid, xp, fp, "peak")
+            assert _differs(want, sc.stitch_upper_closed(grid, xp, fp)).sum() >= 5, (name, tag, grid_tag)
+            assert np.isfinite(want).sum() >= 30
+    assert {sblock - 1, sblock, sblock + 1, 4096} <= reached and long_seen > sblock * smax
+    assert {(n, g) for n, _, g in stitch_cases} >= {(n, g) for n in ("inexact", "k1", "k2", "k3") for g in ("ulp", "cells8", "cellswide")}
+
+    # ---- the inexact geometry: one rounding or two, a guess or the exact expression
+    N, k0, k1, bin_hz, centres, T, present, grid = sc.stitch_inputs("inexact", "all", "ulp", sblock, smax)
+    K = k1 - k0
+    assert bin_hz * N != 1e6 or bin_hz != np.round(bin_hz)                 # 1302.0833...: not a number of Hz
+    xp, fp = sc.frequencies(centres, k0, k1, N, bin_hz), T.reshape(-1).astype(np.float64)
+    fused = sc.frequencies_fused(centres, k0, k1, N, bin_hz)
+    assert (fused != xp).sum() >= 100 and np.max(np.diff(xp)) > 30 * bin_hz
+    assert _differs(sc.stitch(grid, xp, fp, "interp"), sc.stitch(grid, fused, fp, "interp")).sum() >= 100
+    cells = sc.stitch_inputs("inexact", "all", "cells8", sblock, smax)[7]   # cell edges on the bins: there peak shows it
+    assert _differs(sc.stitch(cells, xp, fp, "peak"), sc.stitch(cells, fused, fp, "peak")).sum() >= 30
+    inside = grid[grid >= xp[0]]
+    wrong = sc.locate_by_guess(inside, xp, K, bin_hz) != sc.locate(inside, xp)
+    assert wrong.sum() >= 1000
+    want = np.interp(grid, xp, fp)
+    assert _same(sc.interp_spelled(grid, xp, fp), want)
+    guessed = sc.interp_spelled(grid, xp, fp, locator=lambda x: sc.locate_by_guess(np.float64(x), xp, K, bin_hz))
+    assert _differs(guessed, want).sum() >= 100
+    hit = np.isin(grid, xp)
+    assert _same(want[hit], fp[np.searchsorted(xp, grid[hit])])           # a grid point on a bin takes that bin's value
 
 
 def _err():
