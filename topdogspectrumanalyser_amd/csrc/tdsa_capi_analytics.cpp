@@ -9,7 +9,7 @@ using namespace tdsa;
 namespace {
 
 // scratch that grows on demand, owned by the plan (freed by tdsa_destroy; one plan = one thread at a time)
-int plan_scratch(tdsa_plan p, size_t need) { return grow_device(&p->d_scratch, &p->scratch_bytes, need, p->stream); }
+int plan_scratch(tdsa_plan p, size_t need) { return p->d_scratch.grow(need, p->stream); }
 
 // Where the result arrays of a rows_* call are formed and how they reach the caller's (pageable) arrays: every copy
 // into pageable memory costs ~10 us in the runtime's own staging, so the arrays of a call sit back to back in ONE
@@ -204,10 +204,10 @@ int tdsa_rows_marker_peaks(tdsa_plan p, const float* rows_dev, int n_rows, int n
 struct tdsa_density_s : Lane {
   int n = 0;
   float decay = 0.96f;
-  float* d_hist = nullptr;     // [n][512]
-  float* d_img = nullptr;      // log1p image scratch
-  unsigned char* d_u8 = nullptr;   // the image as bytes (+ 8 bytes: its min / max)
-  float* h_row[2] = {nullptr, nullptr};   // pinned, device-visible staging of host rows (the kernel reads them in place)
+  Dev<float> d_hist;           // [n][512]
+  Dev<float> d_img;            // log1p image scratch
+  Dev<unsigned char> d_u8;     // the image as bytes (+ 8 bytes: its min / max)
+  Pinned<float> h_row[2];      // pinned, device-visible staging of host rows (the kernel reads them in place)
   hipEvent_t ev_row[2] = {nullptr, nullptr};   // ... free again when the update that read them has run
   unsigned tick = 0;
 };
@@ -223,11 +223,9 @@ int tdsa_density_create(int device_id, int n_bins, float decay, tdsa_density* ou
   d->decay = decay;
   const size_t hb = size_t(n_bins) * 512 * sizeof(float);
   hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&d->d_hist, hb);
+  if (e == hipSuccess) e = d->d_hist.alloc(hb / sizeof(float));
   for (int k = 0; k < 2; ++k) {
-    if (e == hipSuccess)
-      e = hipHostMalloc(reinterpret_cast<void**>(&d->h_row[k]), size_t(n_bins) * sizeof(float),
-                        hipHostMallocPortable | hipHostMallocMapped);
+    if (e == hipSuccess) e = d->h_row[k].alloc(size_t(n_bins), hipHostMallocPortable | hipHostMallocMapped);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev_row[k], hipEventDisableTiming);
   }
   if (e == hipSuccess) e = hipMemsetAsync(d->d_hist, 0, hb, d->stream);
@@ -243,12 +241,8 @@ int tdsa_density_create(int device_id, int n_bins, float decay, tdsa_density* ou
 int tdsa_density_destroy(tdsa_density d) {
   if (!d) return TDSA_OK;
   d->drain();
-  free_all({d->d_hist, d->d_img, d->d_u8});
-  for (int k = 0; k < 2; ++k) {
-    if (d->h_row[k]) (void)hipHostFree(d->h_row[k]);
-    if (d->ev_row[k]) (void)hipEventDestroy(d->ev_row[k]);
-  }
-  d->close();
+  for (hipEvent_t ev : d->ev_row)
+    if (ev) (void)hipEventDestroy(ev);
   delete d;
   return TDSA_OK;
 }
@@ -301,7 +295,7 @@ int tdsa_density_read(tdsa_density d, float* hist_host, int as_log1p) {
   const size_t cnt = size_t(d->n) * 512;
   const float* src = d->d_hist;
   if (as_log1p) {
-    if (!d->d_img) HIPCHK(hipMalloc(&d->d_img, cnt * sizeof(float)));
+    if (!d->d_img) HIPCHK(d->d_img.alloc(cnt));
     HIPCHK(launch_log1p(d->d_hist, d->d_img, cnt, d->stream));
     src = d->d_img;
   }
@@ -314,8 +308,8 @@ int tdsa_density_read_u8(tdsa_density d, uint8_t* img_host, float* levels2) {
   if (!d || !img_host) return fail(TDSA_ERR_ARG, "null argument");
   HIPCHK(hipSetDevice(d->device));
   const size_t cnt = size_t(d->n) * 512;
-  if (!d->d_img) HIPCHK(hipMalloc(&d->d_img, cnt * sizeof(float)));
-  if (!d->d_u8) HIPCHK(hipMalloc(&d->d_u8, cnt + 16));
+  if (!d->d_img) HIPCHK(d->d_img.alloc(cnt));
+  if (!d->d_u8) HIPCHK(d->d_u8.alloc(cnt + 16));
   unsigned* d_mm = reinterpret_cast<unsigned*>(d->d_u8 + ((cnt + 7) & ~size_t(7)));
   HIPCHK(launch_log1p(d->d_hist, d->d_img, cnt, d->stream));
   HIPCHK(launch_minmax_pos(d->d_img, cnt, d_mm, d->stream));
@@ -338,15 +332,14 @@ struct tdsa_waterfall_s : Lane {
   int n = 0, history = 0;
   int ptr = 0;
   bool have_last = false;
-  float* d_ring = nullptr;     // [history][n]: every line once, the view is two copies
-  float* d_last = nullptr;     // [n] Waterfall._last_row
-  unsigned char* d_u8 = nullptr;   // [history][n] the view as bytes (tdsa_waterfall_view_u8)
-  float* h_row = nullptr;      // pinned staging of a host row: small rows are read in place by the kernels,
-  float* d_row = nullptr;      // larger ones take one DMA into d_row first (the scatter reads every bin)
-  int* d_flags = nullptr;      // [2][cap] differs, destination line per pushed row
-  int* d_info = nullptr;       // {new rows, last new row} of the push in flight, for the scatter
-  int* h_info = nullptr;       // the same two words, pinned: what the host waits for
-  size_t cap = 0;
+  Dev<float> d_ring;           // [history][n]: every line once, the view is two copies
+  Dev<float> d_last;           // [n] Waterfall._last_row
+  Dev<unsigned char> d_u8;     // [history][n] the view as bytes (tdsa_waterfall_view_u8)
+  Pinned<float> h_row;         // pinned staging of a host row: small rows are read in place by the kernels,
+  Dev<float> d_row;            // larger ones take one DMA into d_row first (the scatter reads every bin)
+  Dev<int> d_flags;            // [2][cap() / 2] differs, destination line per pushed row
+  Dev<int> d_info;             // {new rows, last new row} of the push in flight, for the scatter
+  Pinned<int> h_info;          // the same two words, pinned: what the host waits for
 };
 
 int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float min_db, tdsa_waterfall* out) {
@@ -360,14 +353,13 @@ int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float mi
   w->history = history_lines;
   const size_t cnt = size_t(history_lines) * n_bins;
   hipError_t e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&w->d_ring, cnt * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&w->d_info, 2 * sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&w->h_info), 2 * sizeof(int), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&w->d_last, size_t(n_bins) * sizeof(float));
+  if (e == hipSuccess) e = w->d_ring.alloc(cnt);
+  if (e == hipSuccess) e = w->d_info.alloc(2);
+  if (e == hipSuccess) e = w->h_info.alloc(2, hipHostMallocDefault);
+  if (e == hipSuccess) e = w->d_last.alloc(size_t(n_bins));
   if (e == hipSuccess)
-    e = hipHostMalloc(reinterpret_cast<void**>(&w->h_row), size_t(n_bins) * sizeof(float),
-                      hipHostMallocPortable | hipHostMallocMapped);
-  if (e == hipSuccess) e = hipMalloc(&w->d_row, size_t(n_bins) * sizeof(float));
+    e = w->h_row.alloc(size_t(n_bins), hipHostMallocPortable | hipHostMallocMapped);
+  if (e == hipSuccess) e = w->d_row.alloc(size_t(n_bins));
   if (e == hipSuccess) e = launch_fill(w->d_ring, cnt, min_db, w->stream);    // np.full((2H, W), wf_min_db)
   if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
   if (e != hipSuccess) {
@@ -381,21 +373,17 @@ int tdsa_waterfall_create(int device_id, int history_lines, int n_bins, float mi
 int tdsa_waterfall_destroy(tdsa_waterfall w) {
   if (!w) return TDSA_OK;
   w->drain();
-  free_all({w->d_ring, w->d_last, w->d_u8, w->d_row, w->d_flags, w->d_info});
-  if (w->h_row) (void)hipHostFree(w->h_row);
-  if (w->h_info) (void)hipHostFree(w->h_info);
-  w->close();
   delete w;
   return TDSA_OK;
 }
 
 static int waterfall_push_rows(tdsa_waterfall w, const float* rows_dev, int n_rows, int* n_new) {
-  TRY(grow_device(&w->d_flags, &w->cap, size_t(n_rows), nullptr, 2 * sizeof(int)));   // (every push ends with a wait)
+  TRY(w->d_flags.grow(2 * size_t(n_rows), nullptr));   // (every push ends with a wait)
   // new-row flags, the pointer walk of _add_row as a scan over them, the scatter: three launches, one wait
   w->h_info[0] = 0;
   w->h_info[1] = -1;
   HIPCHK(launch_waterfall_push(rows_dev, n_rows, w->n, w->have_last ? 1 : 0, w->ptr, w->history, w->d_flags,
-                               w->d_flags + w->cap, w->d_info, w->h_info, w->d_ring, w->d_last, w->stream));
+                               w->d_flags + w->d_flags.cap() / 2, w->d_info, w->h_info, w->d_ring, w->d_last, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
   const int fresh = w->h_info[0];
   if (fresh > 0) {
@@ -448,7 +436,7 @@ int tdsa_waterfall_view_u8(tdsa_waterfall w, float min_db, float max_db, uint8_t
   if (!(max_db > min_db)) return fail(TDSA_ERR_ARG, "levels (%g, %g): need max > min", double(min_db), double(max_db));
   HIPCHK(hipSetDevice(w->device));
   const size_t cnt = size_t(w->history) * w->n;
-  if (!w->d_u8) HIPCHK(hipMalloc(&w->d_u8, cnt));
+  if (!w->d_u8) HIPCHK(w->d_u8.alloc(cnt));
   const size_t head = size_t(w->history - w->ptr) * w->n;
   HIPCHK(launch_quantize_u8(w->d_ring + size_t(w->ptr) * w->n, w->d_u8, head, min_db, max_db, w->stream));
   HIPCHK(launch_quantize_u8(w->d_ring, w->d_u8 + head, cnt - head, min_db, max_db, w->stream));

@@ -32,13 +32,13 @@ int process_big(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n_f
   const size_t N = size_t(p->nfft);
   const int n1 = p->nfft >> 14;
   const int group = n_frames < p->big_group ? n_frames : p->big_group;
-  if (!p->d_z) HIPCHK(hipMalloc(&p->d_z, size_t(p->max_frames < p->big_group ? p->max_frames : p->big_group) * N * sizeof(float2)));
+  if (!p->d_z) HIPCHK(p->d_z.alloc(size_t(p->max_frames < p->big_group ? p->max_frames : p->big_group) * N));
   const int in_c64 = in_format == TDSA_IN_C64;
   const auto [xor_mask, in_off, in_scale] = in_format_consts(in_format);
   const long long stride = (long long)hop * bytes_per_sample(in_format);
   const float2* dc_sub = nullptr;
   if (m.dc_alpha >= 0.0f) {   // per-segment mean (alpha = 1) or tracker (alpha < 1)
-    if (!p->d_sums64) HIPCHK(hipMalloc(&p->d_sums64, size_t(p->max_frames) * 2 * sizeof(double)));
+    if (!p->d_sums64) HIPCHK(p->d_sums64.alloc(size_t(p->max_frames) * 2));
     HIPCHK(launch_big_dc(iq_dev, in_c64, xor_mask, stride, p->nfft, n_frames, m.dc_alpha > 1.0f ? 1.0 : double(m.dc_alpha),
                          double(in_off), double(in_scale), p->d_sums64, p->d_dc_state, p->d_dc_sub, p->stream));
     dc_sub = p->d_dc_sub;
@@ -72,7 +72,7 @@ int process_big(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n_f
     fused_tail = welch && p->big_fuse_gather && !p->profiling && n_frames <= group;
     if (fused_tail) {
       if (!p->d_bigq) {
-        HIPCHK(hipMalloc(&p->d_bigq, 32));
+        HIPCHK(p->d_bigq.alloc(32));
         HIPCHK(hipMemsetAsync(p->d_bigq, 0, 32, p->stream));
         p->bigq_tickets = p->bigq_rows = 0;
       }

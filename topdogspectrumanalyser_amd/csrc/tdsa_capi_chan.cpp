@@ -7,7 +7,7 @@ using namespace tdsa;
 // ---- polyphase channelizer (tdsa_chan.hip) -----------------------------------------------------------------------
 struct tdsa_chan_s : Feed {
   int M = 4, log2M = 2, os = 1, max_rows = kChanBlock, P = 1;
-  float2* d_tw = nullptr;             // [M / 2]
+  Dev<float2> d_tw;                   // [M / 2]
   // the base's D = M / os; d_taps: [max_rows][M], tap q M + r at q * M + r; d_hist: [max_rows * M] unpacked inputs
   // (float2) each; the host staging of the outputs is [M][n_out]
 };
@@ -43,8 +43,8 @@ int chan_process(tdsa_chan c, tdsa_plan p, bool host, int fmt, const void* in, s
       a.log2M = c->log2M;
       a.os = c->os;
       a.P = c->P;
-      a.hist = static_cast<float2*>(c->d_hist[c->cur]);
-      a.hist_out = static_cast<float2*>(c->d_hist[c->cur ^ 1]);
+      a.hist = c->d_hist[c->cur].as<float2>();
+      a.hist_out = c->d_hist[c->cur ^ 1].as<float2>();
       a.out = static_cast<float2*>(dst);
       a.out_stride = (long long)dst_stride;
       a.m_first = m_first;
@@ -90,7 +90,7 @@ int tdsa_chan_create(int device_id, int channels, int oversample, int max_taps, 
                                                         : make_float2(float(std::cos(th)), float(std::sin(th)));
   }
   hipError_t e = c->open(false);
-  if (e == hipSuccess) e = hipMalloc(&c->d_tw, tw.size() * sizeof(float2));
+  if (e == hipSuccess) e = c->d_tw.alloc(tw.size());
   if (e == hipSuccess) e = c->alloc(1, size_t(M), sizeof(float2));
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host copy of the twiddles is released
@@ -110,9 +110,6 @@ int tdsa_chan_create(int device_id, int channels, int oversample, int max_taps, 
 int tdsa_chan_destroy(tdsa_chan c) {
   if (!c) return TDSA_OK;
   c->drain();
-  free_all({c->d_tw});
-  c->release();
-  c->close();
   delete c;
   return TDSA_OK;
 }

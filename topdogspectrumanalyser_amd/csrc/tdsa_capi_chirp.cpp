@@ -89,7 +89,7 @@ int chirp_plan_init(tdsa_plan p) {
     }
   };
   // ... rounded once, in the order the first transform leaves its bins in ([k1][k2] on the long-frame kernels)
-  const auto upload_spectrum = [&](float2** dst) -> int {
+  const auto upload_spectrum = [&](Dev<float2>& dst) -> int {
     std::vector<float2> b32(M);
     if (p->chirp_big) {
       const int n1 = M >> kMaxLog2N, n2 = 1 << kMaxLog2N;
@@ -103,19 +103,19 @@ int chirp_plan_init(tdsa_plan p) {
   const int H = p->chirp_split;
   if (H == 0) {
     filter_spectrum(0, -(nfft - 1), nfft - 1);           // b[n] = b[M - n] = conj(a[n]) for n < N
-    TRY(upload_spectrum(&p->d_chirp_b));
+    TRY(upload_spectrum(p->d_chirp_b));
   } else {                                               // (tdsa_chirp.hip: the three segments of the split convolution)
     filter_spectrum(0, -(H - 1), H - 1);
-    TRY(upload_spectrum(&p->d_chirp_b));
+    TRY(upload_spectrum(p->d_chirp_b));
     filter_spectrum(-H, -(nfft - H - 1), H - 1);         // b[m - H], m = k - n' in (-(N - H), H)
-    TRY(upload_spectrum(&p->d_chirp_bm));
+    TRY(upload_spectrum(p->d_chirp_bm));
     filter_spectrum(H, -(H - 1), nfft - H - 1);          // b[m + H], m = k' - n in (-H, N - H)
-    TRY(upload_spectrum(&p->d_chirp_bp));
+    TRY(upload_spectrum(p->d_chirp_bp));
   }
   std::vector<float2> a32(nfft);
   for (int n = 0; n < nfft; ++n) a32[n] = float2{float(ar[n]), float(ai[n])};
-  TRY(upload(a32, &p->d_chirp_a));
-  TRY(upload(std::vector<float>(M, 1.0f), &p->d_ones));
+  TRY(upload(a32, p->d_chirp_a));
+  TRY(upload(std::vector<float>(M, 1.0f), p->d_ones));
   {   // 2^a 3^b 5^c up to 10 000 points: the stages of its mixed-radix transform and W_N^k
     int r = nfft;
     for (const int f : {2, 3, 5}) while (r % f == 0) r /= f;
@@ -123,10 +123,10 @@ int chirp_plan_init(tdsa_plan p) {
       smooth_plan(p);
       p->smooth = p->smooth_stages > 0;
     }
-    if (p->smooth) TRY(upload(unit_circle(nfft), &p->d_smooth_tw));
+    if (p->smooth) TRY(upload(unit_circle(nfft), p->d_smooth_tw));
   }
   // the M-point transforms' column-pass seeds (as for a native long frame of M points)
-  if (p->chirp_big) TRY(upload(seed_table(M, p->log2m), &p->d_tw_seed));
+  if (p->chirp_big) TRY(upload(seed_table(M, p->log2m), p->d_tw_seed));
   return TDSA_OK;
 }
 
@@ -165,8 +165,8 @@ int chirp_transform(tdsa_plan p, const void* in, int in_format, long long stride
   const int H = p->chirp_split;                            // > 0: two half-length rows per frame
   const size_t rows_max = size_t(p->max_frames) * (H ? 2 : 1);
   const int n_rows = n_frames * (H ? 2 : 1);
-  if (!p->d_u0 && !fused) HIPCHK(hipMalloc(&p->d_u0, rows_max * M * sizeof(float2)));
-  if (!p->d_u1 && !(fused && p->chirp_single && !p->chirp_big)) HIPCHK(hipMalloc(&p->d_u1, rows_max * M * sizeof(float2)));
+  if (!p->d_u0 && !fused) HIPCHK(p->d_u0.alloc(rows_max * M));
+  if (!p->d_u1 && !(fused && p->chirp_single && !p->chirp_big)) HIPCHK(p->d_u1.alloc(rows_max * M));
   if (!fused)
     HIPCHK(launch_chirp_pre(in, in_format == TDSA_IN_C64, stride, N, M, n_frames, p->d_window[in_format], p->d_chirp_a, dc_sub,
                             xor_mask, in_off, p->d_u0, s, H));
@@ -176,7 +176,7 @@ int chirp_transform(tdsa_plan p, const void* in, int in_format, long long stride
     // DFT that leaves natural order): tdsa_big.hip
     const int n1 = M >> kMaxLog2N;
     const long long rowb = (long long)(1 << kMaxLog2N) * sizeof(float2), segb = (long long)M * sizeof(float2);
-    if (!p->d_z) HIPCHK(hipMalloc(&p->d_z, rows_max * M * sizeof(float2)));
+    if (!p->d_z) HIPCHK(p->d_z.alloc(rows_max * M));
     BigWindow flat{};                   // the rows are windowed already (chirp_pre): one for every sample
     flat.mode = 2;
     flat.table = p->d_ones;
@@ -320,7 +320,7 @@ int process_chirp(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n
     // directly (n = 1, zero level 0)
     const bool tracked = m.dc_alpha < 1.0f;
     if (chirp_sum_chunks(N) > 1 && !p->d_sums64)      // long frames: several workgroups per frame leave partial sums here
-      HIPCHK(hipMalloc(&p->d_sums64, size_t(p->max_frames) * chirp_sum_chunks(N) * 2 * sizeof(double)));
+      HIPCHK(p->d_sums64.alloc(size_t(p->max_frames) * chirp_sum_chunks(N) * 2));
     HIPCHK(launch_chirp_sums(iq_dev, in_c64, xor_mask, stride, N, n_frames, twice_zero, p->d_sums,
                              tracked ? nullptr : p->d_dc_state, in_scale, s, p->d_sums64));
     dc_sub = p->d_sums;                   // dc_alpha >= 1: the frame's own mean
@@ -332,15 +332,15 @@ int process_chirp(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n
   const float pscale = m.db_mode == TDSA_DB_POW ? m.power_scale : 1.0f;
   float* const tare = p->tare_active ? p->d_tare_base : nullptr;
   const int first = p->frames_seen > 0 ? 1 : 0;
-  if (averaging && !p->d_lin) HIPCHK(hipMalloc(&p->d_lin, size_t(p->max_frames) * N * sizeof(float)));
+  if (averaging && !p->d_lin) HIPCHK(p->d_lin.alloc(size_t(p->max_frames) * N));
   // the power / dB rows leave the second transform directly (linear rows for the averager's scan, else dB rows + hold
   // traces); frames below 1024 points (and the A/B knobs): complex rows in d_u0, chirp_post below
   const bool fusable = chirp_fusable(p) || smooth;
   const bool holding = (m.hold_flags & (TDSA_HOLD_MAX | TDSA_HOLD_MIN)) != 0;
   float* rows = out_db_dev;
   if (fusable && !averaging && rows == nullptr && holding) {   // only the hold traces are wanted: the rows go to scratch
-    if (!p->d_u0) HIPCHK(hipMalloc(&p->d_u0, size_t(p->max_frames) * (p->chirp_split ? 2 : 1) * M * sizeof(float2)));
-    rows = reinterpret_cast<float*>(p->d_u0);
+    if (!p->d_u0) HIPCHK(p->d_u0.alloc(size_t(p->max_frames) * (p->chirp_split ? 2 : 1) * M));
+    rows = p->d_u0.as<float>();
   }
   if (fusable && !averaging && rows == nullptr) {              // nothing to produce (no rows, no hold, no averaging)
     if (dc_own)                                                // (but the estimate the plan carries moves on)
@@ -384,7 +384,7 @@ int process_chirp(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n
     } else {
       // above the LDS limit: column pass (n1-point transforms of fpw adjacent columns, times W_N^(n2 k1)) into z, row pass
       // (n2-point transforms of adjacent rows k1) from z to the dB rows
-      if (!p->d_smooth_z) HIPCHK(hipMalloc(&p->d_smooth_z, size_t(p->max_frames) * N * sizeof(float2)));
+      if (!p->d_smooth_z) HIPCHK(p->d_smooth_z.alloc(size_t(p->max_frames) * N));
       sp.n_total = N;
       sp.n1 = p->smooth_n1;
       sp.n2 = p->smooth_n2;
@@ -404,10 +404,7 @@ int process_chirp(tdsa_plan p, int in_format, const void* iq_dev, int hop, int n
     TRY(chirp_transform(p, iq_dev, in_format, stride, n_frames, dc_sub, xor_mask, in_off, fusable ? &post : nullptr));
   }
   if (averaging) {
-    if (!p->d_carry && p->max_frames > 128) {
-      HIPCHK(hipMalloc(&p->d_carry, size_t(avg_scan_chunks(p->max_frames)) * N * sizeof(double)));
-      p->carry_chunks = size_t(avg_scan_chunks(p->max_frames));
-    }
+    if (!p->d_carry && p->max_frames > 128) HIPCHK(p->d_carry.alloc(size_t(avg_scan_chunks(p->max_frames)) * N));
     if (!fusable)
       HIPCHK(launch_chirp_post(p->d_u0, N, M, n_frames, first, m.db_mode, pscale, m.log_floor,
                                m.cal_offset_db, nullptr, nullptr, p->d_lin, nullptr, nullptr, s, p->chirp_split));

@@ -7,20 +7,18 @@ using namespace tdsa;
 // ---- constellation analysis (tdsa_constellation.hip) ---------------------------------------------
 struct tdsa_constellation_s : Lane {
   size_t max_host = 0;
-  void* h_in = nullptr;          // pinned staging of a host block (up to 8 bytes per sample)
-  void* d_in = nullptr;
-  void* d_tab = nullptr;         // [2][kCstMaxPoints] doubles (floats for a float32 table)
+  Pinned<char> h_in;             // pinned staging of a host block (up to 8 bytes per sample)
+  Dev<char> d_in;
+  Dev<char> d_tab;               // [2][kCstMaxPoints] doubles (floats for a float32 table)
   CstTable tab;
   int bins = kCstMaxBins;
   double range = 1.5;
-  float* d_bs_pow = nullptr;     // per-block sums, grown on demand, each with its own capacity
-  void* d_bs_evm = nullptr;
-  size_t bs_pow_cap = 0, bs_evm_cap = 0;
-  float* d_rms = nullptr;        // per-segment results, grown on demand
-  double* d_evm = nullptr;
-  size_t rms_cap = 0, evm_cap = 0;
-  unsigned char* d_res = nullptr;   // the host path's results: evm, rms, counts, tail i[n_tail] then q[n_tail] ...
-  unsigned char* h_out = nullptr;   // ... and their pinned read-back (one copy)
+  Dev<float> d_bs_pow;     // per-block sums, grown on demand
+  Dev<char> d_bs_evm;
+  Dev<float> d_rms;              // per-segment results, grown on demand
+  Dev<double> d_evm;
+  Dev<unsigned char> d_res;         // the host path's results: evm, rms, counts, tail i[n_tail] then q[n_tail] ...
+  Pinned<unsigned char> h_out;      // ... and their pinned read-back (one copy)
 };
 
 namespace {
@@ -36,10 +34,10 @@ int cst_check_format(int fmt) {
 
 // no stream to drain: every call that launches ends with a wait
 int cst_reserve(tdsa_constellation c, size_t n_blocks, size_t n_seg) {
-  TRY(grow_device(&c->d_bs_pow, &c->bs_pow_cap, n_blocks, nullptr, sizeof(float)));
-  TRY(grow_device(&c->d_bs_evm, &c->bs_evm_cap, n_blocks, nullptr, sizeof(double)));
-  TRY(grow_device(&c->d_rms, &c->rms_cap, n_seg, nullptr, sizeof(float)));
-  return grow_device(&c->d_evm, &c->evm_cap, n_seg, nullptr, sizeof(double));
+  TRY(c->d_bs_pow.grow(n_blocks, nullptr));
+  TRY(c->d_bs_evm.grow(n_blocks * sizeof(double), nullptr));
+  TRY(c->d_rms.grow(n_seg, nullptr));
+  return c->d_evm.grow(n_seg, nullptr);
 }
 
 CstLaunch cst_args(tdsa_constellation c, int fmt, const void* in, size_t seg_len, size_t hop, int n_seg) {
@@ -73,12 +71,12 @@ int tdsa_constellation_create(int device_id, size_t max_host_samples, tdsa_const
   c->max_host = max_host_samples;
   const size_t in_bytes = max_host_samples * 8;
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipHostMalloc(&c->h_in, in_bytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&c->d_in, in_bytes);
-  if (e == hipSuccess) e = hipMalloc(&c->d_tab, 2 * kCstMaxPoints * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&c->d_res, kCstOutTail + in_bytes);
+  if (e == hipSuccess) e = c->h_in.alloc(in_bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = c->d_in.alloc(in_bytes);
+  if (e == hipSuccess) e = c->d_tab.alloc(2 * kCstMaxPoints * sizeof(double));
+  if (e == hipSuccess) e = c->d_res.alloc(kCstOutTail + in_bytes);
   if (e == hipSuccess)
-    e = hipHostMalloc(reinterpret_cast<void**>(&c->h_out), kCstOutTail + in_bytes, hipHostMallocDefault);
+    e = c->h_out.alloc(kCstOutTail + in_bytes, hipHostMallocDefault);
   if (e != hipSuccess) {
     (void)tdsa_constellation_destroy(c);
     return fail(TDSA_ERR_HIP, "constellation create: %s", hipGetErrorString(e));
@@ -97,10 +95,6 @@ int tdsa_constellation_create(int device_id, size_t max_host_samples, tdsa_const
 int tdsa_constellation_destroy(tdsa_constellation c) {
   if (!c) return TDSA_OK;
   c->drain();
-  free_all({c->d_in, c->d_tab, c->d_bs_pow, c->d_bs_evm, c->d_rms, c->d_evm, c->d_res});
-  if (c->h_in) (void)hipHostFree(c->h_in);
-  if (c->h_out) (void)hipHostFree(c->h_out);
-  c->close();
   delete c;
   return TDSA_OK;
 }
@@ -180,7 +174,7 @@ int tdsa_constellation_process(tdsa_constellation c, int in_format, const void* 
   HIPCHK(hipMemcpyAsync(c->d_in, c->h_in, bytes, hipMemcpyHostToDevice, c->stream));
   const size_t cnt_bytes = size_t(c->bins) * c->bins * sizeof(unsigned);
   CstLaunch a = cst_args(c, in_format, c->d_in, n, n, 1);
-  a.evm = reinterpret_cast<double*>(c->d_res);
+  a.evm = c->d_res.as<double>();
   a.rms = reinterpret_cast<float*>(c->d_res + 8);
   a.counts = counts ? reinterpret_cast<unsigned*>(c->d_res + kCstOutCounts) : nullptr;
   a.tail = nt ? reinterpret_cast<float*>(c->d_res + kCstOutTail) : nullptr;

@@ -22,17 +22,17 @@ struct tdsa_corr_s : IqAccum {
   long long trace = 0;             // K, after the cap
   int L = 0, W = 0;
   float threshold = 1.0f, e_ref = 1.0f;
-  float2* d_ref = nullptr;         // [kCorrMaxRef]
-  float2* d_hist = nullptr;        // [2][C][kCorrMaxRef]
-  CorrSummary* d_sum = nullptr;    // [C]
-  CorrRecord* d_rec = nullptr;     // [C][capacity]
-  float* d_ring_m = nullptr;       // the ring and the scratch of the match passes: sized by configure for its min_distance
-  float* d_ring_e = nullptr;
-  float4* d_ring_c = nullptr;
-  unsigned* d_bmax = nullptr;
-  int* d_cnt = nullptr;
-  unsigned long long* d_bits = nullptr;
-  size_t ring = 0, ring_cap = 0, blocks = 0, blocks_cap = 0;   // entries / blocks per stream in use; allocated, all streams
+  Dev<float2> d_ref;               // [kCorrMaxRef]
+  Dev<float2> d_hist;              // [2][C][kCorrMaxRef]
+  Dev<CorrSummary> d_sum;          // [C]
+  Dev<CorrRecord> d_rec;           // [C][capacity]
+  Dev<float> d_ring_m;             // the ring and the scratch of the match passes: sized by configure for its min_distance
+  Dev<float> d_ring_e;
+  Dev<float4> d_ring_c;
+  Dev<unsigned> d_bmax;
+  Dev<int> d_cnt;
+  Dev<unsigned long long> d_bits;
+  size_t ring = 0, blocks = 0;     // entries / blocks per stream in use
   long long seen = 0;              // samples per stream since the last reset
   long long decided = 0;           // windows decided
   int parity = 0;
@@ -151,16 +151,12 @@ int corr_size(tdsa_corr_s* h, int W) {
   const size_t ring = pow2_at_least(most + 2 * size_t(W) + 2 * size_t(kCorrBlock) + size_t(h->trace));
   const size_t blocks = (most + 2 * size_t(W)) / size_t(kCorrBlock) + 4;
   const size_t C = size_t(h->C);
-  size_t cap = h->ring_cap;
-  TRY(grow_device(&h->d_ring_m, &cap, C * ring, nullptr, sizeof(float)));
-  cap = h->ring_cap;
-  TRY(grow_device(&h->d_ring_e, &cap, C * ring, nullptr, sizeof(float)));
-  TRY(grow_device(&h->d_ring_c, &h->ring_cap, C * ring, nullptr, sizeof(float4)));
-  cap = h->blocks_cap;
-  TRY(grow_device(&h->d_bmax, &cap, C * blocks, nullptr, sizeof(unsigned)));
-  cap = h->blocks_cap;
-  TRY(grow_device(&h->d_cnt, &cap, C * blocks, nullptr, sizeof(int)));
-  TRY(grow_device(&h->d_bits, &h->blocks_cap, C * blocks, nullptr, 4 * sizeof(unsigned long long)));
+  TRY(h->d_ring_m.grow(C * ring, nullptr));
+  TRY(h->d_ring_e.grow(C * ring, nullptr));
+  TRY(h->d_ring_c.grow(C * ring, nullptr));
+  TRY(h->d_bmax.grow(C * blocks, nullptr));
+  TRY(h->d_cnt.grow(C * blocks, nullptr));
+  TRY(h->d_bits.grow(4 * C * blocks, nullptr));
   h->ring = ring;
   h->blocks = blocks;
   return TDSA_OK;
@@ -201,10 +197,10 @@ int tdsa_corr_create(int device_id, int streams, int capacity, int64_t trace, si
   h->W = ref_len;
   hipError_t e = h->open(true);
   if (e == hipSuccess) e = h->in.alloc(max_host_samples * 8);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_ref), size_t(kCorrMaxRef) * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_hist), size_t(2) * size_t(streams) * kCorrMaxRef * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_sum), size_t(streams) * sizeof(CorrSummary));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_rec), size_t(streams) * size_t(capacity) * sizeof(CorrRecord));
+  if (e == hipSuccess) e = h->d_ref.alloc(size_t(kCorrMaxRef));
+  if (e == hipSuccess) e = h->d_hist.alloc(size_t(2) * size_t(streams) * kCorrMaxRef);
+  if (e == hipSuccess) e = h->d_sum.alloc(size_t(streams));
+  if (e == hipSuccess) e = h->d_rec.alloc(size_t(streams) * size_t(capacity));
   if (e != hipSuccess) {
     (void)tdsa_corr_destroy(h);
     return fail(TDSA_ERR_HIP, "correlator create: %s", hipGetErrorString(e));
@@ -223,9 +219,6 @@ int tdsa_corr_create(int device_id, int streams, int capacity, int64_t trace, si
 int tdsa_corr_destroy(tdsa_corr h) {
   if (!h) return TDSA_OK;
   h->drain();
-  h->in.release();
-  free_all({h->d_ref, h->d_hist, h->d_sum, h->d_rec, h->d_ring_m, h->d_ring_e, h->d_ring_c, h->d_bmax, h->d_cnt, h->d_bits});
-  h->close();
   delete h;
   return TDSA_OK;
 }

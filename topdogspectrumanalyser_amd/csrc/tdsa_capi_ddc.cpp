@@ -7,7 +7,7 @@ using namespace tdsa;
 // ---- zoom front end: digital down-conversion (tdsa_ddc.hip) ------------------------------------------------------
 struct tdsa_ddc_s : Feed {
   int max_phases = kDdcBlock, phases = kDdcBlock;
-  float2* d_nco = nullptr;            // [kDdcNcoTable]
+  Dev<float2> d_nco;                  // [kDdcNcoTable]
   // the base's d_taps: [max_phases][D], tap q D + r at q * D + r; d_hist: [max_phases * D] mixed inputs (float2) each
   uint32_t p_b = 0, step = 0;         // NCO: p[n] = p_b + (n - n_b) step (mod 2^32)
   long long n_b = 0;
@@ -54,8 +54,8 @@ int ddc_process(tdsa_ddc d, tdsa_plan p, bool host, int fmt, const void* in, siz
       a.D = d->D;
       a.n_taps = d->n_taps;
       a.phases = d->phases;
-      a.hist = static_cast<float2*>(d->d_hist[d->cur]);
-      a.hist_out = static_cast<float2*>(d->d_hist[d->cur ^ 1]);
+      a.hist = d->d_hist[d->cur].as<float2>();
+      a.hist_out = d->d_hist[d->cur ^ 1].as<float2>();
       a.out = static_cast<float2*>(dst);
       a.m_first = m_first;
       a.n_out = n_new;
@@ -92,7 +92,7 @@ int tdsa_ddc_create(int device_id, int decimation, int max_taps, size_t max_host
     nco[k] = make_float2(float(std::cos(th)), float(-std::sin(th)));
   }
   hipError_t e = d->open(false);
-  if (e == hipSuccess) e = hipMalloc(&d->d_nco, kDdcNcoTable * sizeof(float2));
+  if (e == hipSuccess) e = d->d_nco.alloc(kDdcNcoTable);
   if (e == hipSuccess) e = d->alloc(1, 1, sizeof(float2));
   if (e == hipSuccess) e = hipMemcpyAsync(d->d_nco, nco.data(), kDdcNcoTable * sizeof(float2), hipMemcpyHostToDevice, d->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(d->stream);   // the host copy of the table is released
@@ -112,9 +112,6 @@ int tdsa_ddc_create(int device_id, int decimation, int max_taps, size_t max_host
 int tdsa_ddc_destroy(tdsa_ddc d) {
   if (!d) return TDSA_OK;
   d->drain();
-  free_all({d->d_nco});
-  d->release();
-  d->close();
   delete d;
   return TDSA_OK;
 }

@@ -9,7 +9,7 @@ int tdsa_shader_clock(tdsa_plan p, float* shader_mhz, float* ns_per_valu) {
   if (!p) return fail(TDSA_ERR_ARG, "null plan");
   HIPCHK(hipSetDevice(p->device));
   JOIN(p);
-  if (!p->d_clock) HIPCHK(hipMalloc(&p->d_clock, size_t(p->num_cu) * 4 * sizeof(float)));
+  if (!p->d_clock) HIPCHK(p->d_clock.alloc(size_t(p->num_cu) * 4));
   const int iters = 4000;                                    // 256 000 instructions per wave: about a millisecond
   HIPCHK(launch_valu_clock(p->d_clock, p->num_cu, 200, p->stream));
   HIPCHK(hipEventRecord(p->ev0, p->stream));
@@ -98,7 +98,7 @@ int tdsa_debug_timeline(tdsa_plan p, unsigned long long* host_out_2048) {
   HIPCHK(hipSetDevice(p->device));
   JOIN(p);
   if (!p->d_dbg) {
-    HIPCHK(hipMalloc(&p->d_dbg, 2048 * sizeof(unsigned long long)));
+    HIPCHK(p->d_dbg.alloc(2048));
     HIPCHK(hipMemset(p->d_dbg, 0, 2048 * sizeof(unsigned long long)));
   }
   if (host_out_2048) {

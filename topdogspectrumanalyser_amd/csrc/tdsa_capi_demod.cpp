@@ -13,15 +13,15 @@ struct tdsa_demod_s : Feed {
   // the base's D = R; d_taps: [max_rows][R], tap q R + r at q * R + r; d_hist: [C][hist_stride] discriminator values
   // (float) each; the host staging is [C][n_in] complex64 in, [C][n_out] float out
   long long hist_stride = 0;          // floats of history per channel: max phases * R
-  float2* d_last[2] = {nullptr, nullptr};   // [C] the last raw sample, ping-pong with d_hist (the same `cur`)
+  Dev<float2> d_last[2];              // [C] the last raw sample, ping-pong with d_hist (the same `cur`)
   int pole_mode = kDemodPoleOff;
   float scale = 1.0f;
-  float* d_pole = nullptr;            // [2][kDemodPoleBlock]: (1 - c) c^i, then c^(i + 1)
-  float* d_pole_y = nullptr;          // [C]
-  float* d_pend = nullptr;            // [C][kDemodPoleBlock]
-  void* d_meas = nullptr;             // [C] count, [C] sum, [C] sumsq, [C] max, [C] min
+  Dev<float> d_pole;                  // [2][kDemodPoleBlock]: (1 - c) c^i, then c^(i + 1)
+  Dev<float> d_pole_y;                // [C]
+  Dev<float> d_pend;                  // [C][kDemodPoleBlock]
+  Dev<char> d_meas;                   // [C] count, [C] sum, [C] sumsq, [C] max, [C] min
 
-  long long* m_count() const { return static_cast<long long*>(d_meas); }
+  long long* m_count() const { return d_meas.as<long long>(); }
   double* m_sum() const { return reinterpret_cast<double*>(m_count() + C); }
   double* m_sumsq() const { return m_sum() + C; }
   float* m_max() const { return reinterpret_cast<float*>(m_sumsq() + C); }
@@ -90,8 +90,8 @@ int demod_process(tdsa_demod d, tdsa_plan p, bool host, const void* in, size_t n
       a.n_in = (long long)n_in;
       a.n0 = d->n_total;
       a.taps = d->d_taps;
-      a.hist = static_cast<float*>(d->d_hist[d->cur]);
-      a.hist_out = static_cast<float*>(d->d_hist[d->cur ^ 1]);
+      a.hist = d->d_hist[d->cur].as<float>();
+      a.hist_out = d->d_hist[d->cur ^ 1].as<float>();
       a.last = d->d_last[d->cur];
       a.last_out = d->d_last[d->cur ^ 1];
       a.hist_stride = d->hist_stride;
@@ -163,11 +163,11 @@ int tdsa_demod_create(int device_id, int mode, int channels, int decimation, int
   hipError_t e = d->open(true);
   if (e == hipSuccess) e = d->alloc(size_t(channels), size_t(channels), sizeof(float));
   for (int i = 0; i < 2; ++i)
-    if (e == hipSuccess) e = hipMalloc(&d->d_last[i], size_t(channels) * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(&d->d_pole, 2 * kDemodPoleBlock * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d->d_pole_y, size_t(channels) * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d->d_pend, size_t(channels) * kDemodPoleBlock * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d->d_meas, d->meas_bytes());
+    if (e == hipSuccess) e = d->d_last[i].alloc(size_t(channels));
+  if (e == hipSuccess) e = d->d_pole.alloc(2 * kDemodPoleBlock);
+  if (e == hipSuccess) e = d->d_pole_y.alloc(size_t(channels));
+  if (e == hipSuccess) e = d->d_pend.alloc(size_t(channels) * kDemodPoleBlock);
+  if (e == hipSuccess) e = d->d_meas.alloc(d->meas_bytes());
   if (e != hipSuccess) {
     (void)tdsa_demod_destroy(d);
     return fail(TDSA_ERR_HIP, "demod create: %s", hipGetErrorString(e));
@@ -185,9 +185,6 @@ int tdsa_demod_create(int device_id, int mode, int channels, int decimation, int
 int tdsa_demod_destroy(tdsa_demod d) {
   if (!d) return TDSA_OK;
   d->drain();
-  free_all({d->d_last[0], d->d_last[1], d->d_pole, d->d_pole_y, d->d_pend, d->d_meas});
-  d->release();
-  d->close();
   delete d;
   return TDSA_OK;
 }

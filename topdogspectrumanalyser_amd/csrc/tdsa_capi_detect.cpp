@@ -9,7 +9,7 @@ static_assert(sizeof(tdsa_detect_signal) == sizeof(DetSignal), "the public signa
 
 // ---- signal detection (tdsa_detect.hip) --------------------------------------------------------------------------
 struct tdsa_detect_s : RowAnalyser {   // the second records: sub_per_row signals per row (max_signals)
-  unsigned* d_occ = nullptr;       // [n_bins] rows in which the bin was above the threshold
+  Dev<unsigned> d_occ;             // [n_bins] rows in which the bin was above the threshold
   uint64_t rows_flagged = 0;
   int lo = 0, hi = 0, rank = 0, min_width = 1, max_gap = 0;
   float margin = 0.0f, xdb = 0.0f;
@@ -27,8 +27,8 @@ struct tdsa_detect_s : RowAnalyser {   // the second records: sub_per_row signal
     a.min_width = min_width;
     a.max_gap = max_gap;
     a.S = int(sub_per_row);
-    a.row_rec = static_cast<DetRow*>(d_row);
-    a.sig_rec = static_cast<DetSignal*>(d_sub);
+    a.row_rec = d_row.as<DetRow>();
+    a.sig_rec = d_sub.as<DetSignal>();
     a.occ = d_occ;
     return launch_detect(a, s);
   }
@@ -62,7 +62,7 @@ int tdsa_detect_create(int device_id, int n_bins, size_t max_host_rows, tdsa_det
   h->sub_unit = sizeof(DetSignal);
   hipError_t e = h->open(true);
   if (e == hipSuccess) e = h->alloc();
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_occ), size_t(n_bins) * sizeof(unsigned));
+  if (e == hipSuccess) e = h->d_occ.alloc(size_t(n_bins));
   if (e == hipSuccess) e = hipMemsetAsync(h->d_occ, 0, size_t(n_bins) * sizeof(unsigned), h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) {
@@ -76,9 +76,6 @@ int tdsa_detect_create(int device_id, int n_bins, size_t max_host_rows, tdsa_det
 int tdsa_detect_destroy(tdsa_detect h) {
   if (!h) return TDSA_OK;
   h->drain();
-  h->release();
-  free_all({h->d_occ});
-  h->close();
   delete h;
   return TDSA_OK;
 }

@@ -17,17 +17,16 @@ struct tdsa_eye_s : Lane {
   size_t max_host = 0;             // samples one host call stages
   int max_seg = 0;
   int num_cu = 256;
-  float2* d_nco = nullptr;         // [kSegNcoTable]
+  Dev<float2> d_nco;               // [kSegNcoTable]
   Staging in;                      // of a host block, 8 bytes a sample at most
-  unsigned long long* d_state = nullptr;
-  EyeClock* h_clk[2] = {nullptr, nullptr};
-  EyeClock* d_clk[2] = {nullptr, nullptr};
+  Dev<unsigned long long> d_state;
+  Pinned<EyeClock> h_clk[2];
+  Dev<EyeClock> d_clk[2];
   hipEvent_t ev_clk[2] = {nullptr, nullptr};
   bool clk_busy[2] = {false, false};
   int clk_next = 0;
-  void* d_tr = nullptr;            // the traces of a host call, grown on demand ...
-  void* h_tr = nullptr;
-  size_t d_tr_bytes = 0, h_tr_bytes = 0;
+  Dev<char> d_tr;                  // the traces of a host call, grown on demand ...
+  Pinned<char> h_tr;
   bool configured = false;
   uint64_t step = 0;
   int kind = kEyeIq, boxcar = 1, log2p = 5, rows = 128;
@@ -156,17 +155,16 @@ int tdsa_eye_create(int device_id, size_t max_host_samples, int max_segments, td
   h->max_host = max_host_samples;
   h->max_seg = max_segments;
   const std::vector<float2> nco = SegAnalyser::nco_table();
-  const size_t clk_bytes = size_t(max_segments) * sizeof(EyeClock);
   int cus = 0;
   hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id);
   if (e == hipSuccess && cus > 0) h->num_cu = cus;
   if (e == hipSuccess) e = h->open(true);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_nco), kSegNcoTable * sizeof(float2));
+  if (e == hipSuccess) e = h->d_nco.alloc(kSegNcoTable);
   if (e == hipSuccess) e = h->in.alloc(max_host_samples * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_state), tdsa_eye_s::kStateWords * 8);
+  if (e == hipSuccess) e = h->d_state.alloc(tdsa_eye_s::kStateWords);
   for (int i = 0; i < 2; ++i) {
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_clk[i]), clk_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_clk[i]), clk_bytes);
+    if (e == hipSuccess) e = h->h_clk[i].alloc(size_t(max_segments), hipHostMallocDefault);
+    if (e == hipSuccess) e = h->d_clk[i].alloc(size_t(max_segments));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_clk[i], hipEventDisableTiming);
   }
   if (e == hipSuccess) e = hipMemcpyAsync(h->d_nco, nco.data(), kSegNcoTable * sizeof(float2), hipMemcpyHostToDevice, h->stream);
@@ -183,14 +181,8 @@ int tdsa_eye_create(int device_id, size_t max_host_samples, int max_segments, td
 int tdsa_eye_destroy(tdsa_eye h) {
   if (!h) return TDSA_OK;
   h->drain();
-  free_all({h->d_nco, h->d_state, h->d_clk[0], h->d_clk[1], h->d_tr});
-  h->in.release();
-  for (int i = 0; i < 2; ++i) {
-    if (h->h_clk[i]) (void)hipHostFree(h->h_clk[i]);
-    if (h->ev_clk[i]) (void)hipEventDestroy(h->ev_clk[i]);
-  }
-  if (h->h_tr) (void)hipHostFree(h->h_tr);
-  h->close();
+  for (hipEvent_t ev : h->ev_clk)
+    if (ev) (void)hipEventDestroy(ev);
   delete h;
   return TDSA_OK;
 }
@@ -239,8 +231,8 @@ int tdsa_eye_process(tdsa_eye h, const void* in_host, size_t n_samples, size_t s
   TRY(h->own_stream());
   const size_t seg_bytes = (size_t(K - 2) << h->log2p) * h->trace_unit(), tr_bytes = size_t(n_seg) * seg_bytes;
   if (traces_host) {
-    TRY(grow_device(reinterpret_cast<char**>(&h->d_tr), &h->d_tr_bytes, tr_bytes, h->stream));
-    TRY(grow_pinned(&h->h_tr, &h->h_tr_bytes, tr_bytes, h->stream));
+    TRY(h->d_tr.grow(tr_bytes, h->stream));
+    TRY(h->h_tr.grow(tr_bytes, h->stream));
   }
   // the previous host call has waited: the staging is free
   TRY(h->in.fill(h->stream, in_host, 1, n_samples, n_samples, h->in_unit()));

@@ -44,7 +44,7 @@ struct tdsa_fsk_s : SegAnalyser {
     a.out = static_cast<float*>(out);
     a.idx = static_cast<uint8_t*>(idx);
     a.out_stride = (long long)out_stride;
-    a.rec = static_cast<FskRecord*>(d_rec);
+    a.rec = d_rec.as<FskRecord>();
     return launch_fsk(a, s);
   }
 };

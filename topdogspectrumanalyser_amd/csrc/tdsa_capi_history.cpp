@@ -15,17 +15,14 @@ struct tdsa_history_s : Lane {         // its stream: host pushes, views, the ti
   int head = 0;                       // slot of the next row
   int has_min = 0;                    // the newest push brought a min trace
   hipEvent_t ev_in = nullptr;         // the last host rows have left their pinned staging
-  float* d_ring = nullptr;            // [depth][n]
-  float* d_hold = nullptr;            // [n]
-  float* d_min = nullptr;             // [n]
-  unsigned long long* d_keys = nullptr;   // [depth] maximum and first index of each slot's row
-  void* h_in = nullptr;               // pinned staging of one host push: live, max, min rows ...
-  size_t h_in_bytes = 0;
-  float* d_in = nullptr;              // ... and where they land
-  size_t d_in_floats = 0;
-  unsigned char* d_tmp = nullptr;     // what one view needs beside its destinations
-  size_t tmp_bytes = 0;
-  void* h_small = nullptr;            // pinned: the scalars one view reads back
+  Dev<float> d_ring;                  // [depth][n]
+  Dev<float> d_hold;                  // [n]
+  Dev<float> d_min;                   // [n]
+  Dev<unsigned long long> d_keys;         // [depth] maximum and first index of each slot's row
+  Pinned<char> h_in;                  // pinned staging of one host push: live, max, min rows ...
+  Dev<float> d_in;                    // ... and where they land
+  Dev<unsigned char> d_tmp;           // what one view needs beside its destinations
+  Pinned<char> h_small;               // pinned: the scalars one view reads back
 };
 
 namespace {
@@ -82,7 +79,7 @@ size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 int hist_scratch(tdsa_history h, const size_t* bytes, int k, unsigned char** at) {
   size_t need = kSmallBytes;
   for (int i = 0; i < k; ++i) need += round256(bytes[i]);
-  TRY(grow_device(&h->d_tmp, &h->tmp_bytes, need, h->stream));
+  TRY(h->d_tmp.grow(need, h->stream));
   size_t off = kSmallBytes;
   for (int i = 0; i < k; ++i) {
     at[i] = bytes[i] ? h->d_tmp + off : nullptr;
@@ -131,7 +128,7 @@ int hist_deliver(tdsa_history h, const tdsa_history_out* out, void* dst, const v
 
 // the scalars every view reports; synchronises the handle's stream
 int hist_finish(tdsa_history h, tdsa_history_info* info, int rows, int cols, int first, bool hold_peak) {
-  Small* d = reinterpret_cast<Small*>(h->d_tmp);
+  Small* d = h->d_tmp.as<Small>();
   if (h->pushed > 0) {
     const int newest = (h->head - 1 + h->depth) % h->depth;
     HIPCHK(hipMemcpyAsync(&d->live_key, h->d_keys + newest, 8, hipMemcpyDeviceToDevice, h->stream));
@@ -200,11 +197,11 @@ int tdsa_history_create(int device_id, int depth, int n_bins, int kind, tdsa_his
   const size_t cells = size_t(depth) * size_t(n_bins);
   hipError_t e = h->open(true);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_ring), cells * 4);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_hold), size_t(n_bins) * 4);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_min), size_t(n_bins) * 4);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_keys), size_t(depth) * 8);
-  if (e == hipSuccess) e = hipHostMalloc(&h->h_small, kSmallBytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = h->d_ring.alloc(cells);
+  if (e == hipSuccess) e = h->d_hold.alloc(size_t(n_bins));
+  if (e == hipSuccess) e = h->d_min.alloc(size_t(n_bins));
+  if (e == hipSuccess) e = h->d_keys.alloc(size_t(depth));
+  if (e == hipSuccess) e = h->h_small.alloc(kSmallBytes, hipHostMallocDefault);
   if (e != hipSuccess) {
     (void)tdsa_history_destroy(h);
     return fail(TDSA_ERR_HIP, "history create: %s", hipGetErrorString(e));
@@ -221,11 +218,7 @@ int tdsa_history_create(int device_id, int depth, int n_bins, int kind, tdsa_his
 int tdsa_history_destroy(tdsa_history h) {
   if (!h) return TDSA_OK;
   h->drain();
-  free_all({h->d_ring, h->d_hold, h->d_min, h->d_keys, h->d_in, h->d_tmp});
-  if (h->h_in) (void)hipHostFree(h->h_in);
-  if (h->h_small) (void)hipHostFree(h->h_small);
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
-  h->close();
   delete h;
   return TDSA_OK;
 }
@@ -266,10 +259,10 @@ int tdsa_history_push(tdsa_history h, const float* live_host, const float* max_h
   if (h->kind != TDSA_HIST_HEIGHTS && (max_host || min_host)) return fail(TDSA_ERR_ARG, "max / min traces go with heights only");
   TRY(h->own_stream());
   const size_t n = size_t(h->n), row = round256(n * 4);
-  TRY(grow_pinned(&h->h_in, &h->h_in_bytes, 3 * row, h->stream));
-  TRY(grow_device(&h->d_in, &h->d_in_floats, 3 * row / 4, h->stream, 4));
+  TRY(h->h_in.grow(3 * row, h->stream));
+  TRY(h->d_in.grow(3 * row / 4, h->stream));
   HIPCHK(hipEventSynchronize(h->ev_in));   // the previous rows have left the staging
-  unsigned char* st = static_cast<unsigned char*>(h->h_in);
+  unsigned char* st = h->h_in.as<unsigned char>();
   const int k = min_host ? 3 : max_host ? 2 : 1;
   std::memcpy(st, live_host, n * 4);
   if (max_host) std::memcpy(st + row, max_host, n * 4);

@@ -7,7 +7,9 @@
 // (power statistics, pulse analysis, correlation search), RowAnalyser for the analysers of dB rows (signal detection, channel
 // measurements: the records grown on demand and the tail of a call) and SegAnalyser for the analysers of segments
 // (symbol recovery, FSK analysis: the symbol clock, the staged outputs, create and destroy).  All four stage a host
-// block through Staging.  The public face of the library is include/tdsa_hip.h.
+// block through Staging.  Every device buffer and pinned block of the plan, the handles and the bases is a Dev<T> or a
+// Pinned<T> (tdsa_capi_mem.hpp): pointer and capacity under one name, freed by the destructor of what holds them, so a
+// destroy is drain() and delete and names no buffer.  The public face of the library is include/tdsa_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +47,12 @@ int fail(int code, const char* fmt, ...);
     if (rc_try_ != TDSA_OK) return rc_try_;    \
   } while (0)
 
+#pragma GCC visibility pop
+}  // namespace tdsa
+#include "tdsa_capi_mem.hpp"   // Dev<T>, Pinned<T>: who owns memory here (over fail and HIPCHK)
+namespace tdsa {
+#pragma GCC visibility push(hidden)
+
 // Order the plan's main stream after everything in flight on the auxiliary streams.  Every entry point
 // that touches plan state or enqueues on the main stream calls this first; work it enqueues afterwards
 // is in turn waited for by the next overlapped launch (state_dirty).
@@ -74,47 +82,15 @@ constexpr size_t kZeroCopyMax = size_t(256) << 10;       // ... and up to 256 Ki
 
 inline bool avg_active(const tdsa_mode& m) { return m.avg_mode != TDSA_AVG_OFF && m.avg_n > 1; }
 
-// Buffers that grow on demand: `cap` units of `unit` bytes behind *ptr.  drain: the stream whose work may still use the
-// old buffer, waited for before it is freed (null: nobody can).  Synchronize, free, clear, allocate, record - in that
-// order, so that a failed allocation leaves pointer and capacity consistent.
-template <class T>
-int grow_device(T** ptr, size_t* cap, size_t need, hipStream_t drain, size_t unit = 1) {
-  if (need <= *cap) return TDSA_OK;
-  if (drain) HIPCHK(hipStreamSynchronize(drain));
-  if (*ptr) HIPCHK(hipFree(*ptr));
-  *ptr = nullptr;
-  *cap = 0;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(ptr), need * unit));
-  *cap = need;
-  return TDSA_OK;
-}
-// ... the same for pinned, device-visible host memory
-inline int grow_pinned(void** ptr, size_t* cap, size_t need, hipStream_t drain) {
-  if (need <= *cap) return TDSA_OK;
-  if (drain) HIPCHK(hipStreamSynchronize(drain));
-  if (*ptr) HIPCHK(hipHostFree(*ptr));
-  *ptr = nullptr;
-  *cap = 0;
-  HIPCHK(hipHostMalloc(ptr, need, hipHostMallocPortable | hipHostMallocMapped));
-  *cap = need;
-  return TDSA_OK;
-}
-
-// destroy paths: whichever of a handle's device buffers exist
-inline void free_all(std::initializer_list<void*> bufs) {
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-}
-
 // plan tables (tdsa_capi_plan.cpp): exp(-2 pi i k / n), k < n, evaluated in double, rounded once ...
 std::vector<float2> unit_circle(int n);
 // ... and the seeds of the column pass's twiddles of an n = 2^log2n point long transform ([big_seed_rows][16384])
 std::vector<float2> seed_table(int n, int log2n);
 // a host table into a device buffer of its own
 template <class T>
-int upload(const std::vector<T>& v, T** dst) {
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T)));
-  HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+int upload(const std::vector<T>& v, Dev<T>& dst) {
+  HIPCHK(dst.alloc(v.size()));
+  HIPCHK(hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return TDSA_OK;
 }
 
@@ -158,60 +134,55 @@ struct tdsa_plan_s {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   tdsa_mode mode{};
   bool window_set = false;
-  float* d_window[3] = {nullptr, nullptr, nullptr};   // window * input scale, per input format
-  float* d_window_perm[3] = {nullptr, nullptr, nullptr};   // the same in the frame kernel's thread order (N >= 2048)
-  float2* d_tw = nullptr;
-  float* d_hold_max = nullptr;
-  float* d_hold_min = nullptr;
+  tdsa::Dev<float> d_window[3];   // window * input scale, per input format
+  tdsa::Dev<float> d_window_perm[3];   // the same in the frame kernel's thread order (N >= 2048)
+  tdsa::Dev<float2> d_tw;
+  tdsa::Dev<float> d_hold_max;
+  tdsa::Dev<float> d_hold_min;
   long long held_max = 0, held_min = 0;
-  double* d_avg = nullptr;
+  tdsa::Dev<double> d_avg;
   int avg_count = 0;
-  float* d_lin = nullptr;                // [max_frames][N] linear power scratch (averaging modes)
-  double* d_carry = nullptr;             // [chunks][N] chunk carries of the averager scan
-  size_t carry_chunks = 0;               // chunks d_carry has room for
-  float* d_agg = nullptr;                // [grid][N] chunk aggregates formed by the frame kernel's workgroups (sizes >= 4096)
-  float* d_agg_w = nullptr;              // [max_frames] weight of each frame in its workgroup's aggregate
-  double* d_chunk_a = nullptr;           // [kAvgMaxWgChunks + 64] per chunk: product of its frames' multipliers
-  float* d_chunk_v = nullptr;            // [kAvgMaxWgChunks + 64] per chunk: 1 = has frames
+  tdsa::Dev<float> d_lin;                // [max_frames][N] linear power scratch (averaging modes)
+  tdsa::Dev<double> d_carry;             // [chunks][N] chunk carries of the averager scan
+  tdsa::Dev<float> d_agg;                // [grid][N] chunk aggregates formed by the frame kernel's workgroups (sizes >= 4096)
+  tdsa::Dev<float> d_agg_w;              // [max_frames] weight of each frame in its workgroup's aggregate
+  tdsa::Dev<double> d_chunk_a;           // [kAvgMaxWgChunks + 64] per chunk: product of its frames' multipliers
+  tdsa::Dev<float> d_chunk_v;            // [kAvgMaxWgChunks + 64] per chunk: 1 = has frames
   long long agg_w_key[7] = {-1, -1, -1, -1, -1, -1, -1};   // (count, mode, n, frames, chunks, frames per unit, path) the weights in d_agg_w were made for
-  float2* d_cplx = nullptr;              // [max_frames][N] complex spectra (real-input path)
-  float2* d_real = nullptr;              // real-input path: the selected signal(s) as complex streams (two for stereo)
-  size_t real_bytes = 0;
-  float* d_lin1 = nullptr;               // [max_frames][2][N/2+1] one-sided linear power (real-input path)
-  float* d_db1 = nullptr;                // same shape, dB
-  float2* d_dc_state = nullptr;
-  float2* d_sums = nullptr;
-  float2* d_dc_sub = nullptr;
-  float* d_tare_base = nullptr;
-  float* d_tare_acc = nullptr;
+  tdsa::Dev<float2> d_cplx;              // [max_frames][N] complex spectra (real-input path)
+  tdsa::Dev<float2> d_real;              // real-input path: the selected signal(s) as complex streams (two for stereo)
+  tdsa::Dev<float> d_lin1;               // [max_frames][2][N/2+1] one-sided linear power (real-input path)
+  tdsa::Dev<float> d_db1;                // same shape, dB
+  tdsa::Dev<float2> d_dc_state;
+  tdsa::Dev<float2> d_sums;
+  tdsa::Dev<float2> d_dc_sub;
+  tdsa::Dev<float> d_tare_base;
+  tdsa::Dev<float> d_tare_acc;
   bool tare_active = false;
   int tare_count = 0;
-  void* d_in_stage = nullptr;
-  size_t in_stage_bytes = 0;
+  tdsa::Dev<char> d_in_stage;
   // pinned bounce buffers of the host entry points for small calls (the one-frame-per-GUI-tick case): a copy from / to
   // pageable memory costs ~10 us each way in the runtime's own staging, a memcpy through pinned memory ~2 us
-  void* h_in_pin = nullptr;
-  void* h_out_pin = nullptr;
-  size_t in_pin_bytes = 0, out_pin_bytes = 0;
-  float* d_out_stage = nullptr;
-  float* d_trace_in = nullptr;
-  float* d_trace_live = nullptr;
+  tdsa::Pinned<char> h_in_pin;
+  tdsa::Pinned<char> h_out_pin;
+  tdsa::Dev<float> d_out_stage;
+  tdsa::Dev<float> d_trace_in;
+  tdsa::Dev<float> d_trace_live;
   long long frames_seen = 0;             // frames processed since the last hold reset (nan_safe rule)
-  unsigned long long* d_dbg = nullptr;   // TDSA_TIMELINE developer builds
+  tdsa::Dev<unsigned long long> d_dbg;   // TDSA_TIMELINE developer builds
   // long-frame plans, N = 2^15 .. 2^20 = N1 x 16384 (tdsa_big.hip)
   bool big = false;
-  float2* d_z = nullptr;                 // [group][N1][16384] complex64 rows after the column pass
-  float* d_acc = nullptr;                // [N1][16384] power sums of the current call (row pass output)
-  double* d_sum = nullptr;               // [N] fftshift-ed sums over the segments averaged so far
-  void* d_welch = nullptr;               // staging of tdsa_welch_export (one partial) / tdsa_welch_combine (all of them)
-  size_t welch_bytes = 0;
-  float* d_clock = nullptr;              // scratch of tdsa_shader_clock
+  tdsa::Dev<float2> d_z;                 // [group][N1][16384] complex64 rows after the column pass
+  tdsa::Dev<float> d_acc;                // [N1][16384] power sums of the current call (row pass output)
+  tdsa::Dev<double> d_sum;               // [N] fftshift-ed sums over the segments averaged so far
+  tdsa::Dev<char> d_welch;               // staging of tdsa_welch_export (one partial) / tdsa_welch_combine (all of them)
+  tdsa::Dev<float> d_clock;              // scratch of tdsa_shader_clock
   bool big_mean_in_sum = false;          // Welch calls leave the running mean as d_sum / avg_count; d_avg is formed when someone asks
-  double* d_lin64 = nullptr;             // [N] fftshift-ed power of one frame (exp / capped lin averaging)
-  double* d_sums64 = nullptr;            // [max_frames][2] exact I / Q sums of the frames of a call
-  float2* d_tw_seed = nullptr;           // [big_seed_rows][16384] per-column twiddle seeds of the column pass
-  float2* d_tw_row = nullptr;            // W_16384^m : the row pass's twiddle table
-  float* d_ones = nullptr;               // [16384] unit window for the row pass
+  tdsa::Dev<double> d_lin64;             // [N] fftshift-ed power of one frame (exp / capped lin averaging)
+  tdsa::Dev<double> d_sums64;            // [max_frames][2] exact I / Q sums of the frames of a call
+  tdsa::Dev<float2> d_tw_seed;           // [big_seed_rows][16384] per-column twiddle seeds of the column pass
+  tdsa::Dev<float2> d_tw_row;            // W_16384^m : the row pass's twiddle table
+  tdsa::Dev<float> d_ones;               // [16384] unit window for the row pass
   tdsa::BigWindow big_win[3] = {};             // the column pass's window per input format (tdsa_set_window: table or one value)
   int avg_wg_min = 128;                  // batches of more frames than this take the workgroup-chunk scan (tdsa_debug_knob "avg_wg_min")
   bool avg_f64_chunks = false;           // tdsa_debug_knob "avg_f64_chunks": always the scan over fixed 64-frame chunks with float64 aggregates
@@ -225,8 +196,8 @@ struct tdsa_plan_s {
   int smooth_n1 = 0, smooth_n2 = 0;
   int smooth_stages2 = 0;
   int smooth_radix2[tdsa::kSmoothMaxStages] = {0};   // the stages of smooth_n2 (smooth_radix: those of smooth_n1)
-  float2* d_smooth_z = nullptr;          // [max_frames][n1][n2] between the passes
-  float2* d_smooth_tw = nullptr;         // [nfft] exp(-2 pi i k / nfft)
+  tdsa::Dev<float2> d_smooth_z;          // [max_frames][n1][n2] between the passes
+  tdsa::Dev<float2> d_smooth_tw;         // [nfft] exp(-2 pi i k / nfft)
   int chirp_fuse_big = 1;                // tdsa_debug_knob "chirp_fuse_big": 0 = long chirp-z frames run chirp_pre / chirp_post as their own passes
   int chirp_single = 1;                  // tdsa_debug_knob "chirp_single": 0 = chirp-z plans run chirp_pre / two transforms / chirp_post as separate
                                          // kernels (M <= 16384; developer builds: two launches that carry the passes), separate row passes (M > 16384)
@@ -234,7 +205,7 @@ struct tdsa_plan_s {
   int big_group = 64;                    // segments per column-pass / row-pass round (one round for the K = 64 Welch capture)
   int big_fuse_gather = 0;               // tdsa_debug_knob "big_fuse_gather": 1 = Welch captures of one round run row pass + gather + finish as ONE
                                          // launch with a ticket queue (measured: profiles/r06_c5_fused_gather.txt)
-  void* d_bigq = nullptr;                // the queue's counters (32 bytes, zeroed once; they only grow)
+  tdsa::Dev<char> d_bigq;                // the queue's counters (32 bytes, zeroed once; they only grow)
   unsigned long long bigq_tickets = 0, bigq_rows = 0;   // what the next launch starts from
   // frame lengths that are not a power of two (tdsa_chirp.hip): chirp-z on the m_fft-point frame kernel
   bool chirp = false;
@@ -242,26 +213,24 @@ struct tdsa_plan_s {
   bool chirp_big = false;                // M > 16384: the two M-point transforms run on the long-frame kernels (N1 x 16384)
   int chirp_split = 0;                   // frames above 2^19 points: H = ceil(N / 2); the convolution runs as four half-length
                                          // sub-convolutions of M = 2^20 points on rows [2F][M] (tdsa_chirp.hip)
-  float2* d_chirp_bm = nullptr;          // [M] spectra of the filter segments b[m - H], b[m + H] (d_chirp_b: b[m]), split plans only
-  float2* d_chirp_bp = nullptr;
-  float2* d_chirp_a = nullptr;           // [nfft] a[n] = exp(-i pi n^2 / nfft)
-  float2* d_chirp_b = nullptr;           // [M]    FFT_M of conj(a) wrapped around M
-  float2* d_chirp_aw[3] = {nullptr, nullptr, nullptr};   // [nfft] window * input scale * a[n] per input format (M <= 16384: the
+  tdsa::Dev<float2> d_chirp_bm;          // [M] spectra of the filter segments b[m - H], b[m + H] (d_chirp_b: b[m]), split plans only
+  tdsa::Dev<float2> d_chirp_bp;
+  tdsa::Dev<float2> d_chirp_a;           // [nfft] a[n] = exp(-i pi n^2 / nfft)
+  tdsa::Dev<float2> d_chirp_b;           // [M]    FFT_M of conj(a) wrapped around M
+  tdsa::Dev<float2> d_chirp_aw[3];   // [nfft] window * input scale * a[n] per input format (M <= 16384: the
                                          // unpack / window / chirp pass rides the first transform's loads)
-  float2* d_u0 = nullptr;                // [max_frames][M] work rows (allocated on first use)
-  float2* d_u1 = nullptr;
-  void* d_scratch = nullptr;             // grows on demand: results of tdsa_rows_stats / tdsa_rows_top_peaks
-  size_t scratch_bytes = 0;
+  tdsa::Dev<float2> d_u0;                // [max_frames][M] work rows (allocated on first use)
+  tdsa::Dev<float2> d_u1;
+  tdsa::Dev<char> d_scratch;             // grows on demand: results of tdsa_rows_stats / tdsa_rows_top_peaks
   // per-frame scalars (tdsa_set_frame_stats): the results of the last kFsKeep calls.  A call takes the next of ITS stream's
   // kFsKeep slots, so a slot is only ever rewritten by later work of the stream that wrote it (in order, no events between
   // the frame-kernel launches), and the last kFsKeep calls overall are always still there.
   static constexpr int kFsKeep = 4;
   struct FsSlot {
-    void* d_part = nullptr;              // [frames][waves per frame] records of the frame kernel's STATS epilogue
-    float* d_peak = nullptr;             // [frames]
-    int* d_bin = nullptr;
-    double* d_band = nullptr;
-    size_t cap = 0;
+    tdsa::Dev<char> d_part;              // [frames][waves per frame] records of the frame kernel's STATS epilogue
+    tdsa::Dev<float> d_peak;             // [frames]
+    tdsa::Dev<int> d_bin;
+    tdsa::Dev<double> d_band;
     int n_frames = 0;
     int state = 0;                       // 0: nothing, 1: results (in flight on `stream`), 2: the call produced no rows to take them from
     bool pending = false;                // the frame kernel's records are there, frame_stats_finish_kernel has not run yet
@@ -290,8 +259,12 @@ namespace tdsa {
 // rule keeps their state coherent when it moves between streams: a handle's launches are totally ordered through
 // ev_done, whichever stream each goes on.  Every launch on a stream s is bracketed by order(s) and done(s): s first
 // waits for ev_done if the last launch went elsewhere, and afterwards ev_done stands for this one.  The handles that
-// wait for their stream in every call (constellation, density, waterfall, trace) use device, stream, drain and close
-// only; they go behind a producer with plan_order_before.
+// wait for their stream in every call (constellation, density, waterfall, trace) use device, stream and drain only;
+// they go behind a producer with plan_order_before.
+//
+// A handle is deleted only after drain(), which also makes its device current: tdsa_<x>_destroy is null check, drain(),
+// delete - also of a handle whose create failed half way.  The members of the derived handle, its buffers, go first;
+// then ~Lane destroys the events and the stream.
 struct Lane {
   int device = 0;
   hipStream_t stream = nullptr;    // the handle's own: host entry points, views, the timer
@@ -307,14 +280,17 @@ struct Lane {
     if (e == hipSuccess && timer) e = hipEventCreate(&ev_t1);
     return e;
   }
-  // destroy, before the buffers are freed: nothing of the handle's is in flight any more, on any stream ...
+  // before delete: nothing of the handle's is in flight any more, on any stream
   void drain() {
     (void)hipSetDevice(device);
     if (ev_done) (void)hipEventSynchronize(ev_done);
     if (stream) (void)hipStreamSynchronize(stream);
   }
-  // ... and after: the events, then the stream (also of a handle whose create failed half way)
-  void close() {
+  Lane() = default;
+  Lane(const Lane&) = delete;
+  Lane& operator=(const Lane&) = delete;
+  // after the buffers: the events, then the stream
+  ~Lane() {
     for (hipEvent_t ev : {ev_done, ev_t0, ev_t1})
       if (ev) (void)hipEventDestroy(ev);
     if (stream) (void)hipStreamDestroy(stream);
@@ -370,25 +346,20 @@ struct Lane {
 // The staging of a synchronous host entry point: a pinned block and the device block it is copied to.  The host call
 // that filled it has waited for its stream before it returned, so the next one finds it free.
 struct Staging {
-  void* h_in = nullptr;
-  void* d_in = nullptr;
+  Pinned<char> h_in;
+  Dev<char> d_in;
 
   // create, inside the chain that began with open()
   hipError_t alloc(size_t bytes) {
-    const hipError_t e = hipHostMalloc(&h_in, bytes, hipHostMallocDefault);
-    return e == hipSuccess ? hipMalloc(&d_in, bytes) : e;
-  }
-  // destroy: whichever of the two exist
-  void release() {
-    if (d_in) (void)hipFree(d_in);
-    if (h_in) (void)hipHostFree(h_in);
+    const hipError_t e = h_in.alloc(bytes, hipHostMallocDefault);
+    return e == hipSuccess ? d_in.alloc(bytes) : e;
   }
   // `rows` rows of n units of `unit` bytes, row r at in + r * stride units, back to back into h_in; then one copy to
   // d_in, enqueued on s
   int fill(hipStream_t s, const void* in, size_t rows, size_t n, size_t stride, size_t unit) {
     const size_t row = n * unit;
     for (size_t r = 0; r < rows; ++r)
-      std::memcpy(static_cast<char*>(h_in) + r * row, static_cast<const char*>(in) + r * stride * unit, row);
+      std::memcpy(h_in + r * row, static_cast<const char*>(in) + r * stride * unit, row);
     HIPCHK(hipMemcpyAsync(d_in, h_in, rows * row, hipMemcpyHostToDevice, s));
     return TDSA_OK;
   }
@@ -429,15 +400,15 @@ struct Feed : Lane {
   int D = 1;                          // inputs per output
   int max_taps = 1, n_taps = 0;
   size_t taps_len = 0;                // floats of d_taps: the filter's padded [rows][row length]
-  float* d_taps = nullptr;            // zero beyond n_taps
-  void* d_hist[2] = {nullptr, nullptr};   // hist_bytes each, ping-pong
+  Dev<float> d_taps;                  // zero beyond n_taps
+  Dev<char> d_hist[2];                // hist_bytes each, ping-pong
   size_t hist_bytes = 0;
   int cur = 0;
   long long n_total = 0;              // inputs (per row) since the last reset
   size_t max_host = 0;                // samples, all rows together, one host call stages
   Staging in;                         // of a host block, rows back to back ...
-  void* d_out = nullptr;              // ... and of its outputs
-  void* h_out = nullptr;
+  Dev<char> d_out;                    // ... and of its outputs
+  Pinned<char> h_out;
 
   long long m_first() const { return (n_total + D - 1) / D; }   // the next output
   size_t outputs(size_t n_in) const { return size_t((n_total + (long long)n_in + D - 1) / D - m_first()); }
@@ -446,20 +417,14 @@ struct Feed : Lane {
   // brings at most max_host / in_rows samples per row, which complete at most that / D + 1 outputs per row.
   hipError_t alloc(size_t in_rows, size_t out_rows, size_t out_unit) {
     const size_t ob = ((max_host / in_rows) / size_t(D) + 1) * out_rows * out_unit;
-    hipError_t e = hipMalloc(&d_taps, taps_len * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_hist[0], hist_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_hist[1], hist_bytes);
+    hipError_t e = d_taps.alloc(taps_len);
+    if (e == hipSuccess) e = d_hist[0].alloc(hist_bytes);
+    if (e == hipSuccess) e = d_hist[1].alloc(hist_bytes);
     if (e == hipSuccess) e = in.alloc(max_host * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_out, ob);
-    if (e == hipSuccess) e = hipHostMalloc(&h_out, ob, hipHostMallocDefault);
+    if (e == hipSuccess) e = d_out.alloc(ob);
+    if (e == hipSuccess) e = h_out.alloc(ob, hipHostMallocDefault);
     if (e == hipSuccess) e = hipMemsetAsync(d_taps, 0, taps_len * sizeof(float), stream);
     return e;
-  }
-  // destroy, between drain() and close(): whichever of them exist
-  void release() {
-    free_all({d_taps, d_hist[0], d_hist[1], d_out});
-    in.release();
-    if (h_out) (void)hipHostFree(h_out);
   }
 
   // zero history and input count, enqueued on the handle's own stream
@@ -548,7 +513,7 @@ struct Feed : Lane {
     if (n) HIPCHK(hipMemcpyAsync(f->h_out, f->d_out, c.out_rows * orow, hipMemcpyDeviceToHost, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
     for (size_t r = 0; n && r < c.out_rows; ++r)
-      std::memcpy(static_cast<char*>(c.out) + r * c.out_stride * c.out_unit, static_cast<const char*>(f->h_out) + r * orow, orow);
+      std::memcpy(static_cast<char*>(c.out) + r * c.out_stride * c.out_unit, f->h_out + r * orow, orow);
     *c.n_out = n;
     return TDSA_OK;
   }
@@ -648,20 +613,14 @@ struct RowAnalyser : Lane {
   int n_bins = 0;
   size_t max_host = 0;             // rows one host call stages
   Staging in;
-  void* d_row = nullptr;           // the records of either entry point ...
-  void* d_sub = nullptr;
-  size_t row_cap = 0, sub_cap = 0;                     // ... in records ...
-  size_t row_unit = 0, sub_unit = 0, sub_per_row = 1;  // ... of so many bytes; d_sub holds sub_per_row per row
+  Dev<char> d_row;                 // the records of either entry point ...
+  Dev<char> d_sub;
+  size_t row_unit = 0, sub_unit = 0, sub_per_row = 1;  // ... of so many bytes each; d_sub holds sub_per_row per row
   uint64_t rows_seen = 0;
   bool configured = false;
 
   // create, inside the chain that began with open(); n_bins and max_host are set
   hipError_t alloc() { return in.alloc(max_host * size_t(n_bins) * sizeof(float)); }
-  // destroy, between drain() and close()
-  void release() {
-    in.release();
-    free_all({d_row, d_sub});
-  }
 
   static int check(const RowAnalyser* h, const RowNames& who, const void* rows, const void* row_rec, const void* sub_rec) {
     if (!h) return fail(TDSA_ERR_ARG, "null %s", who.handle);
@@ -675,8 +634,8 @@ struct RowAnalyser : Lane {
   // one call on stream s, which the caller has put behind the last launch, over device rows
   template <class H, class R>
   static int run(H* h, hipStream_t s, const float* rows, size_t n_rows, R* row_host, void* sub_host) {
-    TRY(grow_device(&h->d_row, &h->row_cap, n_rows, h->last, h->row_unit));
-    TRY(grow_device(&h->d_sub, &h->sub_cap, n_rows * h->sub_per_row, h->last, h->sub_unit));
+    TRY(h->d_row.grow(n_rows * h->row_unit, h->last));
+    TRY(h->d_sub.grow(n_rows * h->sub_per_row * h->sub_unit, h->last));
     HIPCHK(h->launch(s, rows, n_rows));
     HIPCHK(hipMemcpyAsync(row_host, h->d_row, n_rows * h->row_unit, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(sub_host, h->d_sub, n_rows * h->sub_per_row * h->sub_unit, hipMemcpyDeviceToHost, s));
@@ -696,7 +655,7 @@ struct RowAnalyser : Lane {
     if (n_rows == 0) return TDSA_OK;
     TRY(h->own_stream());
     TRY(h->in.fill(h->stream, rows, 1, n_rows * size_t(h->n_bins), 0, sizeof(float)));
-    return run(h, h->stream, static_cast<const float*>(h->in.d_in), n_rows, row_host, sub_host);
+    return run(h, h->stream, h->in.d_in.template as<const float>(), n_rows, row_host, sub_host);
   }
   // dev: in place, on plan p's stream (null: the handle's own)
   template <class H, class R>
@@ -737,12 +696,11 @@ static_assert(TDSA_SYMSYNC_AUTO == TDSA_FSK_AUTO && TDSA_SYMSYNC_FIXED == TDSA_F
 // plan's device.  None of them makes a HIP call.
 struct SegAnalyser : Lane {
   size_t max_host = 0;             // samples one host call stages
-  float2* d_nco = nullptr;         // [kSegNcoTable]
+  Dev<float2> d_nco;               // [kSegNcoTable]
   Staging in;                      // of a host block, 8 bytes a sample at most ...
-  char* d_out = nullptr;           // ... of its outputs, [out_cap()] of out_unit bytes, then [out_cap()] of aux_unit ...
-  char* h_out = nullptr;
-  void* d_rec = nullptr;           // ... and of the records of either entry point, grown on demand
-  size_t rec_cap = 0;
+  Dev<char> d_out;                 // ... of its outputs, [out_cap()] of out_unit bytes, then [out_cap()] of aux_unit ...
+  Pinned<char> h_out;
+  Dev<char> d_rec;                 // ... and of the records of either entry point, grown on demand
   bool configured = false;
   uint64_t step = 0, delta_fx = 0;
   uint32_t nu = 0;
@@ -778,10 +736,10 @@ struct SegAnalyser : Lane {
     const std::vector<float2> nco = nco_table();
     const size_t out_bytes = h->out_cap() * (H::out_unit + H::aux_unit);
     hipError_t e = h->open(true);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_nco), kSegNcoTable * sizeof(float2));
+    if (e == hipSuccess) e = h->d_nco.alloc(kSegNcoTable);
     if (e == hipSuccess) e = h->in.alloc(max_host_samples * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_out), out_bytes);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_out), out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = h->d_out.alloc(out_bytes);
+    if (e == hipSuccess) e = h->h_out.alloc(out_bytes, hipHostMallocDefault);
     if (e == hipSuccess) e = hipMemcpyAsync(h->d_nco, nco.data(), kSegNcoTable * sizeof(float2), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // the host copy of the table is released
     if (e != hipSuccess) {
@@ -796,10 +754,6 @@ struct SegAnalyser : Lane {
   static int destroy(H* h) {
     if (!h) return TDSA_OK;
     h->drain();
-    free_all({h->d_nco, h->d_out, h->d_rec});
-    h->in.release();
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    h->close();
     delete h;
     return TDSA_OK;
   }
@@ -873,7 +827,7 @@ struct SegAnalyser : Lane {
       return fail(TDSA_ERR_ARG, "block of %zu samples in %d segments of %zu, the handle stages at most %zu "
                   "(max_host_samples)", n_samples, n_seg, seg_len, h->max_host);
     TRY(h->own_stream());
-    TRY(grow_device(&h->d_rec, &h->rec_cap, size_t(n_seg), h->stream, H::rec_unit));
+    TRY(h->d_rec.grow(size_t(n_seg) * H::rec_unit, h->stream));
     // the previous host call has waited: the staging is free
     TRY(h->in.fill(h->stream, in, 1, n_samples, n_samples, h->in_unit()));
     const size_t rows = size_t(n_seg) * size_t(K), aux_at = h->out_cap() * H::out_unit;
@@ -900,7 +854,7 @@ struct SegAnalyser : Lane {
     hipStream_t s;
     TRY(h->producer_stream(p, &s));
     TRY(h->order(s));
-    TRY(grow_device(&h->d_rec, &h->rec_cap, size_t(n_seg), h->last, H::rec_unit));
+    TRY(h->d_rec.grow(size_t(n_seg) * H::rec_unit, h->last));
     HIPCHK(h->launch(s, in, seg_len, hop, n_seg, out, out_stride, aux, K));
     HIPCHK(hipMemcpyAsync(rec, h->d_rec, size_t(n_seg) * H::rec_unit, hipMemcpyDeviceToHost, s));
     TRY(h->done(s));

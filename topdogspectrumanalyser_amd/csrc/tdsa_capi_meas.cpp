@@ -12,7 +12,7 @@ static_assert(TDSA_MEAS_MAX_CHANNELS == kMeasMaxChannels, "the public channel co
 
 // ---- channel measurements (tdsa_meas.hip) ------------------------------------------------------------------------
 struct tdsa_meas_s : RowAnalyser {   // the second records: sub_per_row channels per row
-  float* d_limit = nullptr;        // [n_bins] the limit line, when there is one
+  Dev<float> d_limit;              // [n_bins] the limit line, when there is one
   bool has_limit = false;
   int relative = 0;
   uint64_t rows_failed = 0;
@@ -37,8 +37,8 @@ struct tdsa_meas_s : RowAnalyser {   // the second records: sub_per_row channels
     a.xdb = xdb;
     a.limit = has_limit ? d_limit : nullptr;
     a.relative = relative;
-    a.row_rec = static_cast<MeasRow*>(d_row);
-    a.ch_rec = static_cast<MeasChannel*>(d_sub);
+    a.row_rec = d_row.as<MeasRow>();
+    a.ch_rec = d_sub.as<MeasChannel>();
     return launch_meas(a, s);
   }
   void tally(const tdsa_meas_row* row_host, size_t n_rows) {
@@ -71,7 +71,7 @@ int tdsa_meas_create(int device_id, int n_bins, size_t max_host_rows, tdsa_meas*
   h->sub_unit = sizeof(MeasChannel);
   hipError_t e = h->open(true);
   if (e == hipSuccess) e = h->alloc();
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_limit), size_t(n_bins) * sizeof(float));
+  if (e == hipSuccess) e = h->d_limit.alloc(size_t(n_bins));
   if (e != hipSuccess) {
     (void)tdsa_meas_destroy(h);
     return fail(TDSA_ERR_HIP, "meas create: %s", hipGetErrorString(e));
@@ -83,9 +83,6 @@ int tdsa_meas_create(int device_id, int n_bins, size_t max_host_rows, tdsa_meas*
 int tdsa_meas_destroy(tdsa_meas h) {
   if (!h) return TDSA_OK;
   h->drain();
-  h->release();
-  free_all({h->d_limit});
-  h->close();
   delete h;
   return TDSA_OK;
 }

@@ -16,13 +16,11 @@ static_assert(TDSA_MODQ_NONFINITE == kModqFlagNonFinite && TDSA_MODQ_DEGENERATE 
 struct tdsa_modq_s : Lane {
   size_t max_host = 0;             // symbols one host call stages
   Staging in;
-  ModqTable* d_tab = nullptr;
+  Dev<ModqTable> d_tab;
   bool has_points = false;
-  void* d_rec = nullptr;
-  size_t rec_cap = 0;
-  char* d_out = nullptr;
-  void* h_out = nullptr;
-  size_t d_out_bytes = 0, h_out_bytes = 0;
+  Dev<char> d_rec;
+  Dev<char> d_out;
+  Pinned<char> h_out;
 
   hipError_t launch(hipStream_t s, const void* in, int K, size_t in_stride, int n_seg, void* idx, size_t out_stride, void* err) {
     ModqLaunch a;
@@ -34,7 +32,7 @@ struct tdsa_modq_s : Lane {
     a.idx = static_cast<uint8_t*>(idx);
     a.err = static_cast<float2*>(err);
     a.out_stride = (long long)out_stride;
-    a.rec = static_cast<ModqRecord*>(d_rec);
+    a.rec = d_rec.as<ModqRecord>();
     return launch_modq(a, s);
   }
 };
@@ -78,7 +76,7 @@ int tdsa_modq_create(int device_id, size_t max_host_symbols, tdsa_modq* out) {
   h->max_host = max_host_symbols;
   hipError_t e = h->open(true);
   if (e == hipSuccess) e = h->in.alloc(max_host_symbols * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_tab), sizeof(ModqTable));
+  if (e == hipSuccess) e = h->d_tab.alloc(1);
   if (e != hipSuccess) {
     (void)tdsa_modq_destroy(h);
     return fail(TDSA_ERR_HIP, "modq create: %s", hipGetErrorString(e));
@@ -90,10 +88,6 @@ int tdsa_modq_create(int device_id, size_t max_host_symbols, tdsa_modq* out) {
 int tdsa_modq_destroy(tdsa_modq h) {
   if (!h) return TDSA_OK;
   h->drain();
-  free_all({h->d_tab, h->d_rec, h->d_out});
-  h->in.release();
-  if (h->h_out) (void)hipHostFree(h->h_out);
-  h->close();
   delete h;
   return TDSA_OK;
 }
@@ -135,9 +129,9 @@ int tdsa_modq_process(tdsa_modq h, const void* in_host, size_t n_symbols, int K,
     return fail(TDSA_ERR_ARG, "block of %zu symbols, the handle stages at most %zu (max_host_symbols)", n_symbols, h->max_host);
   TRY(h->own_stream());
   const size_t rows = size_t(n_seg) * size_t(K), idx_at = err_host ? rows * sizeof(float2) : 0, bytes = idx_at + rows;
-  TRY(grow_device(&h->d_rec, &h->rec_cap, size_t(n_seg), h->stream, sizeof(ModqRecord)));
-  TRY(grow_device(&h->d_out, &h->d_out_bytes, bytes, h->stream));
-  TRY(grow_pinned(&h->h_out, &h->h_out_bytes, bytes, h->stream));
+  TRY(h->d_rec.grow(size_t(n_seg) * sizeof(ModqRecord), h->stream));
+  TRY(h->d_out.grow(bytes, h->stream));
+  TRY(h->h_out.grow(bytes, h->stream));
   // the previous host call has waited: the staging is free
   TRY(h->in.fill(h->stream, in_host, 1, n_symbols, n_symbols, sizeof(float2)));
   HIPCHK(h->launch(h->stream, h->in.d_in, K, in_stride, n_seg, h->d_out + idx_at, size_t(K), err_host ? h->d_out : nullptr));
@@ -162,7 +156,7 @@ int tdsa_modq_process_dev(tdsa_modq h, tdsa_plan p, const void* in_dev, int K, s
   hipStream_t s;
   TRY(h->producer_stream(p, &s));
   TRY(h->order(s));
-  TRY(grow_device(&h->d_rec, &h->rec_cap, size_t(n_seg), h->last, sizeof(ModqRecord)));
+  TRY(h->d_rec.grow(size_t(n_seg) * sizeof(ModqRecord), h->last));
   HIPCHK(h->launch(s, in_dev, K, in_stride, n_seg, idx_dev, out_stride, err_dev));
   HIPCHK(hipMemcpyAsync(records_host, h->d_rec, size_t(n_seg) * sizeof(ModqRecord), hipMemcpyDeviceToHost, s));
   TRY(h->done(s));

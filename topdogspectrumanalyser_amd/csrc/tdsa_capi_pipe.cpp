@@ -19,12 +19,12 @@ struct tdsa_pipe_s {
   bool rows_u8 = false;     // ... as bytes under the display's levels (1 B per bin over PCIe instead of 4)
   float lo_db = -120.0f, hi_db = 0.0f;
   struct Slot {
-    void* h_in = nullptr;
-    void* d_in = nullptr;
-    float* h_out = nullptr;
-    float* d_out = nullptr;
-    unsigned char* h_u8 = nullptr;
-    unsigned char* d_u8 = nullptr;
+    Pinned<char> h_in;
+    Dev<char> d_in;
+    Pinned<float> h_out;
+    Dev<float> d_out;
+    Pinned<unsigned char> h_u8;
+    Dev<unsigned char> d_u8;
     hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
     int n_frames = 0;
     bool acquired = false, in_flight = false;
@@ -51,7 +51,7 @@ int tdsa_pipe_create(tdsa_plan p, int in_format, size_t slot_samples, int n_slot
   q->rows = want_rows != 0;
   q->rows_host = want_rows == 1;
   q->rows_u8 = want_rows == 3;
-  q->slots.resize(size_t(n_slots));
+  q->slots = std::vector<tdsa_pipe_s::Slot>(size_t(n_slots));   // (a Slot owns its buffers: it cannot move)
   const size_t in_bytes = slot_samples * size_t(bytes_per_sample(in_format));
   const size_t out_rows = p->big ? 1 : size_t(p->max_frames);
   const size_t out_bytes = out_rows * size_t(p->nfft) * sizeof(float);
@@ -63,16 +63,15 @@ int tdsa_pipe_create(tdsa_plan p, int in_format, size_t slot_samples, int n_slot
   if ((e = hipStreamCreateWithFlags(&q->s_in, hipStreamNonBlocking)) != hipSuccess) return bail(e, "stream");
   if ((e = hipStreamCreateWithFlags(&q->s_out, hipStreamNonBlocking)) != hipSuccess) return bail(e, "stream");
   for (auto& sl : q->slots) {
-    if ((e = hipHostMalloc(&sl.h_in, in_bytes, hipHostMallocDefault)) != hipSuccess) return bail(e, "pinned input slot");
-    if ((e = hipMalloc(&sl.d_in, in_bytes)) != hipSuccess) return bail(e, "device input slot");
+    if ((e = sl.h_in.alloc(in_bytes, hipHostMallocDefault)) != hipSuccess) return bail(e, "pinned input slot");
+    if ((e = sl.d_in.alloc(in_bytes)) != hipSuccess) return bail(e, "device input slot");
     if (q->rows) {
-      if (q->rows_host &&
-          (e = hipHostMalloc(reinterpret_cast<void**>(&sl.h_out), out_bytes, hipHostMallocDefault)) != hipSuccess)
+      if (q->rows_host && (e = sl.h_out.alloc(out_bytes / sizeof(float), hipHostMallocDefault)) != hipSuccess)
         return bail(e, "pinned output slot");
-      if ((e = hipMalloc(reinterpret_cast<void**>(&sl.d_out), out_bytes)) != hipSuccess) return bail(e, "device output slot");
+      if ((e = sl.d_out.alloc(out_bytes / sizeof(float))) != hipSuccess) return bail(e, "device output slot");
       if (q->rows_u8) {
-        if ((e = hipMalloc(reinterpret_cast<void**>(&sl.d_u8), out_bytes / 4)) != hipSuccess) return bail(e, "device byte rows");
-        if ((e = hipHostMalloc(reinterpret_cast<void**>(&sl.h_u8), out_bytes / 4, hipHostMallocDefault)) != hipSuccess)
+        if ((e = sl.d_u8.alloc(out_bytes / 4)) != hipSuccess) return bail(e, "device byte rows");
+        if ((e = sl.h_u8.alloc(out_bytes / 4, hipHostMallocDefault)) != hipSuccess)
           return bail(e, "pinned byte rows");
       }
     }
@@ -91,10 +90,6 @@ int tdsa_pipe_destroy(tdsa_pipe q) {
   if (q->plan) (void)tdsa_synchronize(q->plan);
   if (q->s_out) (void)hipStreamSynchronize(q->s_out);
   for (auto& sl : q->slots) {
-    free_all({sl.d_in, sl.d_out, sl.d_u8});
-    if (sl.h_in) (void)hipHostFree(sl.h_in);
-    if (sl.h_out) (void)hipHostFree(sl.h_out);
-    if (sl.h_u8) (void)hipHostFree(sl.h_u8);
     if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);
     if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     if (sl.ev_d2h) (void)hipEventDestroy(sl.ev_d2h);

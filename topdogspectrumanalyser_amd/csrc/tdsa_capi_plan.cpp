@@ -153,39 +153,38 @@ static int plan_init(tdsa_plan p) {
   HIPCHK(hipEventCreate(&p->ev0));
   HIPCHK(hipEventCreate(&p->ev1));
   HIPCHK(hipEventCreateWithFlags(&p->ev_state, hipEventDisableTiming));
-  const size_t nb = size_t(nfft) * sizeof(float);
-  for (int f = 0; f < 3; ++f) HIPCHK(hipMalloc(&p->d_window[f], nb));
+  for (int f = 0; f < 3; ++f) HIPCHK(p->d_window[f].alloc(size_t(nfft)));
   if (!p->big && !p->chirp && p->log2n >= 11)     // only the 3-pass sizes read the permuted table (Cfg::WIN_LDS below)
-    for (int f = 0; f < 3; ++f) HIPCHK(hipMalloc(&p->d_window_perm[f], nb));
+    for (int f = 0; f < 3; ++f) HIPCHK(p->d_window_perm[f].alloc(size_t(nfft)));
   const int tw_n = p->chirp ? (p->chirp_big ? (1 << kMaxLog2N) : p->m_fft) : nfft;       // the size the frame kernel transforms
-  HIPCHK(hipMalloc(&p->d_hold_max, nb));
-  HIPCHK(hipMalloc(&p->d_hold_min, nb));
-  HIPCHK(hipMalloc(&p->d_avg, size_t(nfft) * sizeof(double)));
-  HIPCHK(hipMalloc(&p->d_dc_state, sizeof(float2)));
-  HIPCHK(hipMalloc(&p->d_sums, (size_t(max_frames) + 8) * sizeof(float2)));   // (+ 7: block sums of overlapping frames)
-  HIPCHK(hipMalloc(&p->d_dc_sub, size_t(max_frames) * sizeof(float2)));
-  HIPCHK(hipMalloc(&p->d_tare_base, nb));
-  HIPCHK(hipMalloc(&p->d_tare_acc, nb));
-  HIPCHK(hipMalloc(&p->d_trace_in, nb));
-  HIPCHK(hipMalloc(&p->d_trace_live, nb));
+  HIPCHK(p->d_hold_max.alloc(size_t(nfft)));
+  HIPCHK(p->d_hold_min.alloc(size_t(nfft)));
+  HIPCHK(p->d_avg.alloc(size_t(nfft)));
+  HIPCHK(p->d_dc_state.alloc(1));
+  HIPCHK(p->d_sums.alloc(size_t(max_frames) + 8));   // (+ 7: block sums of overlapping frames)
+  HIPCHK(p->d_dc_sub.alloc(size_t(max_frames)));
+  HIPCHK(p->d_tare_base.alloc(size_t(nfft)));
+  HIPCHK(p->d_tare_acc.alloc(size_t(nfft)));
+  HIPCHK(p->d_trace_in.alloc(size_t(nfft)));
+  HIPCHK(p->d_trace_live.alloc(size_t(nfft)));
   HIPCHK(hipMemsetAsync(p->d_dc_state, 0, sizeof(float2), p->stream));
   HIPCHK(hipMemsetAsync(p->d_avg, 0, size_t(nfft) * sizeof(double), p->stream));
-  TRY(upload(unit_circle(tw_n), &p->d_tw));      // twiddle table exp(-2 pi i m / N)
+  TRY(upload(unit_circle(tw_n), p->d_tw));      // twiddle table exp(-2 pi i m / N)
   if (p->chirp) TRY(chirp_plan_init(p));
   if (big) {
-    HIPCHK(hipMalloc(&p->d_sum, size_t(nfft) * sizeof(double)));
-    HIPCHK(hipMalloc(&p->d_lin64, size_t(nfft) * sizeof(double)));
+    HIPCHK(p->d_sum.alloc(size_t(nfft)));
+    HIPCHK(p->d_lin64.alloc(size_t(nfft)));
     {   // per-workgroup partial power sums of the row pass: [N1 * split][16384], split = workgroups per k1 row
       const int n1 = nfft >> 14;
       int split = p->num_cu / n1 > 1 ? p->num_cu / n1 : 1;
       const int gmax = p->max_frames < p->big_group ? p->max_frames : p->big_group;
       if (split > gmax) split = gmax;
-      HIPCHK(hipMalloc(&p->d_acc, size_t(n1) * split * (size_t(1) << 14) * sizeof(float)));
+      HIPCHK(p->d_acc.alloc(size_t(n1) * split * (size_t(1) << 14)));
     }
     const int nrow = 1 << kMaxLog2N;
-    TRY(upload(seed_table(nfft, p->log2n), &p->d_tw_seed));
-    TRY(upload(unit_circle(nrow), &p->d_tw_row));
-    TRY(upload(std::vector<float>(nrow, 1.0f), &p->d_ones));
+    TRY(upload(seed_table(nfft, p->log2n), p->d_tw_seed));
+    TRY(upload(unit_circle(nrow), p->d_tw_row));
+    TRY(upload(std::vector<float>(nrow, 1.0f), p->d_ones));
   }
   TRY(reset_hold(p, true, true));
   // defaults = HackRF plain branch (hackrf_samples.py:382-383)
@@ -207,18 +206,6 @@ int tdsa_destroy(tdsa_plan p) {
   for (hipStream_t a : p->aux)
     if (a) (void)hipStreamSynchronize(a);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  free_all({p->d_window[0], p->d_window[1], p->d_window[2], p->d_window_perm[0], p->d_window_perm[1],
-                  p->d_window_perm[2], p->d_tw, p->d_hold_max, p->d_hold_min,
-                  p->d_avg, p->d_lin, p->d_carry, p->d_agg, p->d_agg_w, p->d_chunk_a, p->d_chunk_v, p->d_cplx, p->d_real, p->d_lin1, p->d_db1, p->d_dc_state, p->d_sums, p->d_dc_sub,
-                  p->d_tare_base, p->d_tare_acc, p->d_in_stage, p->d_out_stage, p->d_trace_in,
-                  p->d_trace_live, p->d_scratch, p->d_z, p->d_welch, p->d_clock, p->d_smooth_tw, p->d_smooth_z, p->d_chirp_aw[0], p->d_chirp_aw[1], p->d_chirp_aw[2], p->d_chirp_bm, p->d_chirp_bp, p->d_chirp_a, p->d_chirp_b, p->d_u0, p->d_u1, p->d_acc, p->d_sum, p->d_lin64, p->d_sums64, p->d_tw_seed, p->d_tw_row, p->d_ones,
-                  p->d_dbg, p->d_bigq});
-  if (p->h_in_pin) (void)hipHostFree(p->h_in_pin);
-  if (p->h_out_pin) (void)hipHostFree(p->h_out_pin);
-  for (auto& per_stream : p->fs)
-    for (auto& sl : per_stream) {
-      free_all({sl.d_part, sl.d_peak, sl.d_bin, sl.d_band});
-    }
   if (p->fs_stream) { (void)hipStreamSynchronize(p->fs_stream); (void)hipStreamDestroy(p->fs_stream); }
   for (hipEvent_t e : p->prof_events) (void)hipEventDestroy(e);
   if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -295,7 +282,7 @@ int tdsa_set_window(tdsa_plan p, const float* w_host, int n) {
         const double wv = double(w_host[i]) * double(scale[f]);
         aw[i] = float2{float(wv * ca[i]), float(wv * sa[i])};
       }
-      if (!p->d_chirp_aw[f]) HIPCHK(hipMalloc(&p->d_chirp_aw[f], aw.size() * sizeof(float2)));
+      if (!p->d_chirp_aw[f]) HIPCHK(p->d_chirp_aw[f].alloc(aw.size()));
       HIPCHK(hipMemcpy(p->d_chirp_aw[f], aw.data(), aw.size() * sizeof(float2), hipMemcpyHostToDevice));
     }
   }

@@ -32,20 +32,14 @@ static int frame_stats_begin(tdsa_plan p, int n_frames, hipStream_t s, tdsa_plan
   for (int i = 0; i < tdsa_plan_s::kMaxOverlap - 1; ++i)
     if (s == p->aux[i] && s != p->stream) si = i + 1;
   tdsa_plan_s::FsSlot& sl = p->fs[si][p->fs_count[si]++ % tdsa_plan_s::kFsKeep];
-  if (size_t(n_frames) > sl.cap) {
+  if (size_t(n_frames) > sl.d_peak.cap()) {
     HIPCHK(hipStreamSynchronize(s));                         // whatever last wrote the slot ran on this stream
     if (p->fs_stream) HIPCHK(hipStreamSynchronize(p->fs_stream));
-    void* fb[] = {sl.d_part, sl.d_peak, sl.d_bin, sl.d_band};
-    for (void* b : fb)
-      if (b) HIPCHK(hipFree(b));
-    sl.d_part = nullptr; sl.d_peak = nullptr; sl.d_bin = nullptr; sl.d_band = nullptr;
-    sl.cap = 0;
     const size_t cap = size_t(n_frames) > size_t(p->max_frames) ? size_t(n_frames) : size_t(p->max_frames);
-    HIPCHK(hipMalloc(&sl.d_part, cap * 16 * kStatsRecBytes));   // up to 16 waves per frame
-    HIPCHK(hipMalloc(&sl.d_peak, cap * sizeof(float)));
-    HIPCHK(hipMalloc(&sl.d_bin, cap * sizeof(int)));
-    HIPCHK(hipMalloc(&sl.d_band, cap * sizeof(double)));
-    sl.cap = cap;
+    TRY(sl.d_part.grow(cap * 16 * kStatsRecBytes, nullptr));   // up to 16 waves per frame
+    TRY(sl.d_peak.grow(cap, nullptr));
+    TRY(sl.d_bin.grow(cap, nullptr));
+    TRY(sl.d_band.grow(cap, nullptr));
   }
   sl.n_frames = n_frames;
   sl.state = 0;
@@ -91,8 +85,7 @@ static int check_frames(tdsa_plan p, size_t n_samples, int hop, int n_frames, in
 
 // [chunks][N] carries of the averager's chained scan; work in flight may still read the old ones
 static int grow_carry(tdsa_plan p, size_t need_chunks) {
-  return grow_device(&p->d_carry, &p->carry_chunks, need_chunks, p->d_carry ? p->stream : nullptr,
-                     size_t(p->nfft) * sizeof(double));
+  return p->d_carry.grow(need_chunks * size_t(p->nfft), p->d_carry ? p->stream : nullptr);
 }
 
 namespace tdsa {
@@ -147,10 +140,10 @@ void avg_advance(tdsa_plan p, int n_frames) {
 // the frames' weights, made again only when what they depend on has changed.  ap.wg_chunks is the caller's; path 0: the
 // chunks are the frame kernel's workgroup ranges (fpu frames per unit), path 1: equal ranges of the batch.
 static int avg_chunk_setup(tdsa_plan p, AvgParams& ap, size_t agg_rows, int fpu, int path, hipStream_t s) {
-  if (!p->d_agg) HIPCHK(hipMalloc(&p->d_agg, (agg_rows > 256 ? agg_rows : size_t(256)) * p->nfft * sizeof(float)));
-  if (!p->d_agg_w) HIPCHK(hipMalloc(&p->d_agg_w, size_t(p->max_frames) * sizeof(float)));
-  if (!p->d_chunk_a) HIPCHK(hipMalloc(&p->d_chunk_a, size_t(kAvgMaxWgChunks + 64) * sizeof(double)));
-  if (!p->d_chunk_v) HIPCHK(hipMalloc(&p->d_chunk_v, size_t(kAvgMaxWgChunks + 64) * sizeof(float)));
+  if (!p->d_agg) HIPCHK(p->d_agg.alloc((agg_rows > 256 ? agg_rows : size_t(256)) * p->nfft));
+  if (!p->d_agg_w) HIPCHK(p->d_agg_w.alloc(size_t(p->max_frames)));
+  if (!p->d_chunk_a) HIPCHK(p->d_chunk_a.alloc(size_t(kAvgMaxWgChunks + 64)));
+  if (!p->d_chunk_v) HIPCHK(p->d_chunk_v.alloc(size_t(kAvgMaxWgChunks + 64)));
   ap.chunk_a = p->d_chunk_a;
   ap.chunk_v = p->d_chunk_v;
   ap.agg = p->d_agg;
@@ -173,7 +166,7 @@ static int avg_chunk_setup(tdsa_plan p, AvgParams& ap, size_t agg_rows, int fpu,
 int avg_use_ranges(tdsa_plan p, AvgParams& ap, int n_frames, hipStream_t s) {
   if (p->avg_f64_chunks || n_frames <= 1024 || p->d_carry == nullptr) return TDSA_OK;
   const int ranges = (n_frames + 63) / 64 < 256 ? (n_frames + 63) / 64 : 256;
-  if (size_t(ranges) > p->carry_chunks) return TDSA_OK;
+  if (size_t(ranges) > p->d_carry.cap() / size_t(p->nfft)) return TDSA_OK;
   // a range's aggregate is a float32 sum: kept to the ~160 frames the workgroup-chunk path allows itself; longer
   // ranges (batches of more than 40 960 frames here) take the 64-frame chunks with their float64 aggregates - the
   // reference's TraceAverager is float64 throughout (utils/signal_processing.py:48)
@@ -295,7 +288,7 @@ int process_dev_impl(tdsa_plan p, int in_format, const void* iq_dev, size_t n_sa
   const LaunchGeom g = spectrum_geometry(p->log2n, n_frames,
                                          (overlap && p->n_overlap >= 3) ? (p->num_cu * p->overlap_share + 99) / 100 : p->num_cu);
   if (averaging) {
-    if (!p->d_lin) HIPCHK(hipMalloc(&p->d_lin, size_t(p->max_frames) * p->nfft * sizeof(float)));
+    if (!p->d_lin) HIPCHK(p->d_lin.alloc(size_t(p->max_frames) * p->nfft));
     // Long batches run as a chained scan over chunks of frames (tdsa_trace.hip).  The chunks ARE the frame ranges of the
     // frame kernel's workgroups, which form their chunk's aggregate themselves while the rows pass through their
     // registers - the scan's first pass over the rows disappears (below 4096 points a workgroup's slots take consecutive
@@ -370,8 +363,8 @@ int process_dev_impl(tdsa_plan p, int in_format, const void* iq_dev, size_t n_sa
 // pinned, device-visible bounce buffers of the host entry points (grown on demand; every host call ends with a
 // synchronize, so they are free when the next one starts)
 int ensure_pins(tdsa_plan p, size_t in_bytes, size_t out_bytes) {
-  TRY(grow_pinned(&p->h_in_pin, &p->in_pin_bytes, in_bytes, p->h_in_pin ? p->stream : nullptr));
-  TRY(grow_pinned(&p->h_out_pin, &p->out_pin_bytes, out_bytes, p->h_out_pin ? p->stream : nullptr));
+  TRY(p->h_in_pin.grow(in_bytes, p->h_in_pin ? p->stream : nullptr));
+  TRY(p->h_out_pin.grow(out_bytes, p->h_out_pin ? p->stream : nullptr));
   return TDSA_OK;
 }
 
@@ -445,9 +438,9 @@ static int process_host(tdsa_plan p, int fmt, const void* iq_host, size_t n_samp
   HIPCHK(hipSetDevice(p->device));
   JOIN(p);
   const size_t in_bytes = need * bytes_per_sample(fmt);
-  TRY(grow_device(&p->d_in_stage, &p->in_stage_bytes, in_bytes, p->stream));
+  TRY(p->d_in_stage.grow(in_bytes, p->stream));
   if (out_db_host && !p->d_out_stage)
-    HIPCHK(hipMalloc(&p->d_out_stage, size_t(p->big ? 1 : p->max_frames) * p->nfft * sizeof(float)));
+    HIPCHK(p->d_out_stage.alloc(size_t(p->big ? 1 : p->max_frames) * p->nfft));
   const size_t out_bytes = out_db_host ? size_t(p->big ? 1 : n_frames) * p->nfft * sizeof(float) : 0;
   const bool bounce = in_bytes <= kPinnedBounceMax && out_bytes <= kPinnedBounceMax;
   if (bounce) {
@@ -460,7 +453,7 @@ static int process_host(tdsa_plan p, int fmt, const void* iq_host, size_t n_samp
   if (direct) {
     p->sync_call = true;
     int rc_d = tdsa_process_dev(p, fmt, p->h_in_pin, need, hop, n_frames,
-                                out_db_host ? static_cast<float*>(p->h_out_pin) : nullptr);
+                                out_db_host ? p->h_out_pin.as<float>() : nullptr);
     p->sync_call = false;
     TRY(rc_d);
     JOIN(p);
@@ -523,24 +516,24 @@ int tdsa_process_real2(tdsa_plan p, const float* lr_host, size_t n_samples, int 
   JOIN(p);
   const int n = p->nfft, nb = n / 2 + 1;
   const size_t in_bytes = need * sizeof(float2);
-  TRY(grow_device(&p->d_in_stage, &p->in_stage_bytes, in_bytes, p->stream));
-  if (!p->d_cplx) HIPCHK(hipMalloc(&p->d_cplx, size_t(p->max_frames) * n * sizeof(float2)));
-  if (!p->d_lin1) HIPCHK(hipMalloc(&p->d_lin1, size_t(p->max_frames) * 2 * nb * sizeof(float)));
-  if (!p->d_db1) HIPCHK(hipMalloc(&p->d_db1, size_t(p->max_frames) * 2 * nb * sizeof(float)));
+  TRY(p->d_in_stage.grow(in_bytes, p->stream));
+  if (!p->d_cplx) HIPCHK(p->d_cplx.alloc(size_t(p->max_frames) * n));
+  if (!p->d_lin1) HIPCHK(p->d_lin1.alloc(size_t(p->max_frames) * 2 * nb));
+  if (!p->d_db1) HIPCHK(p->d_db1.alloc(size_t(p->max_frames) * 2 * nb));
   const int n_sig = channel == TDSA_CH_STEREO ? 2 : 1;
-  TRY(grow_device(&p->d_real, &p->real_bytes, in_bytes * n_sig, p->stream));
+  TRY(p->d_real.grow(need * size_t(n_sig), p->stream));
   // one tick of audio is small: samples and dB rows go through pinned, device-visible buffers that the kernels read
   // and write in place (no DMA operation either way); larger batches are copied as before
   const int rows_out = channel == TDSA_CH_STEREO ? 2 * n_frames : n_frames;
   const size_t out_bytes = size_t(rows_out) * nb * sizeof(float);
   const bool direct = in_bytes <= kZeroCopyMax && out_bytes <= kZeroCopyMax;
-  const float2* lr_dev = static_cast<const float2*>(p->d_in_stage);
+  const float2* lr_dev = p->d_in_stage.as<const float2>();
   float* db_dst = p->d_db1;
   if (direct) {
     TRY(ensure_pins(p, in_bytes, out_bytes));
     std::memcpy(p->h_in_pin, lr_host, in_bytes);
-    lr_dev = static_cast<const float2*>(p->h_in_pin);
-    db_dst = static_cast<float*>(p->h_out_pin);
+    lr_dev = p->h_in_pin.as<const float2>();
+    db_dst = p->h_out_pin.as<float>();
   } else {
     HIPCHK(hipMemcpyAsync(p->d_in_stage, lr_host, in_bytes, hipMemcpyHostToDevice, p->stream));
   }
@@ -555,7 +548,7 @@ int tdsa_process_real2(tdsa_plan p, const float* lr_host, size_t n_samples, int 
       const float2* zin = sig == 0 ? za : zb;
       const long long stride = (long long)hop * sizeof(float2);
       if (chirp_sum_chunks(n) > 1 && !p->d_sums64)
-        HIPCHK(hipMalloc(&p->d_sums64, size_t(p->max_frames) * chirp_sum_chunks(n) * 2 * sizeof(double)));
+        HIPCHK(p->d_sums64.alloc(size_t(p->max_frames) * chirp_sum_chunks(n) * 2));
       HIPCHK(launch_chirp_sums(zin, 1, 0u, stride, n, n_frames, 0, p->d_sums, nullptr, 1.0f, p->stream, p->d_sums64));
       TRY(chirp_transform(p, zin, TDSA_IN_C64, stride, n_frames, p->d_sums, 0u, 0.0f));
       HIPCHK(launch_chirp_post_real(p->d_u0, n, p->m_fft, n_frames, n_sig, sig, m.power_scale, p->d_lin1, p->stream));

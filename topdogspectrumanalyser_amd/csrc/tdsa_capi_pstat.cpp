@@ -13,9 +13,9 @@ static_assert(TDSA_PSTAT_MAX_STREAMS == kPstatMaxStreams && TDSA_PSTAT_BINS == k
 
 // ---- power statistics (tdsa_pstat.hip) ---------------------------------------------------------------------------
 struct tdsa_pstat_s : IqAccum {
-  PstatRecord* d_rec = nullptr;    // the state: [C] records, [C][256] mantissa sums, [C][2048] counts
-  unsigned long long* d_msum = nullptr;
-  unsigned long long* d_hist = nullptr;
+  Dev<PstatRecord> d_rec;          // the state: [C] records, [C][256] mantissa sums, [C][2048] counts
+  Dev<unsigned long long> d_msum;
+  Dev<unsigned long long> d_hist;
   std::vector<PstatRecord> fresh;  // [C] what a reset writes: zeros, min_bits all ones
   int exp_lo = -40;
   float gate = 0.0f;
@@ -74,9 +74,9 @@ int tdsa_pstat_create(int device_id, int streams, size_t max_host_samples, tdsa_
   h->fresh.assign(size_t(streams), zero);
   hipError_t e = h->open(true);
   if (e == hipSuccess) e = h->in.alloc(max_host_samples * 8);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_rec), size_t(streams) * sizeof(PstatRecord));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_msum), size_t(streams) * kPstatExponents * 8);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_hist), size_t(streams) * kPstatBins * 8);
+  if (e == hipSuccess) e = h->d_rec.alloc(size_t(streams));
+  if (e == hipSuccess) e = h->d_msum.alloc(size_t(streams) * kPstatExponents);
+  if (e == hipSuccess) e = h->d_hist.alloc(size_t(streams) * kPstatBins);
   if (e != hipSuccess) {
     (void)tdsa_pstat_destroy(h);
     return fail(TDSA_ERR_HIP, "pstat create: %s", hipGetErrorString(e));
@@ -93,9 +93,6 @@ int tdsa_pstat_create(int device_id, int streams, size_t max_host_samples, tdsa_
 int tdsa_pstat_destroy(tdsa_pstat h) {
   if (!h) return TDSA_OK;
   h->drain();
-  h->in.release();
-  free_all({h->d_rec, h->d_msum, h->d_hist});
-  h->close();
   delete h;
   return TDSA_OK;
 }

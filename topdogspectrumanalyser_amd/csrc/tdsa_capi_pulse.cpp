@@ -19,11 +19,11 @@ static_assert(TDSA_PULSE_MAX_STREAMS == kPulseMaxStreams && TDSA_PULSE_MAX_RECOR
 // ---- pulse analysis (tdsa_pulse.hip) -----------------------------------------------------------------------------
 struct tdsa_pulse_s : IqAccum {
   int capacity = 1;
-  PulseTileInfo* d_tiles = nullptr;   // the tile summaries of one launch ...
-  PulseSummary* d_sum = nullptr;   // ... and the state: [C] summaries, [C] open pulses, [C][2] last samples, [C][capacity] records
-  PulseRecord* d_open = nullptr;
-  float2* d_prev = nullptr;
-  PulseRecord* d_rec = nullptr;
+  Dev<PulseTileInfo> d_tiles;         // the tile summaries of one launch ...
+  Dev<PulseSummary> d_sum;         // ... and the state: [C] summaries, [C] open pulses, [C][2] last samples, [C][capacity] records
+  Dev<PulseRecord> d_open;
+  Dev<float2> d_prev;
+  Dev<PulseRecord> d_rec;
   float on_level = 1.0f, off_level = 1.0f;
   long long min_width = 1;
   long long seen = 0;              // samples per stream since the last reset: the index of the next call's first
@@ -107,11 +107,11 @@ int tdsa_pulse_create(int device_id, int streams, int capacity, size_t max_host_
   h->max_host = max_host_samples;
   hipError_t e = h->open(true);
   if (e == hipSuccess) e = h->in.alloc(max_host_samples * 8);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_tiles), size_t(kPulseMaxLaunchTiles) * sizeof(PulseTileInfo));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_sum), size_t(streams) * sizeof(PulseSummary));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_open), size_t(streams) * sizeof(PulseRecord));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_prev), size_t(streams) * 2 * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_rec), size_t(streams) * size_t(capacity) * sizeof(PulseRecord));
+  if (e == hipSuccess) e = h->d_tiles.alloc(size_t(kPulseMaxLaunchTiles));
+  if (e == hipSuccess) e = h->d_sum.alloc(size_t(streams));
+  if (e == hipSuccess) e = h->d_open.alloc(size_t(streams));
+  if (e == hipSuccess) e = h->d_prev.alloc(size_t(streams) * 2);
+  if (e == hipSuccess) e = h->d_rec.alloc(size_t(streams) * size_t(capacity));
   if (e != hipSuccess) {
     (void)tdsa_pulse_destroy(h);
     return fail(TDSA_ERR_HIP, "pulse create: %s", hipGetErrorString(e));
@@ -128,9 +128,6 @@ int tdsa_pulse_create(int device_id, int streams, int capacity, size_t max_host_
 int tdsa_pulse_destroy(tdsa_pulse h) {
   if (!h) return TDSA_OK;
   h->drain();
-  h->in.release();
-  free_all({h->d_tiles, h->d_sum, h->d_open, h->d_prev, h->d_rec});
-  h->close();
   delete h;
   return TDSA_OK;
 }

@@ -18,15 +18,13 @@ struct tdsa_sweep_s : Lane {           // its stream: _read, _get_steps, the tim
   std::vector<unsigned char> valid;   // per step: 1 = present
   bool tab_dirty = true;
   int n_present = 0;
-  float* d_T = nullptr;               // [S][K]
-  size_t T_cap = 0;
-  double* d_grid = nullptr;           // [n_grid]
-  double* d_out = nullptr;            // [n_grid] of a _read without a device pointer
-  double2* d_tab = nullptr;           // [S] (frequency of the first kept bin, centre) of the steps present
-  int* d_step_of = nullptr;           // [S] their step numbers
-  void* h_tab = nullptr;              // pinned: S double2 then S int
-  float* d_rows = nullptr;            // _run_dev: dB rows of one chunk of steps
-  size_t rows_cap = 0;                // floats
+  Dev<float> d_T;                     // [S][K]
+  Dev<double> d_grid;                 // [n_grid]
+  Dev<double> d_out;                  // [n_grid] of a _read without a device pointer
+  Dev<double2> d_tab;                 // [S] (frequency of the first kept bin, centre) of the steps present
+  Dev<int> d_step_of;                 // [S] their step numbers
+  Pinned<char> h_tab;                 // pinned: S double2 then S int
+  Dev<float> d_rows;                  // _run_dev: dB rows of one chunk of steps
   size_t chunk_bytes = kSweepChunkBytes;
 };
 
@@ -79,7 +77,7 @@ int sweep_detect(tdsa_sweep w, hipStream_t s, int first_step, int n_steps, const
 int sweep_upload_table(tdsa_sweep w) {
   if (!w->tab_dirty) return TDSA_OK;
   HIPCHK(hipEventSynchronize(w->ev_tab));
-  double2* tab = static_cast<double2*>(w->h_tab);
+  double2* tab = w->h_tab.as<double2>();
   int* step_of = reinterpret_cast<int*>(tab + w->S);
   int n = 0;
   for (int s = 0; s < w->S; ++s) {
@@ -116,11 +114,11 @@ int tdsa_sweep_create(int device_id, int nfft, int n_steps, int n_grid, tdsa_swe
   const size_t S = size_t(n_steps);
   hipError_t e = w->open(true);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev_tab, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc(&w->d_grid, size_t(n_grid) * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&w->d_out, size_t(n_grid) * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&w->d_tab, S * sizeof(double2));
-  if (e == hipSuccess) e = hipMalloc(&w->d_step_of, S * sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc(&w->h_tab, S * (sizeof(double2) + sizeof(int)), hipHostMallocDefault);
+  if (e == hipSuccess) e = w->d_grid.alloc(size_t(n_grid));
+  if (e == hipSuccess) e = w->d_out.alloc(size_t(n_grid));
+  if (e == hipSuccess) e = w->d_tab.alloc(S);
+  if (e == hipSuccess) e = w->d_step_of.alloc(S);
+  if (e == hipSuccess) e = w->h_tab.alloc(S * (sizeof(double2) + sizeof(int)), hipHostMallocDefault);
   if (e != hipSuccess) {
     (void)tdsa_sweep_destroy(w);
     return fail(TDSA_ERR_HIP, "sweep create: %s", hipGetErrorString(e));
@@ -132,10 +130,7 @@ int tdsa_sweep_create(int device_id, int nfft, int n_steps, int n_grid, tdsa_swe
 int tdsa_sweep_destroy(tdsa_sweep w) {
   if (!w) return TDSA_OK;
   w->drain();
-  free_all({w->d_T, w->d_grid, w->d_out, w->d_tab, w->d_step_of, w->d_rows});
-  if (w->h_tab) (void)hipHostFree(w->h_tab);
   if (w->ev_tab) (void)hipEventDestroy(w->ev_tab);
-  w->close();
   delete w;
   return TDSA_OK;
 }
@@ -161,7 +156,7 @@ int tdsa_sweep_set_geometry(tdsa_sweep w, const double* centres_hz, double bin_h
   HIPCHK(hipSetDevice(w->device));
   HIPCHK(hipEventSynchronize(w->ev_done));   // nothing in flight reads the old T or grid
   HIPCHK(hipStreamSynchronize(w->stream));
-  TRY(grow_device(&w->d_T, &w->T_cap, size_t(w->S) * size_t(k1 - k0), nullptr, sizeof(float)));
+  TRY(w->d_T.grow(size_t(w->S) * size_t(k1 - k0), nullptr));
   HIPCHK(hipMemset(w->d_T, 0, size_t(w->S) * size_t(k1 - k0) * sizeof(float)));   // steps not yet present read as 0
   HIPCHK(hipMemcpy(w->d_grid, grid_hz_host, size_t(w->n_grid) * sizeof(double), hipMemcpyHostToDevice));
   w->centres.assign(centres_hz, centres_hz + w->S);
@@ -214,7 +209,7 @@ int tdsa_sweep_run_dev(tdsa_sweep w, tdsa_plan p, int in_format, const void* iq_
   if (per_chunk < 1) per_chunk = 1;
   if (per_chunk > size_t(n_steps)) per_chunk = size_t(n_steps);
   JOIN(p);
-  TRY(grow_device(&w->d_rows, &w->rows_cap, per_chunk * step_floats, p->stream, sizeof(float)));
+  TRY(w->d_rows.grow(per_chunk * step_floats, p->stream));
   for (int done = 0; done < n_steps; done += int(per_chunk)) {
     const int n = n_steps - done < int(per_chunk) ? n_steps - done : int(per_chunk);
     TRY(tdsa_process_dev_batch(p, in_format, static_cast<const unsigned char*>(iq_dev) + size_t(done) * step_stride_bytes,

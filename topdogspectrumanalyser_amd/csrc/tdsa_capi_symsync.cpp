@@ -40,7 +40,7 @@ struct tdsa_symsync_s : SegAnalyser {
     a.sym = static_cast<float2*>(sym);
     a.raw = static_cast<float2*>(raw);
     a.out_stride = (long long)out_stride;
-    a.rec = static_cast<SymRecord*>(d_rec);
+    a.rec = d_rec.as<SymRecord>();
     return launch_symsync(a, s);
   }
 };

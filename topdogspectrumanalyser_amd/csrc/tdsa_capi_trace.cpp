@@ -5,16 +5,16 @@ using namespace tdsa;
 
 struct tdsa_trace_s : Lane {
   int n = 0;
-  float* d_in = nullptr;
-  float* d_live = nullptr;
-  float* d_hold_max = nullptr;
-  float* d_hold_min = nullptr;
-  float* d_tare_base = nullptr;
-  float* d_tare_acc = nullptr;
-  double* d_avg = nullptr;
-  double* d_avg_in = nullptr;
-  float* h_pin = nullptr;       // pinned, device-visible: [4][n] row in, live / max / min out (one GUI tick, zero-copy)
-  double* h_pin_avg = nullptr;  // pinned: [2][n] linear row in, averager state out (tdsa_trace_avg_process)
+  Dev<float> d_in;
+  Dev<float> d_live;
+  Dev<float> d_hold_max;
+  Dev<float> d_hold_min;
+  Dev<float> d_tare_base;
+  Dev<float> d_tare_acc;
+  Dev<double> d_avg;
+  Dev<double> d_avg_in;
+  Pinned<float> h_pin;          // pinned, device-visible: [4][n] row in, live / max / min out (one GUI tick, zero-copy)
+  Pinned<double> h_pin_avg;     // pinned: [2][n] linear row in, averager state out (tdsa_trace_avg_process)
   long long held_max = 0, held_min = 0;
   bool tare_active = false;
   int tare_count = 0;
@@ -35,13 +35,11 @@ int tdsa_trace_create(int device_id, int n, tdsa_trace* out) {
   if (!t) return fail(TDSA_ERR_NOMEM, "host allocation failed");
   t->device = device_id;
   t->n = n;
-  const size_t nb = size_t(n) * sizeof(float);
   hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-  float** fbufs[] = {&t->d_in, &t->d_live, &t->d_hold_max, &t->d_hold_min, &t->d_tare_base, &t->d_tare_acc};
-  for (float** b : fbufs)
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(b), nb);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->d_avg), size_t(n) * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->d_avg_in), size_t(n) * sizeof(double));
+  for (Dev<float>* b : {&t->d_in, &t->d_live, &t->d_hold_max, &t->d_hold_min, &t->d_tare_base, &t->d_tare_acc})
+    if (e == hipSuccess) e = b->alloc(size_t(n));
+  if (e == hipSuccess) e = t->d_avg.alloc(size_t(n));
+  if (e == hipSuccess) e = t->d_avg_in.alloc(size_t(n));
   if (e != hipSuccess) {                     // a failure half way leaves nothing behind
     (void)tdsa_trace_destroy(t);
     return fail(TDSA_ERR_HIP, "trace create: %s", hipGetErrorString(e));
@@ -53,10 +51,6 @@ int tdsa_trace_create(int device_id, int n, tdsa_trace* out) {
 int tdsa_trace_destroy(tdsa_trace t) {
   if (!t) return TDSA_OK;
   t->drain();
-  free_all({t->d_in, t->d_live, t->d_hold_max, t->d_hold_min, t->d_tare_base, t->d_tare_acc, t->d_avg, t->d_avg_in});
-  if (t->h_pin) (void)hipHostFree(t->h_pin);
-  if (t->h_pin_avg) (void)hipHostFree(t->h_pin_avg);
-  t->close();
   delete t;
   return TDSA_OK;
 }
@@ -83,7 +77,7 @@ int tdsa_trace_update(tdsa_trace t, const float* db_in_host, int n, float cal_of
   const size_t nb = size_t(n) * sizeof(float);
   // one displayed frame: the kernel reads the row from and writes its results to pinned, device-visible memory of the
   // trace object - no DMA operation on the way in or out (each costs ~10 us from / to pageable memory)
-  if (!t->h_pin) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&t->h_pin), 4 * nb, hipHostMallocPortable | hipHostMallocMapped));
+  if (!t->h_pin) HIPCHK(t->h_pin.alloc(4 * size_t(n), hipHostMallocPortable | hipHostMallocMapped));
   float* const h_in = t->h_pin;
   float* const h_live = t->h_pin + n;
   float* const h_max = t->h_pin + 2 * size_t(n);
@@ -171,7 +165,7 @@ int tdsa_trace_avg_process(tdsa_trace t, const double* linear_in_host, int n, do
   // one row per call: in through pinned, device-visible memory the kernel reads in place, the state back through a
   // DMA copy into pinned memory (the float64 state itself stays on the device)
   if (!t->h_pin_avg)
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&t->h_pin_avg), 2 * nb, hipHostMallocPortable | hipHostMallocMapped));
+    HIPCHK(t->h_pin_avg.alloc(2 * size_t(n), hipHostMallocPortable | hipHostMallocMapped));
   double* const h_in = t->h_pin_avg;
   double* const h_out = t->h_pin_avg + n;
   std::memcpy(h_in, linear_in_host, nb);

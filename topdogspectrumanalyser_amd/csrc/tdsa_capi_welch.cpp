@@ -5,7 +5,7 @@
 using namespace tdsa;
 
 // the staging buffer, grown on demand (no stream is drained ahead of the free)
-static int welch_stage(tdsa_plan p, size_t bytes) { return grow_device(&p->d_welch, &p->welch_bytes, bytes, nullptr); }
+static int welch_stage(tdsa_plan p, size_t bytes) { return p->d_welch.grow(bytes, nullptr); }
 
 extern "C" {
 
@@ -139,7 +139,7 @@ static int welch_combine_impl(tdsa_plan p, const void* parts_host, size_t part_s
   if (parts_host) {
     // one strided copy: the parts may sit part_stride_bytes apart in the caller's (pinned, shared) slab
     HIPCHK(hipMemcpy2DAsync(p->d_welch, nb, parts_host, part_stride_bytes, nb, size_t(n_parts), hipMemcpyHostToDevice, p->stream));
-    for (int r = 0; r < n_parts; ++r) part[r] = static_cast<const unsigned char*>(p->d_welch) + nb * size_t(r);
+    for (int r = 0; r < n_parts; ++r) part[r] = p->d_welch.as<const unsigned char>() + nb * size_t(r);
   } else {
     for (int r = 0; r < n_parts; ++r) {
       if (cnt[r] != 0 && !parts_dev[r]) return fail(TDSA_ERR_ARG, "parts_dev[%d] is null", r);
@@ -147,7 +147,7 @@ static int welch_combine_impl(tdsa_plan p, const void* parts_host, size_t part_s
     }
   }
   float* out_dev = out_db_dev ? out_db_dev
-                              : (out_db_host ? reinterpret_cast<float*>(static_cast<unsigned char*>(p->d_welch) + staged) : nullptr);
+                              : (out_db_host ? reinterpret_cast<float*>(p->d_welch + staged) : nullptr);
   const bool hmax = (m.hold_flags & TDSA_HOLD_MAX) != 0, hmin = (m.hold_flags & TDSA_HOLD_MIN) != 0;
   const float pscale = (p->big && m.db_mode == TDSA_DB_POW) ? m.power_scale : 1.0f;
   HIPCHK(launch_welch_combine(part, cnt, n_parts, as_f32, (long long)n, p->big ? p->d_sum : nullptr,

@@ -14,13 +14,11 @@ struct tdsa_zspan_s : Lane {           // its stream: host pushes, views, the ti
   int detector = TDSA_ZS_DET_REAL;
   float log_floor = 0.f, offset_db = 0.f;
   long long total = 0;                // samples pushed since the last reset
-  float* d_ring = nullptr;            // [cap]; absolute sample t lives at t % cap
-  void* h_in = nullptr;               // pinned staging of one host chunk (up to 8 bytes per sample) ...
-  void* d_in = nullptr;               // ... and where it lands
-  unsigned char* d_res = nullptr;     // ZsCtrl, kZsMaxBlocks ZsPart, then the trace of a view without a device pointer
-  size_t res_bytes = 0;
-  void* h_res = nullptr;              // pinned: what one view reads back
-  size_t h_res_bytes = 0;
+  Dev<float> d_ring;                  // [cap]; absolute sample t lives at t % cap
+  Pinned<char> h_in;                  // pinned staging of one host chunk (up to 8 bytes per sample) ...
+  Dev<char> d_in;                     // ... and where it lands
+  Dev<unsigned char> d_res;           // ZsCtrl, kZsMaxBlocks ZsPart, then the trace of a view without a device pointer
+  Pinned<char> h_res;                 // pinned: what one view reads back
 };
 
 namespace {
@@ -89,9 +87,9 @@ int tdsa_zspan_create(int device_id, size_t capacity, size_t max_host_samples, t
   z->max_host = max_host_samples;
   hipError_t e = z->open(true);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&z->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&z->d_ring), capacity * sizeof(float));
-  if (e == hipSuccess) e = hipHostMalloc(&z->h_in, max_host_samples * 8, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&z->d_in, max_host_samples * 8);
+  if (e == hipSuccess) e = z->d_ring.alloc(capacity);
+  if (e == hipSuccess) e = z->h_in.alloc(max_host_samples * 8, hipHostMallocDefault);
+  if (e == hipSuccess) e = z->d_in.alloc(max_host_samples * 8);
   if (e != hipSuccess) {
     (void)tdsa_zspan_destroy(z);
     return fail(TDSA_ERR_HIP, "zero span create: %s", hipGetErrorString(e));
@@ -103,11 +101,7 @@ int tdsa_zspan_create(int device_id, size_t capacity, size_t max_host_samples, t
 int tdsa_zspan_destroy(tdsa_zspan z) {
   if (!z) return TDSA_OK;
   z->drain();
-  free_all({z->d_ring, z->d_in, z->d_res});
-  if (z->h_in) (void)hipHostFree(z->h_in);
-  if (z->h_res) (void)hipHostFree(z->h_res);
   if (z->ev_in) (void)hipEventDestroy(z->ev_in);
-  z->close();
   delete z;
   return TDSA_OK;
 }
@@ -196,8 +190,8 @@ int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int 
   }
   const size_t out_floats = P == 0 ? size_t(length) : size_t(P) * (col_detector == TDSA_ZS_COL_MINMAX ? 2 : 1);
   TRY(z->own_stream());
-  TRY(grow_device(&z->d_res, &z->res_bytes, kZsOutOffset + (out_dev ? 0 : out_floats) * sizeof(float), z->stream));
-  ZsCtrl* ctrl = reinterpret_cast<ZsCtrl*>(z->d_res);
+  TRY(z->d_res.grow(kZsOutOffset + (out_dev ? 0 : out_floats) * sizeof(float), z->stream));
+  ZsCtrl* ctrl = z->d_res.as<ZsCtrl>();
   float* d_out = out_dev ? out_dev : reinterpret_cast<float*>(z->d_res + kZsOutOffset);
   HIPCHK(hipMemsetAsync(z->d_res, 0, kZsCtrlZeroed, z->stream));
   if (n_pairs > 0) {
@@ -232,12 +226,12 @@ int tdsa_zspan_view(tdsa_zspan z, int mode, double level, size_t n_display, int 
   const size_t head_bytes = sizeof(ZsCtrl) + size_t(v.blocks) * sizeof(ZsPart);
   const bool bounce = out_host && !out_dev && out_floats * sizeof(float) <= kZsBounceMax;
   const size_t back = bounce ? kZsOutOffset + out_floats * sizeof(float) : head_bytes;
-  TRY(grow_pinned(&z->h_res, &z->h_res_bytes, back, nullptr));
+  TRY(z->h_res.grow(back, nullptr));
   HIPCHK(hipMemcpyAsync(z->h_res, z->d_res, back, hipMemcpyDeviceToHost, z->stream));
   if (out_host && !bounce)
     HIPCHK(hipMemcpyAsync(out_host, d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, z->stream));
   HIPCHK(hipStreamSynchronize(z->stream));
-  const unsigned char* h = static_cast<const unsigned char*>(z->h_res);
+  const unsigned char* h = z->h_res.as<const unsigned char>();
   if (bounce) std::memcpy(out_host, h + kZsOutOffset, out_floats * sizeof(float));
   ZsCtrl c;
   std::memcpy(&c, h, sizeof(c));
