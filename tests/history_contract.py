@@ -5,6 +5,18 @@ dB rows, plus the screen reduction (`columns`), which the reference does not hav
 
 Rows are float32 and hold no NaN: np.clip passes a NaN on into an `astype(int)` whose result is undefined, so with a NaN
 in a row z is NaN and the colour is unspecified - outside the contract.  +-inf are inside it (z = 0 / 8).
+
+A NaN dB row is nevertheless what a non-finite capture produces, so what it may touch is bounded.  A NaN at bin j of a
+pushed row (or of the max or min trace that came with it) leaves unspecified
+  - that row's z, colour and colour index at j - with `columns`, the value, colour, index and bin of the cell that
+    holds j (one NaN among a cell's bins makes every comparison of its maximum search false);
+  - the hold row at j (the hold cell holding j and its bin), from a NaN in the row or in the max trace;
+  - the min row at j (its cell and bin) while the min trace with the NaN is the newest;
+  - live_peak, and the peak_norm that follows from it, while that row is the newest;
+  - hold_peak until reset_hold.
+Everything else - the other bins and cells of that row, every other row, the keys of the other slots (so live_peak
+again after the next NaN-free push), the rest of the hold and min rows, and hold_peak after reset_hold and a NaN-free
+push - has the bits of the same run with the NaN replaced by -inf.
 """
 import numpy as np
 

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import history_cases as cases
 import history_contract as hc
 from topdogspectrumanalyser_amd import RibbonView, SurfaceView, ThreeDView, TraceHistory, _native as nat, history3d
 
@@ -297,3 +298,192 @@ def test_without_a_gpu_the_handles_report_an_error():
         with pytest.raises(nat.TdsaError):
             v.update_widget_data(np.zeros(8, np.float32), None, np.linspace(1e6, 2e6, 8))
         assert getattr(v, "z", None) is None and getattr(v, "verts", None) is None
+
+
+# ---------------------------------------------------------------------------------------------------- the shape cases
+# tests/history_cases.py builds the rows of tests/test_gpu_history_shapes.py; what those rows claim is proved here.
+def test_push_geometry_is_the_launcher_rule():
+    assert cases.header_const("kHistPushMaxWgs") == 2048 and cases.header_const("kHistMaxCells") == history3d.MAX_CELLS
+    src = open(os.path.join(ROOT, "topdogspectrumanalyser_amd", "csrc", "tdsa_history.hip")).read()
+    launcher = src[src.index("hipError_t launch_hist_push"):src.index("hipError_t launch_hist_reduce")]
+    assert "kHistPushMaxWgs / gx" in launcher and "2048" not in launcher
+    assert cases.push_geometry(1024, 300) == (1, 300, 1, 1) and cases.push_geometry(1000, 75) == (1, 75, 1, 1)
+    want = {(8192, 257): (8, 129, 2, 1), (4099, 250): (17, 84, 3, 1), (1001, 2051): (4, 411, 5, 1), (1024, 2049): (1, 1025, 2, 1)}
+    for shape in cases.CHUNK_SHAPES:
+        assert cases.push_geometry(*shape) == want[shape], shape
+    assert cases.push_geometry(1024, 2049, aligned=False) == (4, 410, 5, 4)    # the same rows behind an odd pointer
+
+
+@pytest.mark.parametrize("depth", cases.CHUNK_DEPTHS)
+@pytest.mark.parametrize("n,n_rows", cases.CHUNK_SHAPES)
+def test_chunk_cases_run_the_chunk_paths(n, n_rows, depth):
+    case = cases.chunk_case(n, n_rows, depth)
+    gx, gy, rpw, last = case["geometry"]
+    skip, batch = case["skip"], case["batch"]
+    assert batch.shape == (n_rows, n) and batch.nbytes <= 9 << 20 and not np.isnan(batch).any()
+    assert rpw >= 2 and 1 <= last < rpw and (gy - 1) * rpw + last == n_rows            # a short last chunk
+    assert 0 < skip == n_rows - depth
+    # one host row first: slot (1 + k) % depth, so row k of the batch wraps to slot 0 where (1 + k) % depth == 0
+    wraps = [k for k in range(skip + 1, n_rows) if (1 + k) % depth == 0]
+    assert wraps, (skip, depth)
+    if depth == 30:                                            # (depth 7: see the next test)
+        assert skip % rpw != 0                                 # the first line of the ring is not the first row of a chunk
+        assert any(k % rpw != 0 for k in wraps)                # and the ring wraps inside a chunk
+    everything = np.concatenate([case["first"][None], batch])
+    top = np.argmax(everything, axis=0) - 1                    # row of the batch that holds each column's maximum
+    for name, cols in case["classes"].items():
+        assert len(cols) >= 200
+        for c in cols:
+            k = case["planted"][int(c)]
+            col = everything[:, c]
+            assert top[c] == k and (np.delete(col, k + 1) < col[k + 1]).all(), (name, c)     # the maximum, and alone
+            assert cases.CEILING < col[k + 1] < -10.0                                          # inside the height scale
+            if name == "skipped":
+                assert k < skip
+                continue
+            assert k >= skip
+            second = int(np.argsort(col)[-2]) - 1
+            if name == "chunk_end":
+                assert k % rpw == rpw - 1 and second == k + 1
+            else:
+                assert k % rpw == 0 and second == k - 1 and second >= skip
+    free = np.setdiff1d(np.arange(n), np.concatenate(list(case["classes"].values())))
+    assert (batch[:, free] == 40.0).any() and np.isposinf(batch[:, free]).any() and np.isneginf(batch[:, free]).any()
+
+
+def test_chunk_depth_7_puts_the_first_line_on_a_chunk_seam_or_inside_one():
+    """With a depth of 7 the first stored row of three batches is the first row of a chunk, of the fourth it is not."""
+    inside = {shape: (shape[1] - 7) % cases.push_geometry(*shape)[2] != 0 for shape in cases.CHUNK_SHAPES}
+    assert inside == {(8192, 257): False, (4099, 250): False, (1001, 2051): True, (1024, 2049): False}
+
+
+def test_one_bin_and_misaligned_cases_take_one_bin_lanes():
+    for n in cases.ONE_BIN_N:
+        P = cases.one_bin_columns(n)
+        assert cases.lane_width(n) == 1 and 1 <= P <= n and P % 4 != 0
+    assert max(cases.ONE_BIN_N) > 4 * cases.BLOCK and 65 in cases.ONE_BIN_N and 257 in cases.ONE_BIN_N
+    for n in cases.MISALIGNED_N:
+        assert n % 4 == 0
+        rows = np.arange(3 * n, dtype=np.float32).reshape(3, n)
+        for off in cases.MISALIGNED_OFFSETS:
+            buf, at = cases.misaligned_buffer(rows, off)
+            assert at % 16 == off and _same(buf[at // 4:at // 4 + 3 * n].reshape(3, n), rows)
+            assert np.isposinf(buf[:at // 4]).all() and np.isposinf(buf[at // 4 + 3 * n:]).all()
+            assert at // 4 >= 4 and buf.size - (at // 4 + 3 * n) >= 4
+
+
+@pytest.mark.parametrize("n", cases.NEGATIVE_N)
+def test_negative_rows_are_what_they_claim(n):
+    V = cases.lane_width(n)
+    named = cases.negative_rows(n)
+    ats = {name: at for name, _, at, _ in named}
+    assert ats["bin 0"] == 0 and ats["last bin"] == n - 1 and ats["last lane of a wave"] == 64 * V - 1
+    assert ats["first bin of the second workgroup"] == 256 * V == (1024 if V == 4 else 256)
+    for name, row, at, negative in named:
+        assert row.dtype == np.float32 and row.shape == (n,) and not np.isnan(row).any()
+        assert int(np.argmax(row)) == at == cases.key_argmax(row), name
+        if negative:
+            assert not (row >= 0).any(), name
+            if np.isfinite(row[at]):
+                assert (np.delete(row, at) < row[at]).sum() >= n - 2, name           # unique, or one equal maximum
+        else:
+            assert row[at] == 0 and (row == 0).sum() == 12 and (row[row != 0] < 0).all(), name
+            zeros = row[row == 0]
+            assert np.signbit(zeros).any() and not np.signbit(zeros).all()
+            assert np.signbit(row[at]) == (name == "-0 before +0")
+    row = dict((name, r) for name, r, _, _ in named)["equal maxima in two workgroups"]
+    first, second = np.flatnonzero(row == row.max())
+    assert first // (256 * V) == 0 and second // (256 * V) >= 1
+    z = hc.heights(np.concatenate([r for _, r, _, neg in named if neg and np.isfinite(r).all()]), *cases.NEGATIVE_AMPLITUDE)
+    assert (z > 0).all() and (z < 8).all()                                           # nothing clipped
+
+
+def test_hist_key_restated_orders_as_argmax():
+    rng = np.random.default_rng(0)
+    for _ in range(2000):
+        row = cases.KEY_SPECIALS[rng.integers(0, cases.KEY_SPECIALS.size, 16)]
+        assert cases.key_argmax(row) == int(np.argmax(row)), row
+    keys = [cases.hist_key(v, 5) for v in cases.KEY_SPECIALS if not (v == 0 and np.signbit(v))]
+    assert keys == sorted(keys) and len(set(keys)) == len(keys) and keys[0] > 0        # 0 is the untouched slot
+    assert cases.hist_key(np.float32(-0.0), 5) == cases.hist_key(np.float32(0.0), 5)
+    assert cases.hist_key(np.float32(-1.0), 4) > cases.hist_key(np.float32(-1.0), 5) > cases.hist_key(np.float32(-1.5), 0)
+
+
+@pytest.mark.parametrize("n,columns", [(n, c) for n, by in cases.WIDTH_CASES.items() for c in by])
+def test_width_cases_sit_on_the_group_thresholds(n, columns):
+    G = cases.WIDTH_CASES[n][columns]
+    cell = n // columns
+    assert G == (64 if cell >= 32 else 16 if cell >= 8 else 4) == cases.reduce_group(n, columns)
+    cells = hc.cells(n, columns)
+    widths = {b - a for a, b in cells}
+    assert widths == ({cell, cell + 1} if n % columns else {cell})                   # both widths where there are two
+    rows, mn, plateaus, dead = cases.width_rows(n, columns)
+    assert rows.shape == (cases.WIDTH_ROWS, n) and not np.isnan(rows).any() and cases.WIDTH_ROWS > cases.WIDTH_DEPTH
+    assert _same(mn, rows.min(axis=0))
+    lo, hi = cells[dead[1]]
+    assert np.isneginf(rows[dead[0], lo:hi]).all() and cases.WIDTH_ROWS - 1 - dead[0] < cases.WIDTH_DEPTH
+    if max(widths) >= 3:
+        assert len(plateaus) >= cases.WIDTH_ROWS // 2
+    for r, c, first, end in plateaus:
+        lo, hi = cells[c]
+        seg = rows[r, lo:hi]
+        assert lo < first < hi and end > first + 1
+        assert int(np.argmax(seg)) == first - lo and (seg[:first - lo] < rows[r, first]).all()
+        assert (rows[r, first:min(end, hi)] == rows[r, first]).all()
+        lanes = [(j - lo) % G for j in range(first, min(end, hi))]
+        assert lanes[0] != 0 and len(set(lanes)) >= 2              # lane 0 holds a lower value, several lanes tie
+        if hi - lo > G:
+            assert min(lanes[1:]) < lanes[0]                       # a later bin of the plateau in a lower lane
+        if end > hi and c + 1 < columns:
+            assert int(np.argmax(rows[r, hi:cells[c + 1][1]])) == 0
+    if n == 1000 and columns in (32, 126):
+        assert any(cells[c][1] - cells[c][0] > G for _, c, _, _ in plateaus)
+
+
+def test_arithmetic_edge_rows_hold_their_edges():
+    row = cases.integer_edge_row(54)
+    z = hc.heights(row, *cases.EXACT_AMPLITUDE)
+    normal = (row == 0) | (np.abs(row) > 1e-30)
+    assert _same(z[normal], np.clip(row, np.float32(0), np.float32(8))[normal]) and (z[~normal] == 0).all()
+    for k in range(9):
+        for v in (k, k + 0.5):
+            below, above = np.nextafter(np.float32(v), np.float32(-9)), np.nextafter(np.float32(v), np.float32(9))
+            assert (row == np.float32(v)).any() and (row == below).any() and (row == above).any()
+    assert set(hc.line_index(z)) == set(range(9))
+    assert _same(cases.integer_edge_row(56)[:54], row)
+    pairs = cases.sextant_pairs()
+    assert sorted(pairs) == [(0, 1), (1, 1), (14, 1), (14, 2), (29, 1), (29, 2), (29, 3)]
+    for (r, s), (z_lo, z_hi) in pairs.items():
+        assert z_lo.dtype == np.float32 and np.nextafter(z_lo, np.float32(9)) == z_hi and 0 < z_lo < 8
+        assert cases.ribbon_sextant(r, z_lo) == s and cases.ribbon_sextant(r, z_hi) == s - 1
+        _, lo_col = hc.ribbon_row(r, [z_lo], [0.0])                # the contract's colours: the one that is 0 changes
+        _, hi_col = hc.ribbon_row(r, [z_hi], [0.0])
+        zero = {0: 2, 1: 2, 2: 0, 3: 0}
+        assert lo_col[0, zero[s]] == 0 and hi_col[0, zero[s - 1]] == 0
+        val = np.float32(hc.ribbon_row_consts(r)[3])
+        full = {0: 0, 1: 1, 2: 1, 3: 2}
+        assert lo_col[0, full[s]] == val and hi_col[0, full[s - 1]] == val
+    assert [float(v) for v in pairs[(29, 1)]] == [float(np.float32(5.979798)), float(np.float32(5.9797983))]
+    srow = cases.sextant_row(113)
+    assert _same(hc.heights(srow, *cases.EXACT_AMPLITUDE), srow)
+    for k, (z_lo, z_hi) in enumerate(pairs.values()):
+        block = srow[16 * k:16 * k + 16]
+        assert block[7] == z_lo and block[8] == z_hi and (np.diff(block.view(np.uint32).astype(np.int64)) == 1).all()
+    rows = cases.surface_edge_rows(24)
+    for ref, rng_db in cases.SURFACE_AMPLITUDES:
+        for v in (ref - rng_db, ref):
+            f = np.float32(v)
+            for x in (f, np.nextafter(f, np.float32(-np.inf)), np.nextafter(f, np.float32(np.inf))):
+                assert (rows[0] == x).any() and (rows[1] == x).any()
+        t = hc.surface_normalise(rows, ref - rng_db, ref)
+        assert not np.isnan(t).any() and (t == 0).any() and (t == 1).any()
+    assert np.isposinf(rows[0]).any() and np.isneginf(rows[0]).any() and np.isfinite(rows[1]).all()
+    assert ((rows[0] == 0) & np.signbit(rows[0])).any()
+
+
+def test_nan_cases_name_the_lane_elements():
+    assert cases.lane_width(cases.NAN_N) == 4
+    assert [b % 4 for b in cases.NAN_BINS[:2]] == [0, 2] and cases.NAN_BINS[2] == cases.NAN_N - 1
+    n, n_rows, depth = cases.NAN_CHUNK
+    assert (n, n_rows) in cases.CHUNK_SHAPES and depth in cases.CHUNK_DEPTHS and cases.lane_width(n) == 4
+    assert [cases.cell_of(1000, 7, j) for j in (0, 141, 142, 999)] == [0, 0, 1, 6]

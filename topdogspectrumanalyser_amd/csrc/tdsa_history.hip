@@ -308,7 +308,7 @@ hipError_t launch_hist_push(const HistPush& a0, hipStream_t s) {
   const bool vec = a.n % 4 == 0 && aligned16(a.in) && (!a.hold_in || aligned16(a.hold_in)) && (!a.min_in || aligned16(a.min_in));
   const int V = vec ? 4 : 1;
   const unsigned gx = blocks_for((unsigned long long)(a.n / V));
-  unsigned gy = 2048 / gx < 1 ? 1 : 2048 / gx;
+  unsigned gy = kHistPushMaxWgs / gx < 1 ? 1 : kHistPushMaxWgs / gx;
   if (gy > unsigned(a.n_rows)) gy = unsigned(a.n_rows);
   a.rows_per_wg = int((unsigned(a.n_rows) + gy - 1) / gy);
   gy = (unsigned(a.n_rows) + unsigned(a.rows_per_wg) - 1) / unsigned(a.rows_per_wg);

@@ -10,6 +10,7 @@ constexpr long long kHistMaxCells = 1ll << 28;   // depth * n_bins: ring indices
 constexpr int kHistRibbonRows = 30;
 constexpr int kHistHues = 11;
 constexpr int kHistNeverPushed = 255;            // colour index of a line no row has reached: RGBA 0
+constexpr int kHistPushMaxWgs = 2048;            // workgroups of one push; more rows than 2048 / (column pieces): row chunks
 
 // Rows of a view, newest first.  linear = 0: row r of the view is ring slot (head - 1 - first - r) mod depth;
 // linear = 1: `base` is [rows][n] already in view order (the output of the reduction).
